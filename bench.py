@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the per-step optimisation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints the result line.  --full adds
+what else the benchmark measures: the per-op profile and roofline of the step, the L-BFGS update
+alone, the 1024x1024 and fp32 legs, images in flight and the CPU baseline (--no-extra and
+--no-cpu-baseline trim those).  --dump-outputs DIR writes, after the timed steps, what the timed
+path returned in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all).
 
 One "step" = one ``optimizer.step(closure)`` of the reference loop
 (optimization.py:175): VGG19 forward + Gram/content losses + backward to the
@@ -138,12 +144,35 @@ def forward_bytes(sched, dtype_bytes: int) -> float:
 
 
 HISTORY_SIZE = 100
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each array as out_dir/<name>.npy (float32, or float64 as computed).  Past DUMP_LIMIT_BYTES in all, the
+    largest arrays are replaced by a fixed sample: every k-th element of the flattened array, the same k and offset
+    in every run with the same arguments."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        if total <= DUMP_LIMIT_BYTES:
+            break
+        a = arrays[name]
+        keep = max(1, (a.nbytes - (total - DUMP_LIMIT_BYTES)) // a.itemsize)
+        stride = -(-a.size // keep)
+        arrays[name] = a.reshape(-1)[int(np.random.default_rng(0).integers(stride))::stride].copy()
+        total -= a.nbytes - arrays[name].nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def run_gpu(args, rank: int, world: int, device: torch.device, size: int, steps: int, warmup: int, *,
-            precision: str | None = None, profile: bool = True, prefill_history: bool = True):
+            precision: str | None = None, profile: bool = True, prefill_history: bool = True,
+            lbfgs_probe: bool = True, keep_outputs: bool = False):
     """One L-BFGS run of `warmup` untimed + `steps` timed optimisation steps through the real
-    OptimizationRunner; returns elapsed seconds of the timed region (+ the kernel breakdown on rank 0)."""
+    OptimizationRunner; returns elapsed seconds of the timed region (+ the kernel breakdown on rank 0,
+    + with keep_outputs the final image(s) and last step's losses, on rank 0, under "outputs")."""
     import torch.distributed as dist
 
     from style_transfer_visualizer_amd import _lib, config as stv_config
@@ -194,9 +223,13 @@ def run_gpu(args, rank: int, world: int, device: torch.device, size: int, steps:
     runner = optimization.OptimizationRunner(
         model, x, cfg, optimizer=opt, progress_bar=_Bar(),
         callbacks=optimization.OptimizationCallbacks(on_step_end=on_end))
-    out, _history, _ = runner.run()
+    out, history, _ = runner.run()
     elapsed = marks["t1"] - marks["t0"]
     elapsed_rank = marks["t1_own"] - marks["t0"]       # this rank's K steps alone (the line's time is the max over ranks, fences included)
+    # what the caller of the timed path receives for its last step: the image and that step's (style, content, total)
+    images = [out.detach()]
+    losses = torch.tensor([[history[k][-1] for k in ("style_loss", "content_loss", "total_loss")]], dtype=torch.float64) \
+        if keep_outputs else None
     if world > 1:
         from style_transfer_visualizer_amd import parallel
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -205,11 +238,18 @@ def run_gpu(args, rank: int, world: int, device: torch.device, size: int, steps:
         # the only data collective of the job: gather the independent results (RCCL over xGMI)
         gathered = parallel.gather_results([(rank, out.detach().contiguous())], world)
         assert len(gathered) == world and all(g is not None for g in gathered)
+        images = gathered
+        if keep_outputs:
+            parts = [torch.empty(1, 3, dtype=torch.float64, device=device) for _ in range(world)]
+            dist.all_gather(parts, losses.to(device))
+            losses = torch.cat(parts).cpu()
 
     info = {"elapsed": elapsed, "elapsed_rank": elapsed_rank, "prefill": prefill}
+    if keep_outputs and rank == 0:
+        info["outputs"] = {"image": torch.cat(images).float().cpu().numpy(), "losses": losses.numpy()}
     st = opt.device_state() if hasattr(opt, "device_state") else {}
     info["lbfgs"] = {k: st.get(k) for k in ("n_iter", "hist_len", "skip", "no_update")}
-    if rank == 0 and hasattr(opt, "device_state"):
+    if rank == 0 and lbfgs_probe and hasattr(opt, "device_state"):
         # the optimizer update alone, at the history length the timed region ended with: 20 updates with the last
         # gradient inside one event pair.  Algorithmic bytes: two sweeps over the 2m history vectors + 8 vectors.
         from style_transfer_visualizer_amd import ops
@@ -419,8 +459,12 @@ def run_spatial(args, rank: int, world: int, device: torch.device) -> dict:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    return {"elapsed": elapsed, "rows": rows, "mode": mode, "scores": [float(v) for v in shard.last_scores.cpu()],
+    info = {"elapsed": elapsed, "rows": rows, "mode": mode, "scores": [float(v) for v in shard.last_scores.cpu()],
             "route": getattr(shard, "route", "eager")}
+    if args.dump_outputs:
+        image = x if args.spatial_mode == "recompute" else shard.gather_image()     # (a collective when world > 1)
+        info["outputs"] = {"image": image.detach().float().cpu().numpy(), "losses": shard.last_scores.double().cpu().numpy()}
+    return info
 
 
 def cpu_baseline(size: int, threads: int) -> dict:
@@ -530,10 +574,15 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-op profile and roofline, the L-BFGS update "
+                         "alone, the extra legs and the CPU baseline (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (image, losses) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the additional legs (1024x1024, steady state at m=100, fp32 parity mode)")
-    ap.add_argument("--per-op", default=None, help="append a per-op device-time table to this file")
+                    help="with --full: skip the additional legs (1024x1024, steady state at m=100, fp32 parity mode)")
+    ap.add_argument("--per-op", default=None, help="append a per-op device-time table to this file (runs the profile pass)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo only to rehearse N>1 on a single GPU")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
@@ -567,6 +616,8 @@ def main() -> None:
 
     if args.spatial:
         info = run_spatial(args, rank, world, device)
+        if rank == 0 and args.dump_outputs:
+            write_outputs(args.dump_outputs, info.pop("outputs"))
         if rank == 0:
             print(json.dumps({
                 "metric": "optimization steps/sec, single 3840x2160 image", "value": round(args.steps / info["elapsed"], 3),
@@ -587,7 +638,10 @@ def main() -> None:
     # of a multi-GPU line is therefore the 1024x1024 workload; 512x512 (configs[1]) runs as an extra leg on the same ranks.
     # N = 1 keeps configs[1] (512x512) as the headline and carries 1024x1024 as `extra_1024` / `roofline.step_1024`.
     head_size = args.size if (world == 1 or args.size != 512) else 1024
-    info = run_gpu(args, rank, world, device, head_size, args.steps, args.warmup)
+    info = run_gpu(args, rank, world, device, head_size, args.steps, args.warmup, profile=bool(args.full or args.per_op),
+                   lbfgs_probe=args.full, keep_outputs=bool(args.dump_outputs))
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, info.pop("outputs"))
     per_rank = [info["elapsed_rank"]]
     if world > 1:
         import torch.distributed as dist
@@ -599,11 +653,12 @@ def main() -> None:
     extra_512 = None
     steady = None
     fp32 = None
-    if world > 1 and head_size != args.size and not args.no_extra:
+    extras = args.full and not args.no_extra
+    if world > 1 and head_size != args.size and extras:
         e = run_gpu(args, rank, world, device, 512, args.steps, args.warmup, profile=False)
         extra_512 = {"workload": "single 512x512 image per GPU (BASELINE configs[1]), same ranks", "steps": args.steps,
                      "value": round(args.steps * world / e["elapsed"], 3), "ms_per_step": round(1e3 * e["elapsed"] / args.steps, 4)}
-    if not args.no_extra and args.size == 512 and world == 1:
+    if extras and args.size == 512 and world == 1:
         k2, w2 = max(10, args.steps // 4), max(5, min(args.warmup, 100))
         e1024 = run_gpu(args, rank, world, device, 1024, k2, w2)
         extra = {"workload": "single 1024x1024 image (BASELINE configs[2])", "steps": k2, "warmup": w2,
@@ -624,7 +679,7 @@ def main() -> None:
                                                "timed_steps": STEADY_STEPS, "precision": "fp32"}}
 
     in_flight = None
-    if not args.no_extra and args.size == 512 and world == 1 and rank == 0:
+    if extras and args.size == 512 and world == 1 and rank == 0:
         # several independent images on the one GPU (main.style_transfer_batch's default is 2 in flight)
         legs = [run_in_flight(device, 512, 2, 150), run_in_flight(device, 512, 3, 150), run_in_flight(device, 1024, 2, 60)]
         in_flight = {"note": ("independent images in flight on ONE GPU, one host thread + stream each: one image's L-BFGS update "
@@ -708,7 +763,7 @@ def main() -> None:
             line["images_in_flight"] = in_flight
             if roof is not None:            # the driver's record keeps `roofline`: the aggregate figures go there too
                 roof["images_in_flight_steps_per_s"] = {f"{g['size']}x{g['size']} x{g['images']}": g["aggregate_steps_per_s"] for g in in_flight["legs"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = host_cpu()
             # BASELINE.md §4 asks for the node's physical cores; on a many-core host the reference's CPU path is
             # not fastest there (small convolutions, 128 threads), so a short probe also tries 64, 32, 16 and 8 threads and
@@ -720,7 +775,7 @@ def main() -> None:
             cpu["probe_steps_per_s"] = {str(k): round(v, 3) for k, v in probe.items()}
             line["host_cpu"] = cpu
             line["cpu_baseline"] = cpu_baseline(args.size, threads)
-            if not args.no_extra and args.size == 512:      # the other two sizes beside it
+            if extras and args.size == 512:      # the other two sizes beside it
                 line["cpu_baseline_other_sizes"] = {"256x256": cpu_baseline(256, threads),
                                                     "1024x1024": cpu_baseline(1024, threads)}
         print(json.dumps(line))

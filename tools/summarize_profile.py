@@ -1,8 +1,8 @@
 """Condense rocprofv3 output (gpurun_out/<prefix>_*) into small, committed files under profiles/.
 
 usage: python tools/summarize_profile.py <tag> <prefix>
-  expects <prefix>_s{512,1024}  : rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py ...
-          <prefix>_f{512,1024}  : rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --steps 3 --warmup 2
+  expects <prefix>_s{512,1024}  : rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full ...
+          <prefix>_f{512,1024}  : rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --full --steps 3 --warmup 2
           <prefix>_w{512,1024}  : the same with --pmc WRITE_SIZE  (the two counters do not fit one pass)
 writes   profiles/<tag>_kernel_stats_{512,1024}.csv and profiles/<tag>_pmc_hbm_{512,1024}.json
 """
