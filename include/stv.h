@@ -30,7 +30,14 @@
 extern "C" {
 #endif
 
-enum { STV_F32 = 0, STV_BF16 = 1 };
+/* STV_BF16X3: fp32 storage (exactly as STV_F32), split-bf16 products - every product of a conv or Gram contraction
+ * is formed as ah*bh + ah*bl + al*bh on the bf16 matrix cores (hi = bf16(x), lo = bf16(x - hi)), fp32 accumulation.
+ * Accepted only by the entry points that form products: stv_conv_igemm, stv_conv_igemm_pool, stv_conv_igemm_dual,
+ * stv_conv_config, stv_conv_tune, stv_conv_uses_ws (always 0), stv_gram_partial and stv_gram_multi; every other
+ * entry point returns STV_ERR_ARG for it.  K-blocked conv weights (STV_W_BLOCKED) are pre-split: each 16-byte group of
+ * four fp32 weights holds their four bf16 hi parts, then their four bf16 lo parts (same byte count); plain-layout
+ * weights are fp32 and split in the kernel: a 3x3 takes K-blocked weights only, a 1x1 plain weights only.  Size guards count bytes: every tensor stays below 2 GiB. */
+enum { STV_F32 = 0, STV_BF16 = 1, STV_BF16X3 = 2 };
 
 enum {
   STV_OK = 0,
@@ -116,6 +123,8 @@ int stv_conv_first_fwd_gram(const float* x_nchw, const float* packed, const floa
  * taps = STV_TUNE_ROUTE (bf16): the shape is measured as stv_conv_igemm_route runs it (dgrad + pooling backward in
  * the epilogue, 2H x 2W output) and remembered under its own key - the routed epilogue prefers smaller tiles. */
 #define STV_TUNE_ROUTE 109
+/* the `element bytes` field of a tile-table entry for a STV_BF16X3 shape: its own key, fp32 tiles */
+#define STV_TUNE_BF16X3 6
 int stv_conv_tune(int H, int W, int cin, int cout, int taps, int dtype, void* stream);
 /* The tile table as data (7 ints per entry: H, W, cin, cout, taps - 9, 1 or STV_TUNE_ROUTE -, element bytes, tile
  * index).  Measuring only happens with STV_CONV_TUNE=1 (or 2) in the environment; otherwise stv_conv_tune and every

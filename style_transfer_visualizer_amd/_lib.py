@@ -12,7 +12,8 @@ from ctypes import c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STV_LIB_PATH") or os.path.join(_HERE, "libstv_hip.so")   # override: diagnostic builds
 
-STV_F32, STV_BF16 = 0, 1
+STV_F32, STV_BF16, STV_BF16X3 = 0, 1, 2     # STV_BF16X3: fp32 storage, split-bf16 products
+TUNE_BF16X3 = 6     # stv.h STV_TUNE_BF16X3: the `elem_bytes` key of a bf16x3 tile-table entry
 RELU_IN, RELU_OUT, MASK, ACCUM, W_BLOCKED, POOL_IDX, POOL_ROUTE, POOL_ONLY = 1, 2, 4, 8, 16, 32, 64, 128
 LANE_SIDE, LANE_JOIN = 1 << 29, 1 << 30          # scheduling hints of the command-buffer executor
 

@@ -1,7 +1,7 @@
 """``style-visualizer`` command line: same flags and override rules as reference cli.py:26-354.
 
 Options that only have meaning for presentation features outside this build (comparison grids)
-are accepted and reported as unavailable.  One addition: ``--precision {fp32,bf16}``.
+are accepted and reported as unavailable.  One addition: ``--precision {fp32,bf16,bf16x3}``.
 """
 from __future__ import annotations
 
@@ -66,8 +66,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
 
     hw = p.add_argument_group("hardware")
     hw.add_argument("--device", type=str, default=S, help="Device to run on (cuda = MI355X under ROCm)")
-    hw.add_argument("--precision", choices=["fp32", "bf16"], default=S,
-                    help="Activation storage: fp32 (parity mode) or bf16 (fp32 accumulate)")
+    hw.add_argument("--precision", choices=["fp32", "bf16", "bf16x3"], default=S,
+                    help="Activation storage: fp32 (parity mode), bf16 (fp32 accumulate) or bf16x3 "
+                         "(fp32 storage, conv/Gram products from split bf16 operands)")
 
     cfg = p.add_argument_group("configuration")
     cfg.add_argument("--config", type=str, help="Path to config.toml")

@@ -2,7 +2,7 @@
 
 Field names, bounds and override precedence follow reference config.py:53-309
 so existing ``config.toml`` files and CLI invocations keep working.  The one
-addition is ``hardware.precision`` ("fp32" parity mode | "bf16" storage).
+addition is ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf16x3" fp32 storage, split-bf16 products).
 """
 from __future__ import annotations
 

@@ -25,7 +25,9 @@ from .constants import GRAM_MATRIX_CLAMP_MAX
 from .logging_utils import logger
 
 VGG19_WEIGHTS_URL = "https://download.pytorch.org/models/vgg19-dcbb9e9d.pth"
-_PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16}
+# storage dtype per precision; "bf16x3" stores fp32 and forms the conv / Gram products from split bf16 operands
+_PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "bf16x3": torch.float32}
+_SPLIT_PRECISIONS = frozenset({"bf16x3"})
 
 # The two torchvision names the reference imports at module level (core_model.py:12) and its tests patch.  Without
 # torchvision (this image) ``vgg19`` is None - ``initialize_vgg`` then builds the same stack itself and loads the
@@ -43,13 +45,22 @@ except ImportError:
         DEFAULT = IMAGENET1K_V1
 
 
-def resolve_precision(precision: str | None = None) -> torch.dtype:
-    """Activation storage dtype: fp32 = parity mode (default), bf16 = performance mode."""
+def _precision_name(precision: str | None) -> str:
     name = precision or os.environ.get("STV_PRECISION", "fp32")
     if name not in _PRECISIONS:
         msg = f"Unsupported precision: {name} (expected one of {sorted(_PRECISIONS)})"
         raise ValueError(msg)
-    return _PRECISIONS[name]
+    return name
+
+
+def resolve_precision(precision: str | None = None) -> torch.dtype:
+    """Activation storage dtype: fp32 = parity mode (default), bf16 = performance mode, bf16x3 = fp32 storage."""
+    return _PRECISIONS[_precision_name(precision)]
+
+
+def resolve_split(precision: str | None = None) -> bool:
+    """True for bf16x3: conv and Gram products formed as ah*bh + ah*bl + al*bh on the bf16 matrix cores."""
+    return _precision_name(precision) in _SPLIT_PRECISIONS
 
 
 # --------------------------------------------------------------------------- gram
@@ -299,10 +310,11 @@ class _Engine:
     """Buffers + command buffers for one (model, image size, device)."""
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
-                 H: int, W: int, dtype: torch.dtype, device: torch.device) -> None:
+                 H: int, W: int, dtype: torch.dtype, device: torch.device, *, split: bool = False) -> None:
         self.layers, self.style_at, self.content_at = layers, style_at, content_at
         self.H, self.W, self.dtype, self.device = H, W, dtype, device
-        self.sched = plan.Schedule(layers, style_at, content_at, H, W, dtype, device, with_grad=True)
+        self.split = split
+        self.sched = plan.Schedule(layers, style_at, content_at, H, W, dtype, device, with_grad=True, split=split)
         s = self.sched
         self.n_style, self.n_content = len(s.style_taps), len(s.content_taps)
         n_terms = self.n_style + self.n_content
@@ -490,7 +502,7 @@ class _Engine:
         Hs, Ws = x.shape[-2:]
         sched = (self.sched if (Hs, Ws) == (self.H, self.W) else
                  plan.Schedule(self.layers, self.style_at, self.content_at, Hs, Ws, self.dtype, self.device,
-                               with_grad=False))
+                               with_grad=False, split=self.split))
         grams = []
 
         def build():
@@ -656,6 +668,7 @@ class StyleContentModel(nn.Module):
         self._style_at = sorted(set(style_layers))
         self._content_at = sorted(set(content_layers))
         self._dtype = resolve_precision(precision)
+        self._split = resolve_split(precision)       # bf16x3: fp32 storage (self._dtype), split-bf16 products
         self._engines: dict = {}
 
     # -- engine plumbing ---------------------------------------------------------
@@ -690,7 +703,7 @@ class StyleContentModel(nn.Module):
         key = (H, W, x.device.index)
         eng = self._engines.get(key)
         if eng is None:
-            eng = _Engine(self._layers(), self._style_at, self._content_at, H, W, self._dtype, x.device)
+            eng = _Engine(self._layers(), self._style_at, self._content_at, H, W, self._dtype, x.device, split=self._split)
             self._engines[key] = eng
         return eng
 
@@ -767,7 +780,8 @@ def prepare_model_and_input(
 ) -> tuple[nn.Module, torch.Tensor, torch.optim.Optimizer]:
     """Build model, start image and optimizer (reference core_model.py:331-350).
 
-    ``precision`` (keyword-only extension): "fp32" | "bf16" activation storage;
+    ``precision`` (keyword-only extension): "fp32" | "bf16" activation storage, or "bf16x3"
+    (fp32 storage, conv / Gram products from split bf16 operands);
     default from ``STV_PRECISION`` or fp32.
     """
     from .optimizers import make_lbfgs  # noqa: PLC0415

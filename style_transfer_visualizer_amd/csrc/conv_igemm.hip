@@ -136,6 +136,8 @@ struct TuneEntry { int H, W, cin, cout, taps, esize, cfg; };
 std::mutex g_tune_mu;
 std::vector<TuneEntry> g_tune;
 
+// table key of a bf16x3 shape (the `esize` field): fp32 storage, its own tile choices
+constexpr int kX3Key = STV_TUNE_BF16X3;
 int tuned_cfg(int H, int W, int cin, int cout, int taps, int esize) {
   std::lock_guard<std::mutex> lk(g_tune_mu);
   for (const TuneEntry& e : g_tune)
@@ -168,7 +170,10 @@ int model_cfg(int H, int W, int cin, int cout) {
 // the plain conv's pick; 256^2 256->128 48 against 59 on 8x128), so it is measured as its own "shape".
 constexpr int kRouteTaps = STV_TUNE_ROUTE;
 
+// elem_bytes: 2 (bf16), 4 (fp32) or kX3Key (bf16x3: fp32 storage, so the fp32 tiles and granularity)
 int choose_cfg(int H, int W, int cin, int cout, int elem_bytes, int taps = 9) {
+  const int key = elem_bytes;
+  if (elem_bytes == kX3Key) elem_bytes = 4;
   const int kVec = 16 / elem_bytes, CK = 32 / elem_bytes;
   if ((cin % CK) || (cout % kVec)) return -1;
   auto served = [&](int cfg) { return (elem_bytes == 4 || (is_m16(cfg) && cin % 32)) ? fp32_cfg(cfg) : cfg; };
@@ -179,14 +184,30 @@ int choose_cfg(int H, int W, int cin, int cout, int elem_bytes, int taps = 9) {
   // STV_CONV_TUNE=0 pins the analytic choice even when another caller in this process has
   // measured the shape already (tests that assert near fp32 rounding want one summation order)
   const char* tune = getenv("STV_CONV_TUNE");
-  const int t = (tune && atoi(tune) == 0) ? -1 : tuned_cfg(H, W, cin, cout, taps, elem_bytes);
+  const int t = (tune && atoi(tune) == 0) ? -1 : tuned_cfg(H, W, cin, cout, taps, key);
   if (t >= 0) return served(t);
   const int m = model_cfg(H, W, cin, cout);
   return served((taps == kRouteTaps && (m == 0 || m == 2)) ? 3 : m);       // untuned routed dgrad: 4x64 where the model says 128-wide
 }
 
-template <typename T, int TAPS>
+// bf16x3: the fp32 tiles (fp32_cfg's range) with split-bf16 products
+template <int TAPS>
+int launch_mfma_x3(const ConvArgs& a, int cfg, hipStream_t st) {
+  switch (fp32_cfg(cfg)) {
+    case 1: return launch_cfg<Cfg<float, 8, 64, 4, 2, TAPS, 1, 3, false, true>>(a, st);
+    case 2: return launch_cfg<Cfg<float, 4, 128, 1, 4, TAPS, 1, 3, false, true>>(a, st);
+    case 4: return launch_cfg<Cfg<float, 4, 64, 2, 2, TAPS, 2, 3, false, true>>(a, st);
+    case 5: return launch_cfg<Cfg<float, 8, 64, 4, 2, TAPS, 1, 2, false, true>>(a, st);
+    case 6: return launch_cfg<Cfg<float, 4, 64, 2, 2, TAPS, 1, 2, false, true>>(a, st);
+    case 7: return launch_cfg<Cfg<float, 2, 64, 2, 2, TAPS, 2, 3, false, true>>(a, st);
+    case 8: return launch_cfg<Cfg<float, 1, 64, 1, 2, TAPS, 2, 3, false, true>>(a, st);
+    default: return launch_cfg<Cfg<float, 4, 64, 2, 2, TAPS, 1, 3, false, true>>(a, st);
+  }
+}
+
+template <typename T, int TAPS, bool X3 = false>
 int launch_mfma(const ConvArgs& a, int cfg, hipStream_t st) {
+  if constexpr (X3) return launch_mfma_x3<TAPS>(a, cfg, st);
   if (is_m16(cfg)) {      // two K-stages per MFMA: bf16, whole pairs of 16-channel stages in both K extents
     if (sizeof(T) == 2 && a.cin % 32 == 0 && (a.x2 == nullptr || a.cin2 % 32 == 0)) return stv_conv_launch_m16(a, cfg, TAPS, st);
     cfg = fp32_cfg(cfg);
@@ -264,6 +285,29 @@ int launch_typed(const ConvArgs& a, hipStream_t st) {
   return launch_mfma<T, TAPS>(a, cfg, st);
 }
 
+// bf16x3 (fp32 storage, split-bf16 products): the matrix-core tiles only - a shape they do not cover is an error,
+// not a quiet fall-back to the direct kernel - and no weight-stationary / K-split variants (bf16 only).
+template <int TAPS>
+int launch_x3(const ConvArgs& a, hipStream_t st) {
+  int cfg = choose_cfg(a.H, a.W, a.cin, a.cout, kX3Key, TAPS);
+  if (cfg < 0) return STV_ERR_ARG;
+  if ((cfg == 7 || cfg == 8) && a.pool != nullptr) cfg = 4;      // one row per wave: no pooling window
+  return launch_mfma_x3<TAPS>(a, cfg, st);
+}
+
+// bf16x3 weight forms are fixed per geometry (conv_mainloop: no per-load choice in the loop): a 3x3 takes K-blocked,
+// pre-split weights (STV_W_BLOCKED), a 1x1 - the Gram-backward product, whose weights are the seed S written every
+// step - plain fp32 weights that the kernel splits.
+bool x3_weights_ok(int taps, int flags) { return (taps == 9) == ((flags & STV_W_BLOCKED) != 0); }
+
+// The byte guard of the bf16x3 entry points: every tensor the kernel addresses through a 32-bit buffer descriptor
+// (input, output, reference map, weights, the second term's input and seed) must stay below 2 GiB in BYTES.
+bool x3_fits(int H, int W, int cin, int cout, int taps, int cin2 = 0) {
+  constexpr size_t kLimit = (size_t)1 << 31;
+  const size_t px = (size_t)H * W, cmax = (size_t)(cin > cout ? cin : cout) > (size_t)cin2 ? (size_t)(cin > cout ? cin : cout) : (size_t)cin2;
+  return px * cmax * 4 < kLimit && (size_t)taps * cin * cout * 4 < kLimit && (size_t)cin2 * cout * 4 < kLimit;
+}
+
 __global__ void tune_fill_kernel(uint32_t* p, size_t n_words, uint32_t seed) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_words) return;
@@ -291,8 +335,9 @@ struct NextWeightsQuiet {
   ~NextWeightsQuiet() { g_stv_next_w = w; g_stv_next_w_bytes = bytes; }
 };
 
-template <typename T>
+template <typename T, bool X3 = false>
 int tune_typed(int H, int W, int cin, int cout, int key_taps, hipStream_t st) {
+  const int key = X3 ? kX3Key : (int)sizeof(T);
   const NextWeightsQuiet quiet;
   const bool route = key_taps == kRouteTaps;       // (bf16 only: the caller checked)
   const int taps = route ? 9 : key_taps;
@@ -302,7 +347,7 @@ int tune_typed(int H, int W, int cin, int cout, int key_taps, hipStream_t st) {
   const size_t bi = route ? ((size_t)H * W * cout + 255) / 256 * 256 : 0;       // arg-max byte map
   if (hipMalloc(reinterpret_cast<void**>(&buf), bx + bw + bi + ny * sizeof(T)) != hipSuccess) {
     (void)hipGetLastError();                       // no room for scratch copies: keep the analytic choice
-    return choose_cfg(H, W, cin, cout, (int)sizeof(T), key_taps);
+    return choose_cfg(H, W, cin, cout, key, key_taps);
   }
   const size_t words = (bx + bw + bi) / 4;         // (random map bytes: codes 0..255, the routing compares and masks as usual)
   hipLaunchKernelGGL(tune_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st,
@@ -358,11 +403,11 @@ int tune_typed(int H, int W, int cin, int cout, int key_taps, hipStream_t st) {
       if (!cfg_valid(cfg, cout) || (sizeof(T) == 4 && fp32_cfg(cfg) != cfg)) continue;
       const int kWarm = 2, kReps = flushbuf ? 6 : 10;
       for (int i = 0; i < kWarm && rc == STV_OK; ++i)
-        rc = taps == 9 ? launch_mfma<T, 9>(a, cfg, st) : launch_mfma<T, 1>(a, cfg, st);
+        rc = taps == 9 ? launch_mfma<T, 9, X3>(a, cfg, st) : launch_mfma<T, 1, X3>(a, cfg, st);
       (void)hipEventRecord(e0, st);
       for (int i = 0; i < kReps && rc == STV_OK; ++i) {
         flush();
-        rc = taps == 9 ? launch_mfma<T, 9>(a, cfg, st) : launch_mfma<T, 1>(a, cfg, st);
+        rc = taps == 9 ? launch_mfma<T, 9, X3>(a, cfg, st) : launch_mfma<T, 1, X3>(a, cfg, st);
       }
       (void)hipEventRecord(e1, st);
       if (hipEventSynchronize(e1) != hipSuccess) rc = STV_ERR_LAUNCH;
@@ -384,22 +429,24 @@ int tune_typed(int H, int W, int cin, int cout, int key_taps, hipStream_t st) {
   if (best != base && t_best > 0.97f * t_base) best = base;
   std::lock_guard<std::mutex> lk(g_tune_mu);
   for (TuneEntry& e : g_tune)
-    if (e.H == H && e.W == W && e.cin == cin && e.cout == cout && e.taps == key_taps && e.esize == (int)sizeof(T)) {
+    if (e.H == H && e.W == W && e.cin == cin && e.cout == cout && e.taps == key_taps && e.esize == key) {
       e.cfg = best;
       return best;
     }
-  g_tune.push_back(TuneEntry{H, W, cin, cout, key_taps, (int)sizeof(T), best});
+  g_tune.push_back(TuneEntry{H, W, cin, cout, key_taps, key, best});
   return best;
 }
 
 }  // namespace
 
 extern "C" int stv_conv_config(int H, int W, int cin, int cout, int taps, int dtype) {
+  if (dtype == STV_BF16X3) return (taps == 9 || taps == 1) ? choose_cfg(H, W, cin, cout, kX3Key, taps) : -1;
   return choose_cfg(H, W, cin, cout, dtype == STV_BF16 ? 2 : 4, taps);
 }
 
 extern "C" int stv_conv_uses_ws(int H, int W, int cin, int cout, int taps, int dtype, int flags, int has_ref, int has_pool) {
   static const char dummy = 0;
+  if (dtype == STV_BF16X3) return 0;           // the weight-stationary kernels are bf16 only
   ConvArgs a{&dummy, &dummy, nullptr, has_ref ? &dummy : nullptr, const_cast<char*>(&dummy), H, W, cin, cout, flags,
              has_pool ? const_cast<char*>(&dummy) : nullptr, nullptr, has_ref ? &dummy : nullptr, has_ref ? &dummy : nullptr,
              has_ref ? cout : 0};      // (cin2 = the layer's own channel count: the Gram term of its tap)
@@ -432,7 +479,8 @@ extern "C" int stv_conv_tune_import(const int* in7, int n_entries) {
   }
   for (int i = 0; i < n_entries; ++i) {
     const int* e = in7 + 7 * i;
-    if (e[0] <= 0 || e[1] <= 0 || e[2] <= 0 || e[3] <= 0 || (e[5] != 2 && e[5] != 4) || !cfg_valid(e[6], e[3])) return STV_ERR_ARG;
+    if (e[0] <= 0 || e[1] <= 0 || e[2] <= 0 || e[3] <= 0 || (e[5] != 2 && e[5] != 4 && e[5] != kX3Key) || !cfg_valid(e[6], e[3])) return STV_ERR_ARG;
+    if (e[5] == kX3Key && (fp32_cfg(e[6]) != e[6] || e[4] == kRouteTaps)) return STV_ERR_ARG;
     if (e[4] != 9 && e[4] != 1 && e[4] != kRouteTaps) return STV_ERR_ARG;
   }
   std::lock_guard<std::mutex> lk(g_tune_mu);
@@ -448,8 +496,17 @@ extern "C" int stv_conv_tune_import(const int* in7, int n_entries) {
 
 extern "C" int stv_conv_tune(int H, int W, int cin, int cout, int taps, int dtype, void* stream) {
   if (H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || (taps != 9 && taps != 1 && taps != kRouteTaps)) return -(100 + STV_ERR_ARG);
-  if (dtype != STV_F32 && dtype != STV_BF16) return -(100 + STV_ERR_ARG);
+  if (dtype != STV_F32 && dtype != STV_BF16 && dtype != STV_BF16X3) return -(100 + STV_ERR_ARG);
   if (taps == kRouteTaps && dtype != STV_BF16) return -(100 + STV_ERR_ARG);
+  if (dtype == STV_BF16X3) {
+    if (!x3_fits(H, W, cin, cout, taps)) return -(100 + STV_ERR_ARG);
+    if (cin % 8 || cout % 4) return -1;
+    const char* mode = getenv("STV_CONV_TUNE");
+    if (!mode || atoi(mode) <= 0) return choose_cfg(H, W, cin, cout, kX3Key, taps);
+    const int known = tuned_cfg(H, W, cin, cout, taps, kX3Key);
+    if (known >= 0) return known;
+    return tune_typed<float, true>(H, W, cin, cout, taps, static_cast<hipStream_t>(stream));
+  }
   if ((size_t)H * W * (size_t)(cin > cout ? cin : cout) >= (size_t)1 << 31) return -(100 + STV_ERR_ARG);
   if (taps == kRouteTaps && (size_t)4 * H * W * (size_t)cout * 2 >= (size_t)1 << 31) return -(100 + STV_ERR_ARG);
   const int esize = dtype == STV_BF16 ? 2 : 4;
@@ -471,6 +528,12 @@ extern "C" int stv_conv_igemm(const void* x, const void* w, const float* bias, c
   if ((flags & STV_MASK) && !ref) return STV_ERR_ARG;
   if (flags & STV_POOL_ONLY) return STV_ERR_ARG;          // only stv_conv_igemm_pool has a pooled map to write instead of y
   if (taps != 9 && taps != 1) return STV_ERR_ARG;
+  if (dtype == STV_BF16X3) {
+    if (!x3_fits(H, W, cin, cout, taps) || !x3_weights_ok(taps, flags)) return STV_ERR_ARG;
+    ConvArgs a{x, w, bias, ref, y, H, W, cin, cout, flags, nullptr, nullptr, nullptr, nullptr, 0};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return taps == 9 ? launch_x3<9>(a, st) : launch_x3<1>(a, st);
+  }
   // the direct fallback (shapes the matrix-core tiling does not cover) reads plain weights only
   if ((flags & STV_W_BLOCKED) && choose_cfg(H, W, cin, cout, dtype == STV_F32 ? 4 : 2, taps) < 0) return STV_ERR_ARG;
   if ((size_t)H * W * (size_t)(cin > cout ? cin : cout) >= (size_t)1 << 31) return STV_ERR_ARG;
@@ -490,6 +553,11 @@ extern "C" int stv_conv_igemm_pool(const void* x, const void* w, const float* bi
   if (!y && !(flags & STV_POOL_ONLY)) return STV_ERR_ARG;
   if (flags & (STV_MASK | STV_ACCUM)) return STV_ERR_ARG;                     // forward convolutions only
   if ((size_t)H * W * (size_t)(cin > cout ? cin : cout) >= (size_t)1 << 31) return STV_ERR_ARG;
+  if (dtype == STV_BF16X3) {
+    if (!x3_fits(H, W, cin, cout, 9) || !x3_weights_ok(9, flags) || choose_cfg(H, W, cin, cout, kX3Key, 9) < 0) return STV_ERR_ARG;
+    ConvArgs a{x, w, bias, nullptr, y, H, W, cin, cout, flags, y_pool, pool_idx, nullptr, nullptr, 0};
+    return launch_x3<9>(a, static_cast<hipStream_t>(stream));
+  }
   if (dtype != STV_F32 && dtype != STV_BF16) return STV_ERR_ARG;
   // the fused pool lives in the matrix-core kernel's epilogue: other shapes pool separately
   if (choose_cfg(H, W, cin, cout, dtype == STV_F32 ? 4 : 2, 9) < 0) return STV_ERR_ARG;
@@ -537,6 +605,12 @@ extern "C" int stv_conv_igemm_dual(const void* x, const void* w, const void* x2,
   if (!x || !w || !x2 || !w2 || !y || H <= 0 || W <= 0 || cin <= 0 || cin2 <= 0 || cout <= 0) return STV_ERR_ARG;
   if ((flags & STV_MASK) && !ref) return STV_ERR_ARG;
   if (flags & (STV_RELU_IN | STV_RELU_OUT | STV_POOL_ONLY)) return STV_ERR_ARG;   // a gradient path: no activations, no pooled output
+  if (dtype == STV_BF16X3) {
+    if (!x3_fits(H, W, cin, cout, 9, cin2) || !x3_weights_ok(9, flags) || choose_cfg(H, W, cin, cout, kX3Key, 9) < 0 || cin2 % 8)
+      return STV_ERR_ARG;
+    ConvArgs a{x, w, nullptr, ref, y, H, W, cin, cout, flags, nullptr, nullptr, x2, w2, cin2};
+    return launch_x3<9>(a, static_cast<hipStream_t>(stream));
+  }
   if (dtype != STV_F32 && dtype != STV_BF16) return STV_ERR_ARG;
   const size_t cmax = (size_t)(cin > cout ? cin : cout) > (size_t)cin2 ? (size_t)(cin > cout ? cin : cout) : (size_t)cin2;
   if ((size_t)H * W * cmax >= (size_t)1 << 31) return STV_ERR_ARG;

@@ -35,8 +35,12 @@ extern thread_local uint32_t g_stv_next_w_bytes;
 namespace {
 
 
-template <typename T, int TH_, int BN_, int WM_, int WN_, int TAPS_, int KS_ = 1, int NBUF_ = 3, bool M16_ = false>
+template <typename T, int TH_, int BN_, int WM_, int WN_, int TAPS_, int KS_ = 1, int NBUF_ = 3, bool M16_ = false,
+          bool X3_ = false>
 struct Cfg {
+  // X3: fp32 storage, split-bf16 products (STV_BF16X3).  The fp32 tile's LDS image and DMA pieces unchanged; only the
+  // fragment reads and the MFMAs differ (conv_mainloop: X3Act, mma_any).
+  static constexpr bool X3 = X3_;
   // M16: the main loop runs on v_mfma_f32_16x16x32_bf16 (bf16 only).  Same LDS image and DMA pieces, but two K-stages
   // (2 x 16 channels) are consumed together - lanes 0-31 of an operand read the first stage's slot, lanes 32-63 the
   // second's - from a ring of FOUR stage slots (two pairs), and the image is NOT swizzled: the 16-row fragments of
@@ -90,6 +94,7 @@ struct Cfg {
   static_assert(KS == 1 || KS == 2, "K split");
   static_assert(NBUF >= 2 && NBUF <= 6, "ring depth");
   static_assert(!M16 || (NBUF == 4 && sizeof(T) == 2), "16x16x32 main loop: bf16, two pairs of stage slots");
+  static_assert(!X3 || (sizeof(T) == 4 && !M16), "split-bf16 products: fp32 storage, 32x32 main loop");
   static_assert(TH % WM == 0 && BN % (WN * 32) == 0, "tile split");
   static_assert(BN % 16 == 0, "swizzle period");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
@@ -110,6 +115,53 @@ template <>
 __device__ __forceinline__ void mma<float>(const f32x4& a, const f32x4& b, f32x16& acc) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
+}
+
+// ---- split-bf16 products (Cfg::X3, STV_BF16X3) ----------------------------------------------------------------------
+// An fp32 value x is carried as hi = bf16_rne(x) and lo = bf16_rne(x - hi) (x - hi is exact in fp32); a product is
+// formed as wh*xh + wl*xh + wh*xl on v_mfma_f32_32x32x16_bf16, the dropped wl*xl and the rounding of lo are
+// ~2^-17 relative.  One fp32 K-stage fragment of a lane (4 channels, 16 bytes) becomes 8 bf16 k-values:
+//   weights     W = [wh0..3 | wl0..3]   (packed once at model build, ops.split_weights: the same 16 bytes)
+//   activation  P = [xh0..3 | xh0..3]   -> W.P = wh.xh + wl.xh
+//               Q = [xl0..3 |  0 .. 0]  -> W.Q = wh.xl
+// lo is zeroed where hi is not finite (Inf / NaN input, or a finite input that rounds to Inf), so a non-finite input
+// still gives a non-finite output through hi and never a NaN made by lo alone.
+struct X3Act { bf16x8v p, q; };
+
+__device__ __forceinline__ float bf16_hi_part(float x, uint32_t& bits) {
+  bits = (uint32_t)f32_to_bf16(x);        // RNE
+  return __uint_as_float(bits << 16);
+}
+// four floats -> packed hi (2 dwords) and lo (2 dwords), each dword = {element 2i (low half), element 2i+1}
+__device__ __forceinline__ void split4(f32x4 v, uint32_t (&hi)[2], uint32_t (&lo)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    uint32_t b0, b1;
+    const float h0 = bf16_hi_part(v[2 * i], b0), h1 = bf16_hi_part(v[2 * i + 1], b1);
+    const float r0 = __builtin_isfinite(h0) ? v[2 * i] - h0 : 0.0f;
+    const float r1 = __builtin_isfinite(h1) ? v[2 * i + 1] - h1 : 0.0f;
+    hi[i] = b0 | (b1 << 16);
+    lo[i] = pack_bf16x2(r0, r1);
+  }
+}
+__device__ __forceinline__ X3Act split_act(f32x4 v) {
+  uint32_t hi[2], lo[2];
+  split4(v, hi, lo);
+  const u32x4 p = {hi[0], hi[1], hi[0], hi[1]}, q = {lo[0], lo[1], 0u, 0u};
+  return X3Act{__builtin_bit_cast(bf16x8v, p), __builtin_bit_cast(bf16x8v, q)};
+}
+__device__ __forceinline__ bf16x8v split_w(f32x4 v) {
+  uint32_t hi[2], lo[2];
+  split4(v, hi, lo);
+  const u32x4 w = {hi[0], hi[1], lo[0], lo[1]};
+  return __builtin_bit_cast(bf16x8v, w);
+}
+// the main loop's product step for every fragment kind: (weights, activations) -> D[cout][pixel]
+__device__ __forceinline__ void mma_any(const f32x4& b, const f32x4& a, f32x16& acc) { mma<float>(b, a, acc); }
+__device__ __forceinline__ void mma_any(const bf16x8v& b, const bf16x8v& a, f32x16& acc) { mma<bf16_t>(b, a, acc); }
+__device__ __forceinline__ void mma_any(const bf16x8v& w, const X3Act& a, f32x16& acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a.p, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a.q, acc, 0, 0, 0);
 }
 
 // ReLU of a fragment as a packed integer max against `floor` (0: ReLU on, INT_MIN pattern: off)
@@ -155,7 +207,9 @@ template <typename C, bool RELU>
 __device__ __forceinline__ void conv_mainloop(const Phase<typename C::Elem>& ph, const Geom& gm, char* smem,
                                               f32x16 (&acc)[C::MT][C::NT]) {
   using T = typename C::Elem;
-  using FragT = typename Frag<T>::type;
+  using FragT = typename Frag<T>::type;                                   // what one lane reads per fragment
+  using AFrag = std::conditional_t<C::X3, X3Act, FragT>;                  // activation operand(s) held in registers
+  using BFrag = std::conditional_t<C::X3, bf16x8v, FragT>;                // weight operand held in registers
   using lds_ptr = __attribute__((address_space(3))) void*;
   constexpr int kVec = elem_traits<T>::kVec;
   const int lane = gm.lane, wave = gm.wave, grp = gm.grp, wm = gm.wm, wn = gm.wn, r = gm.r, h = gm.h;
@@ -250,13 +304,14 @@ __device__ __forceinline__ void conv_mainloop(const Phase<typename C::Elem>& ph,
   // Speed is not the point of this mode (no held-back step either: it would straddle two stage sums).
   constexpr bool BLOCKED = sizeof(T) == 4;
   constexpr int NHOLD = (BLOCKED || C::BIG) ? 0 : ((STV_HOLD_LAST < NSTEP) ? STV_HOLD_LAST : NSTEP);      // steps held back (0: none)
-  FragT hold_a[NHOLD > 0 ? NHOLD : 1][C::MT], hold_b[NHOLD > 0 ? NHOLD : 1][C::NT];
+  AFrag hold_a[NHOLD > 0 ? NHOLD : 1][C::MT];
+  BFrag hold_b[NHOLD > 0 ? NHOLD : 1][C::NT];
 #pragma unroll
   for (int q = 0; q < NHOLD; ++q) {
 #pragma unroll
-    for (int mt = 0; mt < C::MT; ++mt) hold_a[q][mt] = FragT{};
+    for (int mt = 0; mt < C::MT; ++mt) hold_a[q][mt] = AFrag{};
 #pragma unroll
-    for (int nt = 0; nt < C::NT; ++nt) hold_b[q][nt] = FragT{};
+    for (int nt = 0; nt < C::NT; ++nt) hold_b[q][nt] = BFrag{};
   }
   auto flush_held = [&]() {
 #pragma unroll
@@ -264,11 +319,11 @@ __device__ __forceinline__ void conv_mainloop(const Phase<typename C::Elem>& ph,
 #pragma unroll
       for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < C::NT; ++nt) mma<T>(hold_b[q][nt], hold_a[q][mt], acc[mt][nt]);
+        for (int nt = 0; nt < C::NT; ++nt) mma_any(hold_b[q][nt], hold_a[q][mt], acc[mt][nt]);
   };
   auto run_stage = [&](const char* cur, char* fill, int l) {
-    FragT af[2][C::AROWS];
-    FragT bf[PFB + 1][C::NT];
+    AFrag af[2][C::AROWS];
+    BFrag bf[PFB + 1][C::NT];
     f32x16 sacc[BLOCKED ? C::MT : 1][BLOCKED ? C::NT : 1];      // this stage's own sum (fp32 mode)
     if constexpr (BLOCKED) {
 #pragma unroll
@@ -280,13 +335,21 @@ __device__ __forceinline__ void conv_mainloop(const Phase<typename C::Elem>& ph,
     }
     auto load_a = [&](int dx, int j, int set) {
       const FragT v = *reinterpret_cast<const FragT*>(cur + a_addr[dx][j]);
-      af[set][j] = RELU ? relu_frag(v, 0u) : v;
+      if constexpr (C::X3) af[set][j] = split_act(RELU ? relu_frag(v, 0u) : v);
+      else af[set][j] = RELU ? relu_frag(v, 0u) : v;
     };
     auto load_b = [&](int step) {
       const int tap = (step % C::ND) * C::ND + step / C::ND;     // dy * 3 + dx
 #pragma unroll
-      for (int nt = 0; nt < C::NT; ++nt)
-        bf[step % (PFB + 1)][nt] = *reinterpret_cast<const FragT*>(cur + b_lane + (tap * C::BN + nt * 32) * C::KB);
+      for (int nt = 0; nt < C::NT; ++nt) {
+        const char* src = cur + b_lane + (tap * C::BN + nt * 32) * C::KB;
+        if constexpr (C::X3 && C::TAPS == 9)      // 3x3: K-blocked weights, pre-split at packing (the host checks)
+          bf[step % (PFB + 1)][nt] = *reinterpret_cast<const bf16x8v*>(src);
+        else if constexpr (C::X3)                 // 1x1: the Gram-backward seed, plain fp32, split here
+          bf[step % (PFB + 1)][nt] = split_w(*reinterpret_cast<const f32x4*>(src));
+        else
+          bf[step % (PFB + 1)][nt] = *reinterpret_cast<const FragT*>(src);
+      }
     };
     load_b(0);
 #pragma unroll
@@ -325,8 +388,8 @@ __device__ __forceinline__ void conv_mainloop(const Phase<typename C::Elem>& ph,
         for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
           for (int nt = 0; nt < C::NT; ++nt) {
-            if constexpr (BLOCKED) mma<T>(bf[step % (PFB + 1)][nt], af[dx & 1][mt + dy], sacc[mt][nt]);
-            else mma<T>(bf[step % (PFB + 1)][nt], af[dx & 1][mt + dy], acc[mt][nt]);   // D[cout][pixel]
+            if constexpr (BLOCKED) mma_any(bf[step % (PFB + 1)][nt], af[dx & 1][mt + dy], sacc[mt][nt]);
+            else mma_any(bf[step % (PFB + 1)][nt], af[dx & 1][mt + dy], acc[mt][nt]);   // D[cout][pixel]
           }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -695,7 +758,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
         }
         mask_done = true;
       }
-      using C1 = Cfg<T, C::TH, C::BN, C::WM, C::WN, 1, C::KS, C::NBUF, C::M16>;
+      using C1 = Cfg<T, C::TH, C::BN, C::WM, C::WN, 1, C::KS, C::NBUF, C::M16, C::X3>;
       static_assert(C1::RING_BYTES <= C::LDS_BYTES, "the 1x1 pass reuses the 3x3 ring");
       const int nch2 = a.cin2 / C::CK, kh2 = (nch2 + 1) >> 1;       // (the 1x1 term's K is split like the first term's)
       const Phase<T> ph2{static_cast<const T*>(a.x2), static_cast<const T*>(a.w2), a.cin2, false,

@@ -36,7 +36,18 @@ struct GramCfg {
 
 inline int gram_tile(int C) { return C <= 64 ? 64 : 128; }
 
-template <typename T, int TS>
+// bf16x3 (fp32 features, split-bf16 products): a feature value f is staged as ONE 32-bit LDS word {hi, lo} (hi = bf16_rne(f)
+// in the low half, lo = bf16_rne(f - hi) in the high half; lo = 0 where hi is not finite), so the split runs once per
+// element and block while the image keeps the fp32 layout.  A lane's operand of v_mfma_f32_32x32x16_bf16 is 8 pixels of
+// one channel: 8 word reads, repacked into a hi and a lo fragment; R += ah.bh + ah.bl + al.bh (al.bl dropped).
+__device__ __forceinline__ uint32_t split_word(float f) {
+  const uint32_t hb = (uint32_t)f32_to_bf16(f);
+  const float hf = __uint_as_float(hb << 16);
+  const float r = __builtin_isfinite(hf) ? f - hf : 0.0f;
+  return hb | ((uint32_t)f32_to_bf16(r) << 16);
+}
+
+template <typename T, int TS, bool X3 = false>
 __device__ __forceinline__ void gram_partial_body(const T* __restrict__ F, float* __restrict__ partials, int N, int C,
                                                   int ksplit, int chunk, int bx, int by) {
   using G = GramCfg<TS>;
@@ -90,6 +101,13 @@ __device__ __forceinline__ void gram_partial_body(const T* __restrict__ F, float
         float fi[kVec], fj[kVec];
         unpack16<T>(reg_i[it], fi);
         unpack16<T>(reg_j[it], fj);
+        if constexpr (X3) {
+#pragma unroll
+          for (int e = 0; e < kVec; ++e) {
+            fi[e] = __uint_as_float(split_word(fi[e]));
+            fj[e] = __uint_as_float(split_word(fj[e]));
+          }
+        }
 #pragma unroll
         for (int q = 0; q < kVec / 4; ++q) {
           *reinterpret_cast<f32x4*>(buf + pr * G::PITCH + cv + 4 * q) =
@@ -114,6 +132,39 @@ __device__ __forceinline__ void gram_partial_body(const T* __restrict__ F, float
     if (more) stage_load(p_begin + (s + 1) * PK);
     const float* ai = cur + wi * (G::AT * 32) + r;
     const float* bj = cur + G::TILE_FLOATS + wj * (G::AT * 32) + r;
+    if constexpr (X3) {
+      // words of pixels 16 kk + 8 h + e, e < 8 -> (hi, lo) fragments: byte selectors of v_perm_b32 pick the low
+      // (0x05040100) or high (0x07060302) halves of two words
+      auto frag = [&](const float* base, bf16x8v& hi, bf16x8v& lo) {
+        uint32_t w[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) w[e] = __float_as_uint(base[(8 * h + e) * G::PITCH]);
+        u32x4 vh, vl;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          vh[e] = __builtin_amdgcn_perm(w[2 * e + 1], w[2 * e], 0x05040100u);
+          vl[e] = __builtin_amdgcn_perm(w[2 * e + 1], w[2 * e], 0x07060302u);
+        }
+        hi = __builtin_bit_cast(bf16x8v, vh);
+        lo = __builtin_bit_cast(bf16x8v, vl);
+      };
+#pragma unroll
+      for (int kk = 0; kk < PK / 16; ++kk) {
+        bf16x8v ah[G::AT], al[G::AT], bh[G::AT], bl[G::AT];
+#pragma unroll
+        for (int a = 0; a < G::AT; ++a) frag(ai + kk * 16 * G::PITCH + a * 32, ah[a], al[a]);
+#pragma unroll
+        for (int b = 0; b < G::AT; ++b) frag(bj + kk * 16 * G::PITCH + b * 32, bh[b], bl[b]);
+#pragma unroll
+        for (int a = 0; a < G::AT; ++a)
+#pragma unroll
+          for (int b = 0; b < G::AT; ++b) {
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh[b], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bl[b], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[a], bh[b], acc[a][b], 0, 0, 0);
+          }
+      }
+    } else
 #pragma unroll
     for (int q = 0; q < PK / 2; ++q) {
       float av[G::AT], bv[G::AT];
@@ -166,20 +217,20 @@ __device__ __forceinline__ void decode_block(int b, int pairs, int ksplit, int& 
   ks = b / pairs;
 }
 
-template <typename T, int TS>
+template <typename T, int TS, bool X3 = false>
 __global__ __launch_bounds__(256) void gram_partial_kernel(const T* __restrict__ F, float* __restrict__ partials,
                                                            int N, int C, int ksplit, int chunk, int pairs) {
   int pair, ks;
   decode_block(blockIdx.x, pairs, ksplit, pair, ks);
-  gram_partial_body<T, TS>(F, partials, N, C, ksplit, chunk, pair, ks);
+  gram_partial_body<T, TS, X3>(F, partials, N, C, ksplit, chunk, pair, ks);
 }
-template <typename T, int TS>
+template <typename T, int TS, bool X3 = false>
 __global__ __launch_bounds__(256) void gram_partial_multi_kernel(PartialMulti m) {
   const int i = find_tap(m.block0, m.n, blockIdx.x);
   const int b = blockIdx.x - m.block0[i];
   int pair, ks;
   decode_block(b, m.pairs[i], m.ksplit[i], pair, ks);
-  gram_partial_body<T, TS>(static_cast<const T*>(m.F[i]), m.partials[i], m.N[i], m.C[i], m.ksplit[i], m.chunk[i],
+  gram_partial_body<T, TS, X3>(static_cast<const T*>(m.F[i]), m.partials[i], m.N[i], m.C[i], m.ksplit[i], m.chunk[i],
                            pair, ks);
 }
 
@@ -528,7 +579,7 @@ int launch_bf16(const bf16_t* F, float* partials, int N, int C, int pairs, int k
   return STV_OK;
 }
 
-template <typename T>
+template <typename T, bool X3 = false>
 int partial_typed(const void* F, float* partials, int N, int C, hipStream_t st) {
   const int TS = gram_tile(C);
   const int nt = ceil_div(C, TS);
@@ -543,12 +594,12 @@ int partial_typed(const void* F, float* partials, int N, int C, hipStream_t st) 
   chunk = ceil_div(chunk, PK) * PK;
   dim3 grid(pairs * ksplit);
   if (TS == 64) {
-    hipLaunchKernelGGL((gram_partial_kernel<T, 64>), grid, dim3(256), GramCfg<64>::LDS_BYTES, st,
+    hipLaunchKernelGGL((gram_partial_kernel<T, 64, X3>), grid, dim3(256), GramCfg<64>::LDS_BYTES, st,
                        static_cast<const T*>(F), partials, N, C, ksplit, chunk, pairs);
   } else {
-    if (stv_set_max_lds(reinterpret_cast<const void*>(&gram_partial_kernel<T, 128>), GramCfg<128>::LDS_BYTES) != STV_OK)
+    if (stv_set_max_lds(reinterpret_cast<const void*>(&gram_partial_kernel<T, 128, X3>), GramCfg<128>::LDS_BYTES) != STV_OK)
       return STV_ERR_LAUNCH;
-    hipLaunchKernelGGL((gram_partial_kernel<T, 128>), grid, dim3(256), GramCfg<128>::LDS_BYTES, st,
+    hipLaunchKernelGGL((gram_partial_kernel<T, 128, X3>), grid, dim3(256), GramCfg<128>::LDS_BYTES, st,
                        static_cast<const T*>(F), partials, N, C, ksplit, chunk, pairs);
   }
   STV_CHECK_LAUNCH();
@@ -597,6 +648,10 @@ extern "C" int stv_gram_partial(const void* F, float* partials, int n_pixels, in
     if (C % 8) return STV_ERR_ARG;
     return partial_typed<bf16_t>(F, partials, n_pixels, C, st);
   }
+  if (dtype == STV_BF16X3) {     // the fp32 path's layout and granularity; the byte guard counts bytes
+    if (C % 4 || (size_t)n_pixels * C * 4 >= ((size_t)1 << 31)) return STV_ERR_ARG;
+    return partial_typed<float, true>(F, partials, n_pixels, C, st);
+  }
   return STV_ERR_ARG;
 }
 
@@ -631,13 +686,15 @@ extern "C" int stv_gram_finish(const float* partials, const float* target, float
 // ---- batched Gram chain: all taps of a step in two (partial: one per tile size) + one launches ----
 extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype, void* stream) {
   if (!taps || n_taps <= 0 || n_taps > kMaxTaps) return STV_ERR_ARG;
-  if (dtype != STV_F32 && dtype != STV_BF16) return STV_ERR_ARG;
+  if (dtype != STV_F32 && dtype != STV_BF16 && dtype != STV_BF16X3) return STV_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int vec = dtype == STV_F32 ? 4 : 8;
+  const bool x3 = dtype == STV_BF16X3;     // split-bf16 partial sums of fp32 features; the finish is the fp32 one
+  const int vec = dtype == STV_BF16 ? 8 : 4;
   for (int i = 0; i < n_taps; ++i) {
     const stv_gram_tap_t& t = taps[i];
     if (!t.partials || t.n_pixels <= 0 || t.channels <= 0 || t.channels % vec || t.norm <= 0.0f) return STV_ERR_ARG;
     if (dtype == STV_BF16 && (size_t)t.n_pixels * t.channels * 2 >= ((size_t)1 << 31)) return STV_ERR_ARG;
+    if (x3 && t.F && (size_t)t.n_pixels * t.channels * 4 >= ((size_t)1 << 31)) return STV_ERR_ARG;
   }
   // partial sums: one launch per tile size present (bf16 with both sizes present: one launch for both)
   static const bool merge_sizes = !(getenv("STV_GRAM_MERGE") && atoi(getenv("STV_GRAM_MERGE")) == 0);   // A/B aid
@@ -683,6 +740,14 @@ extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype,
         STV_SET_LDS(gram_partial_bf16_multi_kernel<128>, GramBCfg<128>::LDS_BYTES);
         hipLaunchKernelGGL(gram_partial_bf16_multi_kernel<128>, grid, dim3(256), GramBCfg<128>::LDS_BYTES, st, m);
       }
+    } else if (x3) {
+      if (TS == 64) {
+        STV_SET_LDS((gram_partial_multi_kernel<float, 64, true>), GramCfg<64>::LDS_BYTES);
+        hipLaunchKernelGGL((gram_partial_multi_kernel<float, 64, true>), grid, dim3(256), GramCfg<64>::LDS_BYTES, st, m);
+      } else {
+        STV_SET_LDS((gram_partial_multi_kernel<float, 128, true>), GramCfg<128>::LDS_BYTES);
+        hipLaunchKernelGGL((gram_partial_multi_kernel<float, 128, true>), grid, dim3(256), GramCfg<128>::LDS_BYTES, st, m);
+      }
     } else {
       if (TS == 64) {
         STV_SET_LDS((gram_partial_multi_kernel<float, 64>), GramCfg<64>::LDS_BYTES);
@@ -716,7 +781,7 @@ extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype,
     }
     if (!f.n) continue;
     const dim3 grid(f.block0[f.n]);
-    if (dtype == STV_F32) {
+    if (dtype != STV_BF16) {
       if (deep) hipLaunchKernelGGL((gram_finish_multi_kernel<float, 32>), grid, dim3(FIN_L * 32), 0, st, f);
       else hipLaunchKernelGGL((gram_finish_multi_kernel<float, 8>), grid, dim3(FIN_L * 8), 0, st, f);
     } else {

@@ -14,10 +14,16 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import ACCUM, MASK, POOL_ONLY, RELU_IN, RELU_OUT, STV_BF16, STV_F32, W_BLOCKED  # noqa: F401
+from ._lib import ACCUM, MASK, POOL_ONLY, RELU_IN, RELU_OUT, STV_BF16, STV_BF16X3, STV_F32, W_BLOCKED  # noqa: F401
 
 
-def dtype_code(dtype: torch.dtype) -> int:
+def dtype_code(dtype: torch.dtype, *, split: bool = False) -> int:
+    """The library's dtype code; ``split=True`` (fp32 storage only): STV_BF16X3, split-bf16 products."""
+    if split:
+        if dtype != torch.float32:
+            msg = f"split-bf16 products (bf16x3) need fp32 storage, got {dtype}"
+            raise RuntimeError(msg)
+        return STV_BF16X3
     if dtype == torch.float32:
         return STV_F32
     if dtype == torch.bfloat16:
@@ -70,9 +76,25 @@ def block_weights(w: torch.Tensor) -> torch.Tensor:
     return w.reshape(taps, cout, cin // ck, ck).permute(0, 2, 1, 3).contiguous()
 
 
-def conv_uses_mfma(H: int, W: int, cin: int, cout: int, dtype: torch.dtype) -> bool:
+def split_weights(w: torch.Tensor) -> torch.Tensor:
+    """K-blocked fp32 weights -> the pre-split layout of STV_BF16X3 (include/stv.h), same shape, dtype and bytes.
+
+    Each 16-byte group of four weights becomes their four bf16 hi parts (hi = bf16_rne(w)) followed by their four bf16
+    lo parts (lo = bf16_rne(w - hi)): exactly the 8 bf16 k-values one lane hands to the MFMA.  Once, at model build.
+    """
+    if w.dtype != torch.float32 or w.shape[-1] % 4:
+        msg = f"split_weights expects fp32 K-blocked weights, got {tuple(w.shape)}/{w.dtype}"
+        raise RuntimeError(msg)
+    hi = w.to(torch.bfloat16)
+    lo = (w - hi.float()).to(torch.bfloat16)
+    g = w.shape[-1] // 4
+    both = torch.stack([hi.reshape(*w.shape[:-1], g, 4), lo.reshape(*w.shape[:-1], g, 4)], dim=-2)
+    return both.contiguous().view(torch.int16).view(torch.float32).reshape(w.shape).contiguous()
+
+
+def conv_uses_mfma(H: int, W: int, cin: int, cout: int, dtype: torch.dtype, *, split: bool = False) -> bool:
     """True when stv_conv_igemm runs this shape on the matrix cores (else: direct kernel, plain weights)."""
-    return int(_lib.load().stv_conv_config(H, W, cin, cout, 9, dtype_code(dtype))) >= 0
+    return int(_lib.load().stv_conv_config(H, W, cin, cout, 9, dtype_code(dtype, split=split))) >= 0
 
 
 def conv_uses_ws(H: int, W: int, cin: int, cout: int, dtype: torch.dtype, *, flags: int = 0, has_ref: bool = False,
@@ -84,10 +106,10 @@ def conv_uses_ws(H: int, W: int, cin: int, cout: int, dtype: torch.dtype, *, fla
 TUNE_ROUTE = 109      # stv.h STV_TUNE_ROUTE: `taps` value that tunes the shape as conv_igemm_route runs it
 
 
-def conv_tune(H: int, W: int, cin: int, cout: int, taps: int, dtype: torch.dtype) -> int:
+def conv_tune(H: int, W: int, cin: int, cout: int, taps: int, dtype: torch.dtype, *, split: bool = False) -> int:
     """Measure the tile configurations for one conv shape once (stv_conv_tune); returns the choice (-1: direct kernel).
     ``taps=TUNE_ROUTE``: the dgrad with the pooling backward in its epilogue (its own table entry)."""
-    r = int(_lib.load().stv_conv_tune(H, W, cin, cout, taps, dtype_code(dtype), _stream()))
+    r = int(_lib.load().stv_conv_tune(H, W, cin, cout, taps, dtype_code(dtype, split=split), _stream()))
     if r < -1:
         _lib.check(-r - 100, "stv_conv_tune")
     return r
@@ -179,8 +201,9 @@ def conv_first_dgrad(dy: torch.Tensor, wf: torch.Tensor, cin: int,
 
 def conv_igemm(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None,
                ref: torch.Tensor | None = None, out: torch.Tensor | None = None,
-               flags: int = 0) -> torch.Tensor:
-    """x [H,W,Cin], w [taps,Cout,Cin] or K-blocked [taps,Cin/CK,Cout,CK] (same dtype) -> [H,W,Cout]."""
+               flags: int = 0, *, split: bool = False) -> torch.Tensor:
+    """x [H,W,Cin], w [taps,Cout,Cin] or K-blocked [taps,Cin/CK,Cout,CK] (same dtype) -> [H,W,Cout].
+    ``split=True``: bf16x3 (fp32 storage; K-blocked weights must come from ``split_weights``)."""
     H, W, cin = x.shape
     if w.dim() == 4:
         taps, nck, cout, ck = w.shape
@@ -198,15 +221,16 @@ def conv_igemm(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = Non
         out = torch.empty(H, W, cout, device=x.device, dtype=x.dtype)
     lib = _lib.load()
     _lib.check(lib.stv_conv_igemm(_ptr(x), _ptr(w), _ptr(bias), _ptr(ref), _ptr(out), H, W, cin, cout,
-                                  taps, flags, dtype_code(x.dtype), _stream()), "stv_conv_igemm")
+                                  taps, flags, dtype_code(x.dtype, split=split), _stream()), "stv_conv_igemm")
     return out
 
 
 def conv_igemm_pool(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, flags: int = 0,
                     out: torch.Tensor | None = None, pool_out: torch.Tensor | None = None,
-                    pool_idx: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+                    pool_idx: torch.Tensor | None = None, *, split: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
     """3x3 conv (+bias, +ReLU by flag) and MaxPool2d(2,2) of its output in one launch (stv_conv_igemm_pool).
-    ``pool_idx`` (uint8 [H/2][W/2][cout], optional) receives the arg-max map ``maxpool_bwd_idx`` consumes."""
+    ``pool_idx`` (uint8 [H/2][W/2][cout], optional) receives the arg-max map ``maxpool_bwd_idx`` consumes.
+    ``split=True``: bf16x3 (fp32 storage, weights from ``split_weights``)."""
     H, W, cin = x.shape
     if w.dim() == 4:
         taps, nck, cout, ck = w.shape
@@ -222,12 +246,13 @@ def conv_igemm_pool(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None,
         pool_out = torch.empty(H // 2, W // 2, cout, device=x.device, dtype=x.dtype)
     lib = _lib.load()
     _lib.check(lib.stv_conv_igemm_pool(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(pool_out), _ptr(pool_idx), H, W,
-                                       cin, cout, flags, dtype_code(x.dtype), _stream()), "stv_conv_igemm_pool")
+                                       cin, cout, flags, dtype_code(x.dtype, split=split), _stream()), "stv_conv_igemm_pool")
     return out, pool_out
 
 
 def conv_igemm_dual(x: torch.Tensor, w: torch.Tensor, x2: torch.Tensor, w2: torch.Tensor,
-                    ref: torch.Tensor | None = None, out: torch.Tensor | None = None, flags: int = 0) -> torch.Tensor:
+                    ref: torch.Tensor | None = None, out: torch.Tensor | None = None, flags: int = 0, *,
+                    split: bool = False) -> torch.Tensor:
     """out = [out +] mask(ref>0) * conv3x3(x, w) + x2 . w2^T in one launch (stv_conv_igemm_dual)."""
     H, W, cin = x.shape
     if w.dim() == 4:
@@ -243,7 +268,7 @@ def conv_igemm_dual(x: torch.Tensor, w: torch.Tensor, x2: torch.Tensor, w2: torc
         out = torch.empty(H, W, cout, device=x.device, dtype=x.dtype)
     lib = _lib.load()
     _lib.check(lib.stv_conv_igemm_dual(_ptr(x), _ptr(w), _ptr(x2), _ptr(w2), _ptr(ref), _ptr(out), H, W, cin, cin2,
-                                       cout, flags, dtype_code(x.dtype), _stream()), "stv_conv_igemm_dual")
+                                       cout, flags, dtype_code(x.dtype, split=split), _stream()), "stv_conv_igemm_dual")
     return out
 
 
@@ -353,14 +378,14 @@ def gram_loss_parts(C: int) -> int:
     return _lib.load().stv_gram_loss_parts(C)
 
 
-def gram_partial(F: torch.Tensor, partials: torch.Tensor | None = None) -> torch.Tensor:
-    """F [H,W,C] (or [N,C]) -> fp32 partial slabs [ksplit,C,C]."""
+def gram_partial(F: torch.Tensor, partials: torch.Tensor | None = None, *, split: bool = False) -> torch.Tensor:
+    """F [H,W,C] (or [N,C]) -> fp32 partial slabs [ksplit,C,C] (``split=True``: bf16x3 products of fp32 features)."""
     C = F.shape[-1]
     n = F.numel() // C
     if partials is None:
         partials = torch.empty(gram_ksplit(n, C), C, C, device=F.device, dtype=torch.float32)
     lib = _lib.load()
-    _lib.check(lib.stv_gram_partial(_ptr(F), _ptr(partials), n, C, dtype_code(F.dtype), _stream()),
+    _lib.check(lib.stv_gram_partial(_ptr(F), _ptr(partials), n, C, dtype_code(F.dtype, split=split), _stream()),
                "stv_gram_partial")
     return partials
 

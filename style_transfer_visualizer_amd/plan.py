@@ -98,18 +98,28 @@ def _check_layer(layer: nn.Module, idx: int) -> str:
     raise RuntimeError(msg)
 
 
+_PRODUCT_OPS = (OP_CONV, OP_GRAM_PARTIAL, OP_GRAM_MULTI)      # the ops that take STV_BF16X3 in bf16x3 mode
+
+
 class Schedule:
     """Buffers + forward/backward op lists for one image size."""
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
-                 H: int, W: int, dtype: torch.dtype, device: torch.device, *, with_grad: bool, halo: int = 0) -> None:
+                 H: int, W: int, dtype: torch.dtype, device: torch.device, *, with_grad: bool, halo: int = 0,
+                 split: bool = False) -> None:
         """``halo`` = 1: the schedule of one ROW STRIP of a larger image (spatial.py).  ``H`` is the
         strip's own row count; every activation (and the image) carries ``halo`` extra rows above and
         below that the owner fills before each 3x3 convolution reads them (neighbour's rows, or zeros
-        at the image border).  Convolutions run over the whole buffer - their output in the halo
+        at the image border).  ``split=True`` (fp32 storage only): bf16x3 - the conv and Gram ops form their products
+        from split bf16 operands (STV_BF16X3, weights pre-split at packing); every other op runs as in fp32.
+        Convolutions run over the whole buffer - their output in the halo
         rows is meaningless and is replaced by the next exchange - while pooling works on the
         strip's own rows only (strip heights are multiples of 16, so no window straddles two strips)."""
         self.H, self.W, self.dtype, self.device = H, W, dtype, device
+        if split and (dtype != torch.float32 or halo):
+            msg = "bf16x3 (split-bf16 products) runs on fp32 storage and whole images only (no row strips)"
+            raise ValueError(msg)
+        self.split = split
         self.halo = halo
         self.fuse_first_gram = True      # off where the Gram runs over a sub-range of the buffer (spatial.SpatialShard)
         self.nodes: list[Node] = []
@@ -160,15 +170,20 @@ class Schedule:
                     wf = ops.pack_weights_fwd(w).to(self.dtype)
                     wb = ops.pack_weights_bwd(w).to(self.dtype) if self.with_grad else None
                     # matrix-core shapes take K-blocked weights (W_BLOCKED is derived from w.dim() == 4)
-                    blocked = os.environ.get("STV_W_BLOCKED", "1") != "0"     # A/B knob
-                    if blocked and ops.conv_uses_mfma(H, W, cin, cout, self.dtype):
+                    # A/B knob (bf16x3: always blocked - its 3x3 kernels read pre-split K-blocked weights only)
+                    blocked = self.split or os.environ.get("STV_W_BLOCKED", "1") != "0"
+                    if blocked and ops.conv_uses_mfma(H, W, cin, cout, self.dtype, split=self.split):
                         wf = ops.block_weights(wf)
-                    if blocked and wb is not None and ops.conv_uses_mfma(H, W, cout, cin, self.dtype):
+                        if self.split:     # frozen weights: split into bf16 hi / lo once, here
+                            wf = ops.split_weights(wf)
+                    if blocked and wb is not None and ops.conv_uses_mfma(H, W, cout, cin, self.dtype, split=self.split):
                         wb = ops.block_weights(wb)
+                        if self.split:
+                            wb = ops.split_weights(wb)
                     if w.is_cuda:      # measure the tile configurations of this layer's shapes once
-                        ops.conv_tune(H, W, cin, cout, 9, self.dtype)
+                        ops.conv_tune(H, W, cin, cout, 9, self.dtype, split=self.split)
                         if self.with_grad:
-                            ops.conv_tune(H, W, cout, cin, 9, self.dtype)
+                            ops.conv_tune(H, W, cout, cin, 9, self.dtype, split=self.split)
                     node = Node("conv", cur, dst, relu_in=pending_relu, layer=i, wf=wf, wb=wb, bias=bias, cin=cin)
                 pending_relu = False
                 if i + 1 <= last and kinds[i + 1] == "relu" and i not in tapped:
@@ -219,7 +234,8 @@ class Schedule:
     # ------------------------------------------------------------------ op emission
     def _op(self, **kw) -> StvOp:
         op = StvOp()
-        op.dtype = ops.dtype_code(self.dtype)
+        # bf16x3: the ops that form products take STV_BF16X3, every other op runs on the fp32 storage as STV_F32
+        op.dtype = ops.dtype_code(self.dtype, split=self.split and kw.get("op") in _PRODUCT_OPS)
         for k, v in kw.items():
             if isinstance(v, torch.Tensor):
                 self._keep.append(v)
@@ -471,7 +487,7 @@ class Schedule:
                     continue
                 if tap.kind == "style":
                     if d.act.is_cuda:
-                        ops.conv_tune(d.H, d.W, d.C, d.C, 1, self.dtype)     # cached per shape
+                        ops.conv_tune(d.H, d.W, d.C, d.C, 1, self.dtype, split=self.split)     # cached per shape
                     out.append(self._op(op=OP_CONV, p0=d.act, p1=tap.sgrad, q0=wr(d), H=d.H, W=d.W,
                                         cin=d.C, cout=d.C, taps=1, flags=acc_flag(d)))
                 else:

@@ -238,7 +238,11 @@ class HaloShard:
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
-                 style_w: float, content_w: float, group=None) -> None:
+                 style_w: float, content_w: float, group=None, split: bool = False) -> None:
+        if split:
+            msg = ("bf16x3 (split-bf16 products) is not available on the row-strip path: use precision fp32 or "
+                   "bf16 with HaloShard, or bf16x3 on a whole image")
+            raise ValueError(msg)
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -21,12 +21,14 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--sizes", type=int, nargs="*", default=[256, 512, 1024])
 ap.add_argument("--wide", type=int, nargs="*", default=[2160, 3840], help="one H W pair (the 4K config), bf16 only; empty to skip")
 ap.add_argument("--out", default=os.path.join(os.path.dirname(_lib.LIB_PATH), "conv_tiles_gfx950.json"))
+ap.add_argument("--precisions", nargs="*", default=["bf16", "fp32"], help="bf16 / fp32 / bf16x3 (its own table key)")
+ap.add_argument("--add-to", default=None, help="an existing table: keep its entries unchanged, add only shapes it lacks")
 args = ap.parse_args()
 dev = torch.device("cuda")
 lib = _lib.load()
 votes: dict = collections.defaultdict(collections.Counter)
-shapes = [(s, s, p) for s in args.sizes for p in ("bf16", "fp32")]
-if len(args.wide) == 2:
+shapes = [(s, s, p) for s in args.sizes for p in args.precisions]
+if len(args.wide) == 2 and "bf16" in args.precisions:
     shapes.append((args.wide[0], args.wide[1], "bf16"))
 for rnd in range(args.rounds):
     lib.stv_conv_tune_import(None, 0)                      # empty table: everything is measured again
@@ -47,7 +49,8 @@ os.environ["STV_CONV_TUNE"] = "0"
 entries = []
 for key, cnt in sorted(votes.items()):
     H, W, cin, cout, taps, eb = key
-    analytic = int(lib.stv_conv_config(H, W, cin, cout, taps, 1 if eb == 2 else 0))
+    code = {2: _lib.STV_BF16, 4: _lib.STV_F32, _lib.TUNE_BF16X3: _lib.STV_BF16X3}[eb]
+    analytic = int(lib.stv_conv_config(H, W, cin, cout, taps, code))
     top = max(cnt.values())
     best = [c for c, v in cnt.items() if v == top]
     cfg = analytic if analytic in best else min(best)
@@ -63,6 +66,15 @@ doc = {"tool": "tools/tune_tiles.py", "rounds": args.rounds,
                "rocm": str(torch.version.hip)},
        "arch": str(_props.gcnArchName).split(":")[0],
        "date": datetime.date.today().isoformat(), "entries": entries}
+if args.add_to:       # the existing table stays as it is (its header and entries); only shapes it does not hold are added
+    with open(args.add_to) as fh:
+        old = json.load(fh)
+    have = {(e["H"], e["W"], e["cin"], e["cout"], e["taps"], e["elem_bytes"]) for e in old["entries"]}
+    new = [e for e in entries if (e["H"], e["W"], e["cin"], e["cout"], e["taps"], e["elem_bytes"]) not in have]
+    for e in new:
+        e["measured"] = {k: doc[k] for k in ("tool", "rounds", "device", "box", "date")}
+    old["entries"] = old["entries"] + new
+    doc, entries = old, new
 with open(args.out, "w") as fh:
     json.dump(doc, fh, indent=1)
 print(f"wrote {len(entries)} entries to {args.out}; differ from the analytic choice: {sum(e['cfg'] != e['analytic'] for e in entries)}")
