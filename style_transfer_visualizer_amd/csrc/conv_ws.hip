@@ -46,16 +46,6 @@
 #ifndef STV_WS_F_AUX
 #define STV_WS_F_AUX 0       // ... of the z-tile DMA (backward form: last use of that map in the step)
 #endif
-#ifndef STV_WS_SWEEP
-// Forward form behind a ReLU: 1 = clamp the staged halo tile ONCE in LDS (a sweep under the previous tile's MFMAs),
-// 0 = every A fragment after its read.  Measured (round 5, profiles/r05_ws_sweep_ab.log): the sweep is 1-3 % SLOWER -
-// isolated 116.5-118.2 against 114.8 us, step 2.599 against 2.562-2.607 ms at 1024^2 - so the default stays 0
-// (profiles/EXPERIMENTS.md 3.9); the sweep is kept for A/B builds (tools/build_variant.sh).
-#define STV_WS_SWEEP 0
-#endif
-#ifndef STV_WS_W_AGPR
-#define STV_WS_W_AGPR 1      // resident weights pinned to AGPRs (0: wherever the register allocator puts them)
-#endif
 #ifndef STV_WS128_DEFAULT
 #define STV_WS128_DEFAULT 1  // the 128 -> 128 layer on this kernel unless STV_CONV_WS128=0
 #endif
@@ -88,8 +78,6 @@ template <int CIN> struct WsGeom {
   static constexpr int NCOL = 3 * NSTAGE;                    // tap columns of a tile: (stage, dx)
   static constexpr int NCHUNK = 3 * MT;                      // deferred epilogue chunks: MT row stores + 2 MT pooling half-steps
   static constexpr int SPW = NSTAGE / 4;                     // K-stages each wave fetches per tile
-  static constexpr int NSWEEP = IN_BYTES / 4096;             // 16-byte slots of a halo tile per thread (ReLU sweep): 11 / 10
-  static_assert(IN_BYTES % 4096 == 0 && NSWEEP < NCOL, "ReLU sweep: whole rounds of 256 slots, one per tap column");
   static_assert(NCHUNK <= NCOL, "one epilogue chunk per tap column");
 };
 
@@ -113,7 +101,7 @@ __device__ __forceinline__ bf16x8v relu_frag(bf16x8v v, uint32_t floor) {
 }
 
 template <int CIN, bool DG, bool RELU_IN, bool POOL, bool MASKED = false, bool DUAL = false>
-__global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgroups, int diag) {
+__global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgroups) {
 #if defined(__HIP_DEVICE_COMPILE__)
   using lds_ptr = __attribute__((address_space(3))) void*;
   using G = WsGeom<CIN>;
@@ -156,7 +144,6 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
         const int elem = w_blocked ? (((tap * NSTAGE + s) * a.cout + n) * CK + h * 8) : ((tap * a.cout + n) * CIN + s * CK + h * 8);
         wreg[s][tap] = __builtin_bit_cast(bf16x8v, __builtin_amdgcn_raw_buffer_load_b128(rs_w, (uint32_t)(elem * 2), 0, 0));
       }
-#if STV_WS_W_AGPR
     // The resident weights are MFMA operands only: pinned to the accumulation half of the register file.  Left to the
     // allocator they are loaded as ordinary VGPR values, spilled to AGPRs under the pressure of a 476-register kernel and
     // copied back - four v_accvgpr_read_b32 in front of every group of four MFMAs, 144-227 per tile (round 5, read off
@@ -165,7 +152,6 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
     for (int s = 0; s < NSTAGE; ++s)
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) asm volatile("" : "+a"(wreg[s][tap]));
-#endif
   }
   bf16x8v sreg[DG && DUAL ? FSTAGES : 1];          // DG with a fused 1x1 term: S rows of this wave's channels (plain [cout][cout])
   constexpr bool dual = DG && DUAL;                // (compile-time, like POOL: no branch between MFMA groups)
@@ -258,36 +244,6 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
   wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
-  // ---- ReLU on the input, once per staged tile (forward form behind a tapped layer: the stored map is pre-ReLU) -----
-  // Per fragment the packed max costs 4 VALU x 3 dx x (MT + 2) rows x NSTAGE stages per wave and tile (288 for Cin = 64:
-  // every staged value is clamped six times over - three tap columns, two channel halves of the workgroup); as a sweep
-  // over the landed tile it is one 16-byte slot per thread and round, NSWEEP rounds: 44 VALU + 22 LDS operations.  The
-  // sweep of tile k + 1 rides under the MFMAs of tile k, one round per tap column (read in one column, clamp + write in
-  // the next), and the barrier at the end of tile k publishes it.  For that the tile has to have LANDED when tile k
-  // starts: the wait at the end of a tile covers everything this wave has in flight (vmcnt 0: the halo tile requested a
-  // whole tile ago, and the previous tile's deferred stores - loads and stores retire out of order with respect to each
-  // other, so a counted wait could not tell them apart).
-  constexpr bool sweep = !DG && RELU_IN && (STV_WS_SWEEP != 0);
-  bf16x8v swv[2];
-  auto sweep_read = [&](char* buf, int c, int set) {
-    swv[set] = *reinterpret_cast<const bf16x8v*>(buf + (c * 256 + tid) * 16);
-  };
-  auto sweep_write = [&](char* buf, int c, int set) {      // (whole-vector packed max, as relu_frag does for a fragment)
-    *reinterpret_cast<bf16x8v*>(buf + (c * 256 + tid) * 16) = relu_frag(swv[set], 0u);
-  };
-  if constexpr (sweep) {                             // the first tile has nobody's MFMAs to hide behind
-    if (t_first < ntiles) {
-#pragma unroll
-      for (int c = 0; c < G::NSWEEP; ++c) {
-        sweep_read(smem, c, c & 1);
-        sweep_write(smem, c, c & 1);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the sweep's LDS writes are done before the others read
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  }
-
   // ---- forward form: the epilogue of tile k runs in the shadow of tile k + 1's MFMAs ------------------
   // One wave per SIMD has no other wave to overlap its epilogue with, but its own MFMAs leave seven of eight
   // issue slots to the vector ALU.  At the end of a tile only the rounding (acc -> packed bf16 words Pp, 64
@@ -311,7 +267,7 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
       const auto sy = __builtin_amdgcn_permlane32_swap(Q[4 + jp], Q[4 + jp + 1], false, false);
       const u32x4 out = {sx[0], sy[0], sx[1], sy[1]};
       const int nn = nb + 8 * jp + 8 * h;
-      const uint32_t off = (poff != kOob && !(diag & 1)) ? poff + (uint32_t)(nn * 2) : kOob;
+      const uint32_t off = (poff != kOob) ? poff + (uint32_t)(nn * 2) : kOob;
       __builtin_amdgcn_raw_buffer_store_b128(out, rs_out, off, 0, STV_STORE_AUX);
     }
   };
@@ -369,7 +325,7 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
           // channels e = 0,1 come from code[j] (bytes 0 and 2), e = 2,3 from code[4 + j]
           const uint32_t word = __builtin_amdgcn_perm(codep[mp][4 + j], codep[mp][j], 0x06040200u);
           const int nn = nb + 8 * j + 4 * h;
-          const uint32_t off = (pix_ok && !(diag & 1)) ? (uint32_t)((gyp * Wp + gxp) * a.cout + nn) : kOob;
+          const uint32_t off = pix_ok ? (uint32_t)((gyp * Wp + gxp) * a.cout + nn) : kOob;
           __builtin_amdgcn_raw_buffer_store_b32(word, rs_i, off, 0, 0);
         }
       }
@@ -408,26 +364,16 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
     // ReLU) clamped one column ahead, in the shadow of the 12 MFMAs in between.
     auto load_col = [&](int col, int set) { load_col_from(cur, col, set); };
     auto relu_col = [&](int set) {
-      if (RELU_IN && !sweep) {
+      if (RELU_IN) {
 #pragma unroll
         for (int j = 0; j < AROWS; ++j) af[set][j] = relu_frag(af[set][j], 0u);
       }
     };
     relu_col(0);                                     // (columns 0 and 1 are on their way already)
-    if (diag & 4) {                                  // (timing knock-out: no MFMA loop)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt] = acc0;
-    }
-    if (!(diag & 4))
 #pragma unroll
     for (int col = 0; col < NCOL; ++col) {
       const int s = col / 3, dx = col - s * 3;
       if (col + 2 < NCOL) load_col(col + 2, (col + 2) % 3);
-      if constexpr (sweep) {                           // the NEXT tile's buffer (no next tile: a buffer nobody reads again)
-        char* const nxt_buf = smem + ((slot + 1 == NB) ? 0 : slot + 1) * WsLds<CIN, DG>::BUF;
-        if (col < G::NSWEEP) sweep_read(nxt_buf, col, col & 1);
-        if (col >= 1 && col - 1 < G::NSWEEP) sweep_write(nxt_buf, col - 1, (col - 1) & 1);
-      }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int dy = 0; dy < 3; ++dy)
@@ -489,12 +435,9 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
     // DMA's IN_PIECES operations outstanding" implies every older load, i.e. the next tile, has landed.
     // The previous tile's deferred stores count too: they can only make the wait longer, never satisfied
     // early (the threshold is exactly the newest DMA's size).
-    const bool more = t + NB * tstride < ntiles && !(diag & 2);
-    // (STV_WS_SWEEP=2, diagnostic build: the sweep with the counted wait - NOT guaranteed to have the swept tile landed;
-    //  isolates what the full drain costs)
-    if ((!sweep || STV_WS_SWEEP == 2) && NB == 3 && t + 2 * tstride < ntiles && !(diag & 2)) wait_vmcnt<kTileOps>();
+    const bool more = t + NB * tstride < ntiles;
+    if (NB == 3 && t + 2 * tstride < ntiles) wait_vmcnt<kTileOps>();
     else wait_vmcnt<0>();
-    if constexpr (sweep) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the next tile's sweep: its writes were issued columns ago
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (NB == 2 && more) issue_tile(t + NB * tstride, cur);
@@ -509,10 +452,6 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
     // bf16 is a negative int16; the bias already sits in the accumulators).  P[mt][0..3] = channel pairs (0,1)
     // of groups j, P[mt][4..7] = pairs (2,3): a lane holds channels nb + 8j + 4h + e of pixel (row mt, column r).
     {
-      if (diag & 4) {                                  // (timing knock-out without the MFMA loop: nothing carried the chunks)
-#pragma unroll
-        for (int c = 0; c < (DG ? MT : NCHUNK); ++c) deferred(c);
-      }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -557,8 +496,7 @@ int launch_ws(const ConvArgs& a, hipStream_t st) {
   if (per_cb < 1) per_cb = 1;
   if (per_cb > ntiles) per_cb = ntiles;
   const int n_wg = per_cb * ncb;
-  const char* dg = getenv("STV_WS_DIAG");            // timing experiments only (results are then wrong)
-  hipLaunchKernelGGL((conv_ws_kernel<CIN, DG, RELU_IN, POOL, MASKED, DUAL>), dim3(n_wg), dim3(256), (WsLds<CIN, DG>::BYTES), st, a, n_wg, dg ? atoi(dg) : 0);
+  hipLaunchKernelGGL((conv_ws_kernel<CIN, DG, RELU_IN, POOL, MASKED, DUAL>), dim3(n_wg), dim3(256), (WsLds<CIN, DG>::BYTES), st, a, n_wg);
   STV_CHECK_LAUNCH();
   return STV_OK;
 }

@@ -323,59 +323,6 @@ def test_conv_ws_forward_pool_and_backward(case, monkeypatch):
         assert float((d / (2.0 ** -7 * torch.maximum(out.float().abs(), out_gen.float().abs()) + 1e-6)).max()) <= 1.0
 
 
-@pytest.mark.parametrize("case,skew", [((64, 75, 101), "1"), ((64, 75, 101), "0"), ((128, 40, 72), "1"), ((64, 8, 32), "1"), ((64, 13, 7), "0"),
-                                       ((64, 4, 33), "1"), ((64, 512, 512), "1"), ((128, 256, 320), "0")])
-def test_conv_ws2_forward_and_pool(case, skew, monkeypatch):
-    """The two-waves-per-SIMD form of the weight-stationary kernel (csrc/conv_ws2.hip, STV_CONV_WS2; Cin = 64, forward
-    forms; K split between the two waves of a SIMD, partial sums exchanged through LDS): bias / ReLU-on-load / ReLU /
-    fused max-pool + arg-max map / STV_POOL_ONLY against the CPU convolution, on ragged, single-tile and many-tile images,
-    with the two wave classes finishing their tile at the same time and half a tile apart (STV_WS2_SKEW)."""
-    cout, H, W = case
-    cin, dtype = 64, torch.bfloat16
-    monkeypatch.setenv("STV_CONV_WS2", "2")
-    monkeypatch.setenv("STV_WS2_SKEW", skew)
-    x = rnd((1, cin, H, W), 171)
-    w = rnd((cout, cin, 3, 3), 172, -1, 1) * (2.0 / (9 * cin)) ** 0.5
-    b = rnd((cout,), 173, -0.2, 0.2)
-    xq, wq = q(x, dtype), q(w, dtype)
-    xn = ops.to_nhwc(x, dtype).to(DEV)
-    for blocked in (True, False):
-        wp = ops.pack_weights_fwd(w).to(dtype).to(DEV)
-        if blocked:
-            wp = ops.block_weights(wp)
-        for flags in (0, ops.RELU_IN | ops.RELU_OUT):
-            ref = F.conv2d(F.relu(xq) if flags & ops.RELU_IN else xq, wq, b, padding=1)
-            ref = F.relu(ref) if flags & ops.RELU_OUT else ref
-            y = ops.conv_igemm(xn, wp, b.to(DEV), flags=flags)
-            assert_close(ops.from_nhwc(y), ref, dtype, 9 * cin, f"ws2 fwd {case} flags={flags} blocked={blocked}")
-            # the one-wave-per-SIMD kernel on the same launch: another order of the K halves, same values to rounding
-            monkeypatch.setenv("STV_CONV_WS2", "0")
-            monkeypatch.setenv("STV_CONV_WS", "2")
-            y1 = ops.conv_igemm(xn, wp, b.to(DEV), flags=flags)
-            monkeypatch.setenv("STV_CONV_WS2", "2")
-            d = (y.float() - y1.float()).abs()
-            assert float((d / (2.0 ** -7 * torch.maximum(y.float().abs(), y1.float().abs()) + 1e-6)).max()) <= 1.0
-            assert float((d > 0).float().mean()) < 5e-3
-    wp = ops.block_weights(ops.pack_weights_fwd(w).to(dtype).to(DEV))
-    for relu_in in (0, ops.RELU_IN):
-        idx = torch.full((H // 2, W // 2, cout), 255, device=DEV, dtype=torch.uint8)
-        y, yp = ops.conv_igemm_pool(xn, wp, b.to(DEV), flags=ops.RELU_OUT | relu_in, pool_idx=idx)
-        ref = F.relu(F.conv2d(F.relu(xq) if relu_in else xq, wq, b, padding=1))
-        assert_close(ops.from_nhwc(y), ref, dtype, 9 * cin, f"ws2 conv+pool {case} relu_in={relu_in}")
-        assert torch.equal(ops.from_nhwc(yp).cpu(), F.max_pool2d(ops.from_nhwc(y).cpu(), 2, 2))
-        assert int(idx.max()) <= 7
-        idx2 = torch.full_like(idx, 255)
-        y2 = torch.full_like(y, 7.0)
-        _, yp2 = ops.conv_igemm_pool(xn, wp, b.to(DEV), flags=ops.RELU_OUT | relu_in | ops.POOL_ONLY, out=y2, pool_idx=idx2)
-        assert torch.equal(yp2, yp) and torch.equal(idx2, idx) and bool((y2 == 7.0).all())
-    dyp = ops.to_nhwc(rnd((1, cout, H // 2, W // 2), 174), dtype).to(DEV)
-    for flags in (0, ops.MASK):
-        a_, b_ = torch.zeros_like(y), torch.zeros_like(y)
-        ops.maxpool_bwd(y, dyp, out=a_, flags=flags)
-        ops.maxpool_bwd_idx(idx, dyp, H, W, out=b_, flags=flags)
-        assert torch.equal(a_, b_), f"ws2 arg-max map differs from the activation-based routing, flags={flags}"
-
-
 @pytest.mark.parametrize("cfg", [None, 0, 1, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18])
 @pytest.mark.parametrize("case", [(128, 64, 32, 64), (256, 128, 16, 40), (512, 512, 8, 8), (512, 256, 12, 20)])
 def test_conv_igemm_route_equals_dgrad_then_pool_backward(cfg, case, monkeypatch):
@@ -455,123 +402,6 @@ def test_conv_igemm_every_tile_config(dtype, cfg, case, monkeypatch):
     ops.conv_igemm(ops.to_nhwc(x, dtype).to(DEV), wp, None, ref=ops.to_nhwc(z, dtype).to(DEV), out=out,
                    flags=ops.MASK | ops.ACCUM)
     assert_close(ops.from_nhwc(out), ref2, dtype, 9 * cin, f"cfg {cfg} mask+accum {case}")
-
-
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("case", [(128, 512, 21, 70, None), (256, 512, 16, 64, 3), (64, 256, 40, 33, 5), (512, 512, 8, 8, 11), (128, 384, 12, 40, 1)])
-def test_conv_xshare_changes_nothing(dtype, case, monkeypatch):
-    """STV_CONV_XSHARE = 2 / 4 deals the channel blocks of a spatial tile to 2 / 4 XCDs (ConvArgs::xshare; the block
-    decode of conv_igemm_kernel.h): another workgroup -> output-block mapping, the same per-block arithmetic - results
-    bit-identical to the default mapping, also where the block count is not divisible by the request (384 / 128 = 3
-    blocks: falls back to 1) and with a second pass (mask + accumulate) on top."""
-    cin, cout, H, W, cfg = case
-    if cfg is not None:
-        monkeypatch.setenv("STV_CONV_CFG", str(cfg))
-    x = ops.to_nhwc(rnd((1, cin, H, W), 141), dtype).to(DEV)
-    w = rnd((cout, cin, 3, 3), 142, -1, 1) * (2.0 / (9 * cin)) ** 0.5
-    wp = ops.block_weights(ops.pack_weights_fwd(w).to(dtype).to(DEV))
-    b = rnd((cout,), 143, -0.2, 0.2).to(DEV)
-    z = ops.to_nhwc(rnd((1, cout, H, W), 144), dtype).to(DEV)
-    prev = ops.to_nhwc(rnd((1, cout, H, W), 145), dtype).to(DEV)
-
-    def both():
-        y = ops.conv_igemm(x, wp, b, flags=ops.RELU_IN | ops.RELU_OUT).clone()
-        out = prev.clone()
-        ops.conv_igemm(x, wp, None, ref=z, out=out, flags=ops.MASK | ops.ACCUM)
-        return y, out
-    monkeypatch.setenv("STV_CONV_XSHARE", "1")
-    base = both()
-    ref = F.relu(F.conv2d(F.relu(ops.from_nhwc(x).cpu()), q(w, dtype), b.cpu(), padding=1))
-    assert_close(ops.from_nhwc(base[0]), ref, dtype, 9 * cin, f"xshare 1 {case}")
-    for g in (2, 4):
-        monkeypatch.setenv("STV_CONV_XSHARE", str(g))
-        got = both()
-        assert torch.equal(got[0], base[0]) and torch.equal(got[1], base[1]), f"xshare {g} {case}"
-
-
-@pytest.fixture
-def xk_workspace(monkeypatch):
-    """K split across workgroups switched on for the test, with its scratch (stv_conv_workspace)."""
-    monkeypatch.setenv("STV_CONV_XK", "1")
-    ws = torch.zeros(ops.conv_workspace_bytes(), dtype=torch.uint8, device=DEV)
-    ops.set_conv_workspace(ws)
-    yield ws
-    ops.set_conv_workspace(None)
-
-
-@pytest.mark.parametrize("case", [(512, 512, 64, 64), (512, 448, 40, 96), (256, 512, 61, 64), (512, 384, 64, 64)])
-def test_conv_split_k_across_workgroups(case, xk_workspace, monkeypatch):
-    """ConvArgs::xk (STV_CONV_XK=1): two workgroups per output tile, each on half of K, the later one adds the other's fp32
-    partial sums and runs the epilogue - every epilogue of the general kernel behind it (bias + ReLU, mask + accumulate, the
-    fused 1x1 Gram term, the max-pool + arg-max map, the routed pooling backward), ragged tiles, a tile count that is not
-    a multiple of eight (padding blocks) - against the CPU reference; the same bits on every run (a + b == b + a:
-    whichever half finishes first); the scratch words are zero again after every launch; and the plain kernel for
-    comparison (another summation order: same tolerance, not the same bits)."""
-    cin, cout, H, W = case
-    dtype = torch.bfloat16
-    ws = xk_workspace
-    x = rnd((1, cin, H, W), 151)
-    w = rnd((cout, cin, 3, 3), 152, -1, 1) * (2.0 / (9 * cin)) ** 0.5
-    b = rnd((cout,), 153, -0.2, 0.2)
-    z = rnd((1, cout, H, W), 154)
-    prev = rnd((1, cout, H, W), 155)
-    xd, bd = ops.to_nhwc(x, dtype).to(DEV), b.to(DEV)
-    wp = ops.block_weights(ops.pack_weights_fwd(w).to(dtype).to(DEV))
-    zd, pd = ops.to_nhwc(z, dtype).to(DEV), ops.to_nhwc(prev, dtype).to(DEV)
-
-    def clean():
-        torch.cuda.synchronize()
-        assert int(ws[:65536].max()) == 0, "tickets / flags not reset"
-    # forward: bias + ReLU in and out
-    ref = F.relu(F.conv2d(F.relu(q(x, dtype)), q(w, dtype), b, padding=1))
-    y1 = ops.conv_igemm(xd, wp, bd, flags=ops.RELU_IN | ops.RELU_OUT).clone()
-    clean()
-    assert_close(ops.from_nhwc(y1), ref, dtype, 9 * cin, f"xk fwd {case}")
-    for _ in range(3):
-        assert torch.equal(ops.conv_igemm(xd, wp, bd, flags=ops.RELU_IN | ops.RELU_OUT), y1), "not reproducible"
-    monkeypatch.setenv("STV_CONV_XK", "0")
-    y0 = ops.conv_igemm(xd, wp, bd, flags=ops.RELU_IN | ops.RELU_OUT)
-    monkeypatch.setenv("STV_CONV_XK", "1")
-    assert_close(ops.from_nhwc(y0), ref, dtype, 9 * cin, f"plain fwd {case}")
-    assert not torch.equal(y0, y1) or cin < 256, "the K split did not engage (same bits as the plain kernel)"
-    # mask + accumulate (a dgrad's epilogue)
-    ref2 = F.conv2d(q(x, dtype), q(w, dtype), None, padding=1) * (q(z, dtype) > 0).float() + q(prev, dtype)
-    out = pd.clone()
-    ops.conv_igemm(xd, wp, None, ref=zd, out=out, flags=ops.MASK | ops.ACCUM)
-    clean()
-    assert_close(ops.from_nhwc(out), ref2, dtype, 9 * cin, f"xk mask+accum {case}")
-    # fused max-pool + arg-max map (even sizes only)
-    if H % 2 == 0 and W % 2 == 0:
-        idx = torch.full((H // 2, W // 2, cout), 255, device=DEV, dtype=torch.uint8)
-        y, yp = ops.conv_igemm_pool(xd, wp, bd, flags=ops.RELU_OUT, pool_idx=idx)
-        clean()
-        refp = F.relu(F.conv2d(q(x, dtype), q(w, dtype), b, padding=1))
-        assert_close(ops.from_nhwc(y), refp, dtype, 9 * cin, f"xk conv+pool {case}")
-        assert torch.equal(ops.from_nhwc(yp).cpu(), F.max_pool2d(ops.from_nhwc(y).cpu(), 2, 2))
-        assert int(idx.max()) <= 7
-    # the dgrad with the Gram-backward 1x1 term of its output: dy has `cin` channels (the layer above), the output,
-    # F = z and S have `cout` (this layer) - as in test_conv_igemm_dual_dgrad_plus_gram_term
-    wd = rnd((cin, cout, 3, 3), 157, -1, 1) * (2.0 / (9 * cin)) ** 0.5
-    s_mat = rnd((cout, cout), 156, -0.02, 0.02)
-    sq = q((s_mat + s_mat.t()) * 0.5, dtype)
-    xr = torch.zeros(1, cout, H, W, requires_grad=True)
-    F.conv2d(xr, q(wd, dtype), None, padding=1).backward(q(x, dtype))
-    ref3 = xr.grad * (q(z, dtype) > 0).float() + torch.einsum("bchw,nc->bnhw", q(z, dtype), sq)
-    wb = ops.block_weights(ops.pack_weights_bwd(wd).to(dtype).to(DEV))
-    out3 = torch.empty_like(zd)
-    ops.conv_igemm_dual(xd, wb, zd, sq.to(dtype).to(DEV).contiguous(), ref=zd, out=out3, flags=ops.MASK)
-    clean()
-    assert_close(ops.from_nhwc(out3), ref3, dtype, 9 * cin + cout, f"xk dual {case}")
-    # the routed pooling backward in the epilogue (a dgrad in front of a max-pool): against the plain kernel's routing of
-    # the same sums rounded the same way is not available (another summation order), so against dgrad-then-pool-backward
-    if H % 2 == 0 and W % 2 == 0 and 4 * H * W * cout * 2 < 2 ** 31:
-        idx = torch.from_numpy((synthetic.hash_uniform(158, 3, H * W * cout) * 8).astype(np.uint8).reshape(H, W, cout)).to(DEV)
-        routed = ops.conv_igemm_route(xd, wp, idx, flags=ops.MASK)
-        clean()
-        plain = ops.conv_igemm(xd, wp, None, flags=0)            # the same sums (K split as well), unrouted
-        want = torch.zeros(2 * H, 2 * W, cout, device=DEV, dtype=dtype)
-        ops.maxpool_bwd_idx(idx, plain, 2 * H, 2 * W, out=want, flags=ops.MASK)
-        assert torch.equal(routed, want), f"xk route {case}"
 
 
 @pytest.mark.parametrize("hint_bytes", [1, 100, 4096, 1 << 20, 5 << 20])
