@@ -32,5 +32,5 @@ struct ConvArgs {
 bool stv_conv_ws_supported(const ConvArgs& a, int dtype, int taps);
 int stv_conv_ws_launch(const ConvArgs& a, hipStream_t st);
 
-// conv_igemm16.hip: the general kernel's tiles on v_mfma_f32_16x16x32_bf16 (configurations 13 and up; bf16, cin % 32 == 0).
-int stv_conv_launch_m16(const ConvArgs& a, int cfg, int taps, hipStream_t st);
+// conv_igemm16.hip: the general kernel's tiles that are built there (conv_tiles.h: kUnit16; bf16, cin % 32 == 0).
+int stv_conv_launch_unit16(const ConvArgs& a, int cfg, int taps, hipStream_t st);

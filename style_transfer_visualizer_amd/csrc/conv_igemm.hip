@@ -22,8 +22,9 @@
 // MFMA shapes: bf16 -> v_mfma_f32_32x32x16_bf16 (lane (r,h) holds k = 8h..8h+7),
 //              fp32 -> v_mfma_f32_32x32x2_f32 x4 with lane (r,h) holding
 //              k = 4h..4h+3 (any k permutation is fine as long as A and B agree).
-// ReLU-on-load (STV_RELU_IN) is one packed integer max per fragment dword (a negative bf16 / fp32
-// is a negative integer), against a scalar that is 0 or INT_MIN - branch-free.
+// ReLU-on-load (STV_RELU_IN) is one packed integer max with 0 per fragment dword (a negative bf16 /
+// fp32 is a negative integer) in a variant of the kernel of its own (the compile-time RELU
+// parameter): the launches that do not ask for it pay nothing.
 // The MFMAs take the weights as the row operand, so an accumulator lane holds 16 channels of one
 // pixel; the epilogue (bias, ReLU, ReLU mask, accumulate, the optional fused 2x2 max-pool) runs in
 // registers and v_permlane32_swap pairs the half-waves' channel groups into 16-byte stores.
@@ -96,37 +97,9 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvArgs a) {
 }
 
 // ---- tile choice --------------------------------------------------------------------------------
-// Configurations: 0 = 8x128, 1 = 8x64, 2 = 4x128, 3 = 4x64 (TH x BN), 4 = 4x64 with K split over two
-// wave groups, 5 = 8x64 and 6 = 4x64 on a two-deep LDS ring (two / three workgroups per CU),
-// 7 = 2x64 with the K split (the 32x32-pixel layers: four times the workgroups of 4x64 x 2),
-// 8 = 1x64 with the K split in four-wave workgroups (a 32x32-pixel layer then covers all 256 CUs).  -1 = the shape is outside the matrix-core tiling (direct fallback).
-constexpr int kNumCfg = 19;     // 9 / 10 = 16x64 (four row blocks per wave: half the weight traffic per output) on the three- / two-deep ring
-// 11 = 2x32 with the K split (four waves: 2 rows x 2 K groups): on a 32x32-pixel layer still one workgroup per CU, which
-// stages 434 KB instead of 1x64's 694 KB;  12 = the same on 4 rows (eight waves)
-// 13-17 = 8x64, 16x64, 4x64, 2x32 / K split, 4x32 / K split with the main loop on v_mfma_f32_16x16x32_bf16 (conv_igemm16.hip): two K-stages per
-// MFMA out of a ring of four stage slots; bf16 with cin % 32 == 0 only (fp32_cfg names the tile that serves the rest)
-// 18 = 16x128 on the two-deep ring (also built in conv_igemm16.hip; bf16 only like its neighbours there)
-const int kCfgTH[kNumCfg] = {8, 8, 4, 4, 4, 8, 4, 2, 1, 16, 16, 2, 4, 8, 16, 4, 2, 4, 16},
-          kCfgBN[kNumCfg] = {128, 64, 128, 64, 64, 64, 64, 64, 64, 64, 64, 32, 32, 64, 64, 64, 32, 32, 128};
-constexpr int kFirstM16 = 13;
-bool is_m16(int cfg) { return cfg >= kFirstM16; }       // (= "launched from conv_igemm16.hip": cin % 32 == 0, bf16)
-
-bool cfg_valid(int cfg, int cout) { return cfg >= 0 && cfg < kNumCfg && !(cout <= 64 && kCfgBN[cfg] == 128); }
-// fp32 (parity mode) keeps a second accumulator set per K-stage (blocked summation): the eight-wave tiles with 64+
-// accumulator registers per lane (8x128, 16x64) would spill at their 256-register budget, so they are served by
-// the four-wave 4x128 tile (512 registers per wave) and the 8x64 tiles instead.
-int fp32_cfg(int cfg) {
-  switch (cfg) {
-    case 0: return 2;
-    case 9: case 13: case 14: return 1;
-    case 10: return 5;
-    case 11: case 16: return 7;
-    case 12: case 17: return 4;
-    case 15: return 3;
-    case 18: return 2;
-    default: return cfg;
-  }
-}
+// The configurations are the rows of kTiles (conv_tiles.h).  -1 = the shape is outside the matrix-core tiling (direct fallback).
+bool cfg_valid(int cfg, int cout) { return cfg >= 0 && cfg < kNumCfg && !(cout <= 64 && kTiles[cfg].BN == 128); }
+int fp32_cfg(int cfg) { return kTiles[cfg].alt; }      // the tile that serves 4-byte elements in place of `cfg`
 
 // Measured choices (stv_conv_tune), keyed by shape.
 struct TuneEntry { int H, W, cin, cout, taps, esize, cfg; };
@@ -150,9 +123,9 @@ int model_cfg(int H, int W, int cin, int cout) {
   float best_cost = 3.4e38f;
   for (int i = 0; i < 4; ++i) {
     if (!cfg_valid(i, cout)) continue;
-    const long blocks = (long)ceil_div(W, 32) * ceil_div(H, kCfgTH[i]) * ceil_div(cout, kCfgBN[i]);
+    const long blocks = (long)ceil_div(W, 32) * ceil_div(H, kTiles[i].TH) * ceil_div(cout, kTiles[i].BN);
     const float waves = (float)((blocks + 255) / 256);   // eff is per CU, whatever the residency
-    const float cost = waves * (float)(kCfgTH[i] * kCfgBN[i]) / eff[i];
+    const float cost = waves * (float)(kTiles[i].TH * kTiles[i].BN) / eff[i];
     if (cost < best_cost) { best_cost = cost; best = i; }
   }
   // a grid that cannot give every CU a workgroup, on a deep K: split K inside the workgroup
@@ -167,13 +140,19 @@ int model_cfg(int H, int W, int cin, int cout) {
 // the plain conv's pick; 256^2 256->128 48 against 59 on 8x128), so it is measured as its own "shape".
 constexpr int kRouteTaps = STV_TUNE_ROUTE;
 
+// The choice without a measurement: the cost model's, but 4x64 for a routed dgrad where the model says 128 wide
+int analytic_cfg(int H, int W, int cin, int cout, int taps) {
+  const int m = model_cfg(H, W, cin, cout);
+  return (taps == kRouteTaps && kTiles[m].BN == 128) ? kRouteTile : m;
+}
+
 // elem_bytes: 2 (bf16), 4 (fp32) or kX3Key (bf16x3: fp32 storage, so the fp32 tiles and granularity)
 int choose_cfg(int H, int W, int cin, int cout, int elem_bytes, int taps = 9) {
   const int key = elem_bytes;
   if (elem_bytes == kX3Key) elem_bytes = 4;
   const int kVec = 16 / elem_bytes, CK = 32 / elem_bytes;
   if ((cin % CK) || (cout % kVec)) return -1;
-  auto served = [&](int cfg) { return (elem_bytes == 4 || (is_m16(cfg) && cin % 32)) ? fp32_cfg(cfg) : cfg; };
+  auto served = [&](int cfg) { return (elem_bytes == 4 || (kTiles[cfg].kpairs && cin % 32)) ? kTiles[cfg].alt : cfg; };
   if (const char* force = getenv("STV_CONV_CFG")) {   // tuning aid (tools/conv_sweep.py)
     const int f = atoi(force);
     if (cfg_valid(f, cout)) return served(f);
@@ -183,49 +162,21 @@ int choose_cfg(int H, int W, int cin, int cout, int elem_bytes, int taps = 9) {
   const char* tune = getenv("STV_CONV_TUNE");
   const int t = (tune && atoi(tune) == 0) ? -1 : tuned_cfg(H, W, cin, cout, taps, key);
   if (t >= 0) return served(t);
-  const int m = model_cfg(H, W, cin, cout);
-  return served((taps == kRouteTaps && (m == 0 || m == 2)) ? 3 : m);       // untuned routed dgrad: 4x64 where the model says 128-wide
+  return served(analytic_cfg(H, W, cin, cout, taps));
 }
 
-// bf16x3: the fp32 tiles (fp32_cfg's range) with split-bf16 products
-template <int TAPS>
-int launch_mfma_x3(const ConvArgs& a, int cfg, hipStream_t st) {
-  switch (fp32_cfg(cfg)) {
-    case 1: return launch_cfg<Cfg<float, 8, 64, 4, 2, TAPS, 1, 3, false, true>>(a, st);
-    case 2: return launch_cfg<Cfg<float, 4, 128, 1, 4, TAPS, 1, 3, false, true>>(a, st);
-    case 4: return launch_cfg<Cfg<float, 4, 64, 2, 2, TAPS, 2, 3, false, true>>(a, st);
-    case 5: return launch_cfg<Cfg<float, 8, 64, 4, 2, TAPS, 1, 2, false, true>>(a, st);
-    case 6: return launch_cfg<Cfg<float, 4, 64, 2, 2, TAPS, 1, 2, false, true>>(a, st);
-    case 7: return launch_cfg<Cfg<float, 2, 64, 2, 2, TAPS, 2, 3, false, true>>(a, st);
-    case 8: return launch_cfg<Cfg<float, 1, 64, 1, 2, TAPS, 2, 3, false, true>>(a, st);
-    default: return launch_cfg<Cfg<float, 4, 64, 2, 2, TAPS, 1, 3, false, true>>(a, st);
-  }
-}
-
+// Launches tile `cfg` or its stand-in.  X3: bf16x3, the fp32 tiles with split-bf16 products.
 template <typename T, int TAPS, bool X3 = false>
 int launch_mfma(const ConvArgs& a, int cfg, hipStream_t st) {
-  if constexpr (X3) return launch_mfma_x3<TAPS>(a, cfg, st);
-  if (is_m16(cfg)) {      // two K-stages per MFMA: bf16, whole pairs of 16-channel stages in both K extents
-    if (sizeof(T) == 2 && a.cin % 32 == 0 && (a.x2 == nullptr || a.cin2 % 32 == 0)) return stv_conv_launch_m16(a, cfg, TAPS, st);
-    cfg = fp32_cfg(cfg);
-  }
-  switch (cfg) {
-    // the two 8-row tiles run 8 waves (two per SIMD: one wave's waits hide under the other's MFMAs)
-    case 0: return launch_cfg<Cfg<T, 8, 128, 4, 2, TAPS>>(a, st);   // 64 px x 64 couts per wave
-    case 1: return launch_cfg<Cfg<T, 8, 64, 4, 2, TAPS>>(a, st);    // 64 px x 32 couts per wave
-    case 2: return launch_cfg<Cfg<T, 4, 128, 1, 4, TAPS>>(a, st);
-    case 4: return launch_cfg<Cfg<T, 4, 64, 2, 2, TAPS, 2>>(a, st);   // small layers: K split over two wave groups
-    case 5: return launch_cfg<Cfg<T, 8, 64, 4, 2, TAPS, 1, 2>>(a, st);
-    case 6: return launch_cfg<Cfg<T, 4, 64, 2, 2, TAPS, 1, 2>>(a, st);
-    case 7: return launch_cfg<Cfg<T, 2, 64, 2, 2, TAPS, 2>>(a, st);
-    case 8: return launch_cfg<Cfg<T, 1, 64, 1, 2, TAPS, 2>>(a, st);
-    case 9: return launch_cfg<Cfg<T, 16, 64, 4, 2, TAPS>>(a, st);
-    case 10: return launch_cfg<Cfg<T, 16, 64, 4, 2, TAPS, 1, 2>>(a, st);
-    case 11: return launch_cfg<Cfg<T, 2, 32, 2, 1, TAPS, 2>>(a, st);
-    case 12: return launch_cfg<Cfg<T, 4, 32, 4, 1, TAPS, 2>>(a, st);
-    default: return launch_cfg<Cfg<T, 4, 64, 2, 2, TAPS>>(a, st);
-  }
+  // two K-stages per MFMA: bf16, whole pairs of 16-channel stages in both K extents
+  const bool pairs = sizeof(T) == 2 && a.cin % 32 == 0 && (a.x2 == nullptr || a.cin2 % 32 == 0);
+  if (sizeof(T) == 4 || (kTiles[cfg].kpairs && !pairs)) cfg = kTiles[cfg].alt;
+  if (kTiles[cfg].unit == kUnit16) return stv_conv_launch_unit16(a, cfg, TAPS, st);
+  return launch_tile<kUnitMain, T, TAPS, X3>(a, cfg, st);
 }
+
+// a pooled output needs a tile whose waves own both rows of a pooling window
+int pool_cfg(int cfg, const ConvArgs& a) { return (cfg >= 0 && a.pool != nullptr && !tile_pools(cfg)) ? kPoolTile : cfg; }
 
 template <typename T, int TAPS>
 int launch_typed(const ConvArgs& a, hipStream_t st) {
@@ -235,8 +186,7 @@ int launch_typed(const ConvArgs& a, hipStream_t st) {
     g_stv_next_w_bytes = 0;
     return stv_conv_ws_launch(a, st);
   }
-  int cfg = choose_cfg(a.H, a.W, a.cin, a.cout, (int)sizeof(T), TAPS);
-  if ((cfg == 7 || cfg == 8 || cfg == 11 || cfg == 12 || cfg == 16 || cfg == 17) && a.pool != nullptr) cfg = 4;      // one row per wave: no pooling window
+  const int cfg = pool_cfg(choose_cfg(a.H, a.W, a.cin, a.cout, (int)sizeof(T), TAPS), a);
   if (cfg < 0) {
     const size_t total = (size_t)a.H * a.W * a.cout;
     hipLaunchKernelGGL((conv_direct_kernel<T, TAPS>), dim3((unsigned)((total + 255) / 256)),
@@ -251,10 +201,9 @@ int launch_typed(const ConvArgs& a, hipStream_t st) {
 // not a quiet fall-back to the direct kernel - and not the weight-stationary kernel (bf16 only).
 template <int TAPS>
 int launch_x3(const ConvArgs& a, hipStream_t st) {
-  int cfg = choose_cfg(a.H, a.W, a.cin, a.cout, kX3Key, TAPS);
+  const int cfg = pool_cfg(choose_cfg(a.H, a.W, a.cin, a.cout, kX3Key, TAPS), a);
   if (cfg < 0) return STV_ERR_ARG;
-  if ((cfg == 7 || cfg == 8) && a.pool != nullptr) cfg = 4;      // one row per wave: no pooling window
-  return launch_mfma_x3<TAPS>(a, cfg, st);
+  return launch_mfma<float, TAPS, true>(a, cfg, st);
 }
 
 // bf16x3 weight forms are fixed per geometry (conv_mainloop: no per-load choice in the loop): a 3x3 takes K-blocked,
@@ -346,23 +295,21 @@ int tune_typed(int H, int W, int cin, int cout, int key_taps, hipStream_t st) {
     (void)hipEventSynchronize(e1);
     (void)hipEventElapsedTime(&t_flush, e0, e1);
   }
-  int base = route ? ((model_cfg(H, W, cin, cout) == 0 || model_cfg(H, W, cin, cout) == 2) ? 3 : model_cfg(H, W, cin, cout))
-                   : model_cfg(H, W, cin, cout);
+  int base = analytic_cfg(H, W, cin, cout, key_taps);
   if (sizeof(T) == 4) base = fp32_cfg(base);
   int best = base;
   float t_best = 3.4e38f, t_base = 3.4e38f;
   int rc = STV_OK;
-  // The 16x128 tile (18) is not offered by default: it wins the hot loop by 7-9 % on every shape with >= 512 tiles and
-  // LOSES in the step (round 4: closure +1.9 % at 1024^2 with it on the 256^2 layers, nothing at 3840x2160) - see DESIGN 3.8
-  int ncfg = kNumCfg - 1;
-  if (const char* lim = getenv("STV_CONV_TUNE_CFGS")) ncfg = atoi(lim) < kNumCfg ? atoi(lim) : kNumCfg;   // A/B aid (19: every tile)
+  // the tiles that are timed: the table's `tuned` column, or rows 0 .. n-1 with STV_CONV_TUNE_CFGS=n (A/B aid; 19: every tile)
+  const char* lim = getenv("STV_CONV_TUNE_CFGS");
+  auto offered = [&](int cfg) { return lim ? cfg < atoi(lim) : kTiles[cfg].tuned; };
   // two interleaved rounds, the faster time of each configuration counts: one round's order effects
   // (clock ramp after the fill, a neighbour's tail) otherwise decide between near-equal tiles
   float t_cfg[kNumCfg];
   for (int cfg = 0; cfg < kNumCfg; ++cfg) t_cfg[cfg] = 3.4e38f;
   for (int round = 0; round < 2 && rc == STV_OK; ++round)
-    for (int cfg = 0; cfg < ncfg && rc == STV_OK; ++cfg) {
-      if (!cfg_valid(cfg, cout) || (sizeof(T) == 4 && fp32_cfg(cfg) != cfg)) continue;
+    for (int cfg = 0; cfg < kNumCfg && rc == STV_OK; ++cfg) {
+      if (!offered(cfg) || !cfg_valid(cfg, cout) || (sizeof(T) == 4 && fp32_cfg(cfg) != cfg)) continue;
       const int kWarm = 2, kReps = flushbuf ? 6 : 10;
       for (int i = 0; i < kWarm && rc == STV_OK; ++i)
         rc = taps == 9 ? launch_mfma<T, 9, X3>(a, cfg, st) : launch_mfma<T, 1, X3>(a, cfg, st);
@@ -378,7 +325,7 @@ int tune_typed(int H, int W, int cin, int cout, int key_taps, hipStream_t st) {
       if (flushbuf) ms -= t_flush;
       if (ms < t_cfg[cfg]) t_cfg[cfg] = ms;
     }
-  for (int cfg = 0; cfg < ncfg; ++cfg) {
+  for (int cfg = 0; cfg < kNumCfg; ++cfg) {     // (a tile that was not timed keeps its 3.4e38)
     if (cfg == base) t_base = t_cfg[cfg];
     if (t_cfg[cfg] < t_best) { t_best = t_cfg[cfg]; best = cfg; }
   }

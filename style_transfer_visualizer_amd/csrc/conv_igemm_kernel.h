@@ -1,12 +1,14 @@
 // The implicit-GEMM convolution kernel template and its launcher (description: conv_igemm.hip).
-// A header so that the tile configurations can be instantiated in more than one translation unit (conv_igemm.hip: the
-// tiles on v_mfma_f32_32x32x16_bf16 / the fp32 tiles; conv_igemm16.hip: the tiles whose main loop runs on
-// v_mfma_f32_16x16x32_bf16) and built in parallel.
+// A header so that the tile configurations (conv_tiles.h) can be instantiated in more than one translation unit
+// (conv_igemm.hip: the tiles on v_mfma_f32_32x32x16_bf16 / the fp32 tiles; conv_igemm16.hip: the tiles whose main loop
+// runs on v_mfma_f32_16x16x32_bf16) and built in parallel.
 #pragma once
 #include <type_traits>
+#include <utility>
 
 #include "stv_common.h"
 #include "conv_args.h"
+#include "conv_tiles.h"
 
 #ifndef STV_STAMP          // (conv_igemm.hip defines the phase-stamp macro first in its diagnostic build)
 #define STV_STAMP(k) do {} while (0)
@@ -162,23 +164,6 @@ __device__ __forceinline__ void mma_any(const bf16x8v& w, const X3Act& a, f32x16
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a.q, acc, 0, 0, 0);
 }
 
-// ReLU of a fragment as a packed integer max against `floor` (0: ReLU on, INT_MIN pattern: off)
-__device__ __forceinline__ bf16x8v relu_frag(bf16x8v v, uint32_t floor) {
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const s16x8 lo = (s16x8)((short)(floor & 0xFFFFu));                  // splat
-  return __builtin_bit_cast(bf16x8v, __builtin_elementwise_max(__builtin_bit_cast(s16x8, v), lo));
-}
-__device__ __forceinline__ f32x4 relu_frag(f32x4 v, uint32_t floor) {
-  typedef __attribute__((ext_vector_type(4))) int i32x4;
-  const i32x4 lo = (i32x4)((int)floor);
-  return __builtin_bit_cast(f32x4, __builtin_elementwise_max(__builtin_bit_cast(i32x4, v), lo));
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // One pass of the implicit GEMM over a whole K range: streams `ph` (input tensor, weight tensor,
 // their K extent) through the LDS ring and accumulates into `acc`.  The kernel runs it once for
 // a plain convolution and a second time - 1x1 geometry, other tensors, same accumulators - for
@@ -189,7 +174,6 @@ struct Phase {
   const T* w;
   int cin;
   bool w_blocked;
-  uint32_t relu_floor;
 };
 struct Geom {
   int H, W, cout, x0, y0, n0;
@@ -373,7 +357,6 @@ __device__ __forceinline__ void conv_mainloop(const Phase<typename C::Elem>& ph,
         if (k < C::PPW) dma(k, l + C::NBUF - 1, fill);
       __builtin_amdgcn_sched_barrier(0);
       if (step >= NSTEP - NHOLD) {
-        constexpr int dummy = 0; (void)dummy;
         const int q = step - (NSTEP - NHOLD);
 #pragma unroll
         for (int mt = 0; mt < C::MT; ++mt) hold_a[q][mt] = af[dx & 1][mt + dy];
@@ -607,6 +590,29 @@ __device__ __forceinline__ void acc16_to_acc32(const f32x4 (&a16)[C::MT][2][C::N
         }
 }
 
+// One phase on whichever main loop the tile has: its product lands in `acc` (`add`: on top of what is there; the
+// 32x32 loop accumulates in place either way, so its first phase starts from zeroed accumulators).  The 16x16x32
+// loop works in blocks of its own, which then move into the layout the epilogue is written for.
+template <typename C, bool RELU>
+__device__ __forceinline__ void run_phase(const Phase<typename C::Elem>& ph, const Geom& gm, char* smem,
+                                          f32x16 (&acc)[C::MT][C::NT], bool add) {
+  if constexpr (C::M16) {
+    f32x4 a16[C::MT][2][C::NT][2];
+#pragma unroll
+    for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+      for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+        for (int nt = 0; nt < C::NT; ++nt)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) a16[mt][pb][nt][cb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    conv_mainloop16<C, RELU>(ph, gm, smem, a16);
+    acc16_to_acc32<C>(a16, acc, add);
+  } else {
+    conv_mainloop<C, RELU>(ph, gm, smem, acc);
+  }
+}
+
 template <typename C, bool RELU>
 __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (LDS address-space casts are device-only)
@@ -642,13 +648,10 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
   const T* __restrict__ xin = static_cast<const T*>(a.x);
   const T* __restrict__ wgt = static_cast<const T*>(a.w);
   const bool w_blocked = (a.flags & STV_W_BLOCKED) != 0;
-  // ReLU-on-load floor: integer max with 0 clears negative elements, with INT_MIN it is the identity
-  const uint32_t relu_floor = (a.flags & STV_RELU_IN) ? 0u : (sizeof(T) == 2 ? 0x80008000u : 0x80000000u);
   STV_STAMP(0);
   // Accumulator layout (MFMA roles: rows = output channels, columns = pixels): this lane owns
   // pixel r of its wave's row blocks and, per 32-channel block, channels 8j + 4h + e (j, e < 4).
   // Its bias values are requested first: a global round trip is ~2 us on a busy chip.
-  const int wm_ = (wave / C::WN), wn_ = (wave % C::WN);
   const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(a.bias), 0, a.bias != nullptr ? a.cout * 4 : 0, 0x00020000);
   f32x4 bias_v[C::NT][4];           // channels past cout (and a null bias) read as zero
@@ -657,7 +660,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
     for (int nt = 0; nt < C::NT; ++nt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int nn = n0 + wn_ * (C::NT * 32) + nt * 32 + 8 * j + 4 * (lane >> 5);
+        const int nn = n0 + wn * (C::NT * 32) + nt * 32 + 8 * j + 4 * (lane >> 5);
         const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs_b, (uint32_t)(nn * 4), 0, 0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) bias_v[nt][j][e] = __uint_as_float(t[e]);
@@ -675,22 +678,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
 
   constexpr uint32_t kOob = 0x80000000u;   // >= num_records for every tensor this kernel accepts
   const Geom geom{a.H, a.W, a.cout, x0, y0, n0, lane, wave, grp, wm, wn, r, h};
-  const Phase<T> ph1{xin, wgt, a.cin, w_blocked, relu_floor};
-  if constexpr (C::M16) {
-    f32x4 a16[C::MT][2][C::NT][2];
-#pragma unroll
-    for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-      for (int pb = 0; pb < 2; ++pb)
-#pragma unroll
-        for (int nt = 0; nt < C::NT; ++nt)
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb) a16[mt][pb][nt][cb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    conv_mainloop16<C, RELU>(ph1, geom, smem, a16);
-    acc16_to_acc32<C>(a16, acc, false);
-  } else {
-    conv_mainloop<C, RELU>(ph1, geom, smem, acc);
-  }
+  run_phase<C, RELU>(Phase<T>{xin, wgt, a.cin, w_blocked}, geom, smem, acc, false);
   STV_STAMP(2);
 
   // ---- fused second term (3x3 kernels only): the ReLU mask belongs to the first term alone, so it
@@ -719,10 +707,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
                 for (int e = 0; e < 4; ++e) acc[mt][nt][4 * j + e] = (__uint_as_float(m[e]) > 0.0f) ? acc[mt][nt][4 * j + e] : 0.0f;
               } else {
                 const auto m = __builtin_amdgcn_raw_buffer_load_b64(rs_m, off, 0, 0);
-                acc[mt][nt][4 * j + 0] = ((int)(m[0] << 16) > 0) ? acc[mt][nt][4 * j + 0] : 0.0f;
-                acc[mt][nt][4 * j + 1] = ((int)(m[0] & 0xFFFF0000u) > 0) ? acc[mt][nt][4 * j + 1] : 0.0f;
-                acc[mt][nt][4 * j + 2] = ((int)(m[1] << 16) > 0) ? acc[mt][nt][4 * j + 2] : 0.0f;
-                acc[mt][nt][4 * j + 3] = ((int)(m[1] & 0xFFFF0000u) > 0) ? acc[mt][nt][4 * j + 3] : 0.0f;
+                keep_where_bf16_positive(acc[mt][nt], 4 * j, m[0], m[1]);
               }
             }
         }
@@ -730,23 +715,8 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
       }
       using C1 = Cfg<T, C::TH, C::BN, C::WM, C::WN, 1, C::KS, C::NBUF, C::M16, C::X3>;
       static_assert(C1::RING_BYTES <= C::LDS_BYTES, "the 1x1 pass reuses the 3x3 ring");
-      const Phase<T> ph2{static_cast<const T*>(a.x2), static_cast<const T*>(a.w2), a.cin2, false,
-                         sizeof(T) == 2 ? 0x80008000u : 0x80000000u};
-      if constexpr (C::M16) {            // the 1x1 product in blocks of its own, then added in the epilogue's layout
-        f32x4 b16[C::MT][2][C::NT][2];
-#pragma unroll
-        for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-          for (int pb = 0; pb < 2; ++pb)
-#pragma unroll
-            for (int nt = 0; nt < C::NT; ++nt)
-#pragma unroll
-              for (int cb = 0; cb < 2; ++cb) b16[mt][pb][nt][cb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        conv_mainloop16<C1, false>(ph2, geom, smem, b16);
-        acc16_to_acc32<C>(b16, acc, true);
-      } else {
-        conv_mainloop<C1, false>(ph2, geom, smem, acc);
-      }
+      const Phase<T> ph2{static_cast<const T*>(a.x2), static_cast<const T*>(a.w2), a.cin2, false};
+      run_phase<C1, false>(ph2, geom, smem, acc, true);
     }
   }
 
@@ -846,10 +816,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
                 const uint32_t off = (poff != kOob && nn < a.cout) ? poff + (uint32_t)(nn * 2) : kOob;
                 if (masked) {     // the mask applies to the new term only: it has to come first
                   const auto m = __builtin_amdgcn_raw_buffer_load_b64(rs_ref, off, 0, 0);
-                  v[0] = ((int)(m[0] << 16) > 0) ? v[0] : 0.0f;
-                  v[1] = ((int)(m[0] & 0xFFFF0000u) > 0) ? v[1] : 0.0f;
-                  v[2] = ((int)(m[1] << 16) > 0) ? v[2] : 0.0f;
-                  v[3] = ((int)(m[1] & 0xFFFF0000u) > 0) ? v[3] : 0.0f;
+                  keep_where_bf16_positive(v, 0, m[0], m[1]);
                 }
                 const auto o = __builtin_amdgcn_raw_buffer_load_b64(rs_old, off, 0, 0);
                 v[0] += __uint_as_float(o[0] << 16);
@@ -1006,6 +973,30 @@ int launch_cfg(const ConvArgs& a_in, hipStream_t st) {
   else hipLaunchKernelGGL((conv_igemm_kernel<C, false>), grid, dim3(C::THREADS), C::LDS_BYTES, st, a);
   STV_CHECK_LAUNCH();
   return STV_OK;
+}
+
+// Row I of the tile table (conv_tiles.h), if translation unit UNIT builds it for element T: the one place that turns a
+// row into its Cfg<...>.  4-byte elements (fp32, bf16x3) instantiate only the rows that serve them.
+template <TileUnit UNIT, typename T, int TAPS, bool X3, int I>
+bool launch_row(const ConvArgs& a, int cfg, hipStream_t st, int& rc) {
+  constexpr Tile t = kTiles[I];
+  if constexpr (t.unit == UNIT && (sizeof(T) == 2 || tile_serves_f32(I))) {
+    if (cfg == I) {
+      rc = launch_cfg<Cfg<T, t.TH, t.BN, t.WM, t.WN, TAPS, t.KS, t.NBUF, t.M16, X3>>(a, st);
+      return true;
+    }
+  }
+  return false;
+}
+template <TileUnit UNIT, typename T, int TAPS, bool X3, int... I>
+int launch_rows(const ConvArgs& a, int cfg, hipStream_t st, std::integer_sequence<int, I...>) {
+  int rc = STV_ERR_ARG;      // (a row this unit does not build for T: conv_igemm.hip::launch_mfma maps those away)
+  (void)(launch_row<UNIT, T, TAPS, X3, I>(a, cfg, st, rc) || ...);
+  return rc;
+}
+template <TileUnit UNIT, typename T, int TAPS, bool X3 = false>
+int launch_tile(const ConvArgs& a, int cfg, hipStream_t st) {
+  return launch_rows<UNIT, T, TAPS, X3>(a, cfg, st, std::make_integer_sequence<int, kNumCfg>{});
 }
 
 }  // namespace

@@ -89,17 +89,6 @@ template <int CIN, bool DG> struct WsLds {
 static_assert(WsLds<64, true>::BYTES <= 160 * 1024 && WsLds<64, false>::BYTES <= 160 * 1024, "LDS budget");
 static_assert(WsLds<128, true>::BYTES <= 160 * 1024 && WsLds<128, false>::BYTES <= 160 * 1024, "LDS budget");
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ bf16x8v relu_frag(bf16x8v v, uint32_t floor) {
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const s16x8 lo = (s16x8)((short)(floor & 0xFFFFu));
-  return __builtin_bit_cast(bf16x8v, __builtin_elementwise_max(__builtin_bit_cast(s16x8, v), lo));
-}
-
 template <int CIN, bool DG, bool RELU_IN, bool POOL, bool MASKED = false, bool DUAL = false>
 __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgroups) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -406,10 +395,7 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(ConvArgs a, int n_workgrou
           for (int j = 0; j < 4; ++j) {
             const int off = (2 * wn + (j >> 1)) * F_STAGE + fp * KB + (((j & 1) ^ swz) << 4) + 8 * h;
             const uint2 m = *reinterpret_cast<const uint2*>(fb + off);
-            acc[mt][4 * j + 0] = ((int)(m.x << 16) > 0) ? acc[mt][4 * j + 0] : 0.0f;
-            acc[mt][4 * j + 1] = ((int)(m.x & 0xFFFF0000u) > 0) ? acc[mt][4 * j + 1] : 0.0f;
-            acc[mt][4 * j + 2] = ((int)(m.y << 16) > 0) ? acc[mt][4 * j + 2] : 0.0f;
-            acc[mt][4 * j + 3] = ((int)(m.y & 0xFFFF0000u) > 0) ? acc[mt][4 * j + 3] : 0.0f;
+            keep_where_bf16_positive(acc[mt], 4 * j, m.x, m.y);
           }
         }
         if constexpr (dual) {

@@ -46,6 +46,33 @@ __device__ __forceinline__ uint32_t relu_bf16x2(uint32_t w) {
   return w & ~m;
 }
 
+// ReLU of a fragment as a packed integer max against `floor` (0: ReLU; a negative bf16 / fp32 is a negative integer)
+__device__ __forceinline__ bf16x8v relu_frag(bf16x8v v, uint32_t floor) {
+  typedef __attribute__((ext_vector_type(8))) short s16x8;
+  const s16x8 lo = (s16x8)((short)(floor & 0xFFFFu));                  // splat
+  return __builtin_bit_cast(bf16x8v, __builtin_elementwise_max(__builtin_bit_cast(s16x8, v), lo));
+}
+__device__ __forceinline__ f32x4 relu_frag(f32x4 v, uint32_t floor) {
+  typedef __attribute__((ext_vector_type(4))) int i32x4;
+  const i32x4 lo = (i32x4)((int)floor);
+  return __builtin_bit_cast(f32x4, __builtin_elementwise_max(__builtin_bit_cast(i32x4, v), lo));
+}
+
+// acc[base .. base + 3] (a float array or vector) kept where the packed bf16 reference value of the same channel
+// ({m0: channels 0, 1; m1: 2, 3}) is positive, zeroed elsewhere: positive <=> its 16 bits, as the top of an int, are > 0
+template <typename Acc>
+__device__ __forceinline__ void keep_where_bf16_positive(Acc& acc, int base, uint32_t m0, uint32_t m1) {
+  acc[base + 0] = ((int)(m0 << 16) > 0) ? acc[base + 0] : 0.0f;
+  acc[base + 1] = ((int)(m0 & 0xFFFF0000u) > 0) ? acc[base + 1] : 0.0f;
+  acc[base + 2] = ((int)(m1 << 16) > 0) ? acc[base + 2] : 0.0f;
+  acc[base + 3] = ((int)(m1 & 0xFFFF0000u) > 0) ? acc[base + 3] : 0.0f;
+}
+
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
 template <typename T> struct elem_traits;
 template <> struct elem_traits<float> {
   static constexpr int kVec = 4;  // elements per 16-byte vector
