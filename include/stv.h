@@ -146,6 +146,11 @@ void stv_conv_next_weights(const void* w, size_t bytes);
 /* Number of tile configurations stv_conv_config() can return (0 .. n-1): tools and the bench that name the kernel
  * instantiation of a tile check their tables against it. */
 int stv_conv_num_configs(void);
+/* What the calling thread's most recent stv_conv_igemm* call launched: the tile-table row (0 .. n-1) after every
+ * stand-in rule (4-byte elements, whole stage pairs in both K extents, a pooled output on a tile without a pooling
+ * window), -1 for the direct kernel, -2 for the weight-stationary kernel.  Host bookkeeping, no device work: the
+ * tests use it to check that a forced tile (STV_CONV_CFG) is the tile that ran.  Since version 102. */
+int stv_conv_last_launch(void);
 int stv_conv_igemm(const void* x, const void* w, const float* bias, const void* ref,
                    void* y, int H, int W, int cin, int cout, int taps, int flags,
                    int dtype, void* stream);

@@ -165,12 +165,18 @@ int choose_cfg(int H, int W, int cin, int cout, int elem_bytes, int taps = 9) {
   return served(analytic_cfg(H, W, cin, cout, taps));
 }
 
+// What this thread's most recent conv entry point launched (stv_conv_last_launch): the table row after every
+// stand-in rule, kLaunchedDirect / kLaunchedWs for the two kernels outside the table.  Host bookkeeping only.
+constexpr int kLaunchedDirect = -1, kLaunchedWs = -2;
+thread_local int g_last_launch = kLaunchedDirect;
+
 // Launches tile `cfg` or its stand-in.  X3: bf16x3, the fp32 tiles with split-bf16 products.
 template <typename T, int TAPS, bool X3 = false>
 int launch_mfma(const ConvArgs& a, int cfg, hipStream_t st) {
   // two K-stages per MFMA: bf16, whole pairs of 16-channel stages in both K extents
   const bool pairs = sizeof(T) == 2 && a.cin % 32 == 0 && (a.x2 == nullptr || a.cin2 % 32 == 0);
   if (sizeof(T) == 4 || (kTiles[cfg].kpairs && !pairs)) cfg = kTiles[cfg].alt;
+  g_last_launch = cfg;
   if (kTiles[cfg].unit == kUnit16) return stv_conv_launch_unit16(a, cfg, TAPS, st);
   return launch_tile<kUnitMain, T, TAPS, X3>(a, cfg, st);
 }
@@ -184,10 +190,12 @@ int launch_typed(const ConvArgs& a, hipStream_t st) {
   if (stv_conv_ws_supported(a, elem_traits<T>::kDtype, TAPS)) {
     g_stv_next_w = nullptr;        // (the weight-stationary kernel does not touch ahead: the hint is consumed, not left for a later launch)
     g_stv_next_w_bytes = 0;
+    g_last_launch = kLaunchedWs;
     return stv_conv_ws_launch(a, st);
   }
   const int cfg = pool_cfg(choose_cfg(a.H, a.W, a.cin, a.cout, (int)sizeof(T), TAPS), a);
   if (cfg < 0) {
+    g_last_launch = kLaunchedDirect;
     const size_t total = (size_t)a.H * a.W * a.cout;
     hipLaunchKernelGGL((conv_direct_kernel<T, TAPS>), dim3((unsigned)((total + 255) / 256)),
                        dim3(256), 0, st, a);
@@ -476,6 +484,8 @@ extern "C" int stv_conv_igemm_pool(const void* x, const void* w, const float* bi
 }
 
 extern "C" int stv_conv_num_configs(void) { return kNumCfg; }
+
+extern "C" int stv_conv_last_launch(void) { return g_last_launch; }
 
 extern "C" void stv_conv_next_weights(const void* w, size_t bytes) {
   g_stv_next_w = (bytes > 0 && bytes < ((size_t)1 << 31)) ? w : nullptr;

@@ -16,7 +16,9 @@ import torch.nn.functional as F
 
 from oracle import core_model_ref as ocm
 from oracle import optim_ref
-from style_transfer_visualizer_amd import ops, synthetic
+from style_transfer_visualizer_amd import _lib, ops, synthetic
+
+from . import exact_ints as ei
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +41,16 @@ def tol(dtype, k_terms=1):
     if dtype == torch.float32:
         return 2e-6 * max(1.0, k_terms ** 0.5)
     return 6e-3
+
+
+def assert_ran(cfg, dtype, cin, cin2=None, *, pooled=False):
+    """A forced tile (STV_CONV_CFG=cfg) is the tile that ran: the row itself, or the stand-in the table names for it
+    (4-byte elements, broken stage pairs, a pooled output on a tile without a pooling window) - tests/exact_ints.py."""
+    if cfg is None:
+        return
+    want = ei.expected_row(cfg, "bf16" if dtype == torch.bfloat16 else "fp32", cin, cin2, pooled=pooled)
+    got = int(_lib.load().stv_conv_last_launch())
+    assert got == want, f"STV_CONV_CFG={cfg}: launched row {got}, expected row {want}"
 
 
 def assert_close(got, ref, dtype, k_terms=1, what=""):
@@ -207,6 +219,7 @@ def test_conv_igemm_dual_dgrad_plus_gram_term(dtype, cfg, flags, case, monkeypat
     ref, dev = _dual_case(dtype, flags, case)
     out = dev["prev"].clone()
     ops.conv_igemm_dual(dev["dy"], dev["wb"], dev["z"], dev["s"], ref=dev["z"] if flags & ops.MASK else None, out=out, flags=flags)
+    assert_ran(cfg, dtype, cd, cs)
     assert_close(ops.from_nhwc(out), ref, dtype, 9 * cd + cs, f"dual {case} flags={flags}")
 
 
@@ -227,6 +240,7 @@ def test_conv_igemm_with_fused_maxpool(dtype, cfg, case, monkeypatch):
     wp = ops.block_weights(ops.pack_weights_fwd(w).to(dtype).to(DEV))
     idx = torch.full((H // 2, W // 2, cout), 255, device=DEV, dtype=torch.uint8)
     y, yp = ops.conv_igemm_pool(ops.to_nhwc(x, dtype).to(DEV), wp, b.to(DEV), flags=ops.RELU_OUT, pool_idx=idx)
+    assert_ran(cfg, dtype, cin, pooled=True)
     assert_close(ops.from_nhwc(y), ref, dtype, 9 * cin, f"conv {case}")
     assert yp.shape == (H // 2, W // 2, cout)
     # the pooled map is exactly the pool of the stored map (same rounding, max commutes with it)
@@ -351,6 +365,7 @@ def test_conv_igemm_route_equals_dgrad_then_pool_backward(cfg, case, monkeypatch
         ops.maxpool_bwd_idx(idx, pooled_grad, 2 * H, 2 * W, out=want, flags=flags)
         got = torch.full((2 * H, 2 * W, cs), -3.0, device=DEV, dtype=dtype)
         ops.conv_igemm_route(dy, wb, idx, out=got, flags=flags)
+        assert_ran(cfg, dtype, cd)
         assert torch.equal(got, want), f"route {case} cfg={cfg} flags={flags}"
 
 
@@ -396,11 +411,13 @@ def test_conv_igemm_every_tile_config(dtype, cfg, case, monkeypatch):
     ref = F.relu(F.conv2d(F.relu(q(x, dtype)), q(w, dtype), b, padding=1))
     wp = ops.block_weights(ops.pack_weights_fwd(w).to(dtype).to(DEV))
     y = ops.conv_igemm(ops.to_nhwc(x, dtype).to(DEV), wp, b.to(DEV), flags=ops.RELU_IN | ops.RELU_OUT)
+    assert_ran(cfg, dtype, cin)
     assert_close(ops.from_nhwc(y), ref, dtype, 9 * cin, f"cfg {cfg} fwd {case}")
     ref2 = F.conv2d(q(x, dtype), q(w, dtype), None, padding=1) * (q(z, dtype) > 0).float() + q(prev, dtype)
     out = ops.to_nhwc(prev, dtype).to(DEV)
     ops.conv_igemm(ops.to_nhwc(x, dtype).to(DEV), wp, None, ref=ops.to_nhwc(z, dtype).to(DEV), out=out,
                    flags=ops.MASK | ops.ACCUM)
+    assert_ran(cfg, dtype, cin)
     assert_close(ops.from_nhwc(out), ref2, dtype, 9 * cin, f"cfg {cfg} mask+accum {case}")
 
 
