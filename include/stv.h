@@ -334,6 +334,26 @@ int stv_lbfgsc_dots(const float* grad, void* state, void* workspace, size_t n, i
 int stv_lbfgsc_apply(float* x, const float* grad, void* state, void* workspace, size_t n, int history, float lr,
                      float tol_grad, float tol_change, void* stream);
 size_t stv_lbfgsc_dots_offset(size_t n, int history, int* count, int* max_index);
+/* Since version 103.  torch.optim.LBFGS.step with max_iter > 1 (no line search), one call per iteration:
+ * `iters_per_step` consecutive calls on one state block are ONE optimizer step, each behind the evaluation of the
+ * image the previous call left.  iters_per_step = min(max_iter, max(1, max_eval - 1)) is known on the host; the step's
+ * data-dependent exits are decided on the device and nothing is read back: the position inside the step and a
+ * live/dead flag live in the state block, so the same call (one captured program) serves every position.
+ *   call 1:  max|g| <= tol_grad                              -> nothing changes (torch's early return), rest of the step dead
+ *   call k>1, tested in front of any state change, each:      -> nothing changes, rest of the step dead
+ *            max|g| <= tol_grad,  max|fl32(d*t)| <= tol_change (d, t of the previous iteration),
+ *            |loss - prev_loss| < tol_change (formed in double from the two fp32 values; NaN never stops)
+ *   g.d > -tol_change                                         -> state saved, image not moved, rest of the step dead
+ * A dead call is a no-op, so the caller keeps issuing the step's remaining evaluations + calls: they see an unchanged
+ * image.  `loss`: device fp32 scalar, the total score of the evaluation that produced `grad`.  With
+ * iters_per_step = 1 the call is bit-identical to stv_lbfgsc_step (image and workspace).  State and workspace are the
+ * ones of stv_lbfgsc_step; m_max counts iterations.  stv_lbfgsc_iter_reset: the step was abandoned midway (the closure
+ * raised) - the next call is call 1 of a new step; an enqueue on `stream`, not a synchronisation.
+ * The sharded halves (stv_lbfgsc_dots / _apply) and stv_lbfgs_step stay one iteration per step. */
+int stv_lbfgsc_iter(float* x, const float* grad, const float* loss, void* state, void* workspace, size_t n,
+                    int history, int m_max, int iters_per_step, float lr, float tol_grad, float tol_change,
+                    void* stream);
+int stv_lbfgsc_iter_reset(void* state, void* stream);
 /* scalars are computed in double on the host exactly as torch does
  * (1-beta1, 1-beta2, 1-beta1**t, sqrt(1-beta2**t)) and passed rounded to fp32 */
 int stv_adam_step(float* x, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n,
@@ -347,7 +367,7 @@ enum {
   STV_OP_CONV_FIRST_FWD = 1, STV_OP_CONV_FIRST_DGRAD, STV_OP_CONV, STV_OP_POOL_FWD,
   STV_OP_POOL_BWD, STV_OP_RELU_FWD, STV_OP_RELU_BWD, STV_OP_GRAM_PARTIAL,
   STV_OP_GRAM_FINISH, STV_OP_CONTENT_LOSS, STV_OP_CONTENT_GRAD, STV_OP_LOSS_COMBINE,
-  STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP
+  STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER
 };
 /* Scheduling hints in stv_op_t.flags (masked off before the kernel sees them):
  * an op with STV_LANE_SIDE may run concurrently with the ops after it: it reads only
@@ -367,7 +387,9 @@ enum { STV_LANE_SIDE = 1 << 29, STV_LANE_JOIN = 1 << 30 };
  * LBFGS_STEP runs stv_lbfgsc_step as the LAST op of a step's schedule (p0 = grad, q0 = x, q1 = state, q2 = workspace,
  * n = elements, cin = history, cout = m_max, f0 = lr, f1 = tol_grad, f2 = tol_change): closure and optimizer update are
  * then one replayed hipGraph - the reference's optimizer.step(closure), optimization.py:186, without a graph boundary
- * between the two. */
+ * between the two.
+ * LBFGS_ITER runs stv_lbfgsc_iter in the same place with the same operands, plus p1 = loss (device fp32 scalar: the
+ * total score LOSS_COMBINE wrote) and taps = iters_per_step: the one program replays for every iteration of every step. */
 typedef struct {
   int32_t op, dtype, flags, taps;
   int32_t H, W, cin, cout;

@@ -19,7 +19,7 @@ LANE_SIDE, LANE_JOIN = 1 << 29, 1 << 30          # scheduling hints of the comma
 
 (OP_CONV_FIRST_FWD, OP_CONV_FIRST_DGRAD, OP_CONV, OP_POOL_FWD, OP_POOL_BWD, OP_RELU_FWD,
  OP_RELU_BWD, OP_GRAM_PARTIAL, OP_GRAM_FINISH, OP_CONTENT_LOSS, OP_CONTENT_GRAD,
- OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP) = range(1, 16)
+ OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER) = range(1, 17)
 
 CONTENT_LOSS_PARTS = 256
 
@@ -104,6 +104,9 @@ SIGNATURES = {
     "stv_lbfgsc_dots": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "stv_lbfgsc_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_float, c_void_p]),
     "stv_lbfgsc_dots_offset": (c_size_t, [c_size_t, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "stv_lbfgsc_iter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_float, c_float, c_float,
+                                c_void_p]),
+    "stv_lbfgsc_iter_reset": (c_int, [c_void_p, c_void_p]),
     "stv_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p]),
     "stv_program_create": (c_int, [ctypes.POINTER(StvOp), c_int, ctypes.POINTER(c_void_p)]),
     "stv_program_run": (c_int, [c_void_p, c_int, c_void_p]),

@@ -589,6 +589,10 @@ class _Engine:
                 op = s._op(op=_lib.OP_LBFGS_STEP, p0=grad, q0=x, q1=then_step.state, q2=then_step.work, n=x.numel(),
                            cin=then_step.history, cout=then_step.history, f0=then_step.lr, f1=then_step.tol_grad,
                            f2=then_step.tol_change)
+                if then_step.iters_per_step:
+                    # several iterations per optimizer step: the same program replays for each of them (position and
+                    # stop flag are device state); the step's loss test reads the total the combine op wrote
+                    op.op, op.taps, op.p1 = _lib.OP_LBFGS_ITER, then_step.iters_per_step, self.scores[2:].data_ptr()
                 op.flags |= _lib.LANE_JOIN
                 tail.append(op)
             return (self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w)

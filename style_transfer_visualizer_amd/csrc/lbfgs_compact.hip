@@ -1,5 +1,5 @@
 // L-BFGS step in "dot-product space": the same update as torch.optim.LBFGS.step
-// (max_iter = 1, no line search; see optim.hip for the operation-ordered form)
+// (no line search; see optim.hip for the operation-ordered form; stv_lbfgsc_iter: max_iter > 1, one call per iteration)
 // but with the history read exactly twice per step instead of through 2m
 // dependent vector passes.
 //
@@ -17,6 +17,7 @@
 //            coefficients (in double) and emits d = cg*g + sum cs_j s_j + cy_j y_j;
 //   pass B : second sweep forms d, applies x += t*d and prev_g = g.
 // HBM traffic per step: (4m + 8) vectors instead of ~(8m) with 2m+4 launches.
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -32,11 +33,15 @@ namespace {
 
 constexpr int MAX_HIST = 128;
 constexpr int MAX_S = MAX_HIST + 1;
-constexpr int NSCAL = 8;   // gmax, |g|_1, g.g, g.s_c, g.y_c, s_c.y_c, y_c.y_c, (spare)
+constexpr int NSCAL = 8;   // gmax, |g|_1, g.g, g.s_c, g.y_c, s_c.y_c, y_c.y_c, max|d*t| (stv_lbfgsc_iter only)
+constexpr int SC_DTMAX = 7;
 
+// step_pos / prev_loss belong to stv_lbfgsc_iter (several iterations per optimizer step): step_pos = k after the
+// k-th call of a step while the step is live, -k once a data-dependent exit has made the rest of it dead, 0 between
+// steps; prev_loss = the loss consumed by the last iteration that ran.  stv_lbfgsc_step / _apply carry both through.
 struct CState {
-  int n_iter, hist_len, head, skip, no_update, pushed, steps_seen, pad0;
-  float t, H_diag, gtd, gmax, ys, yy, cg, pad1;
+  int n_iter, hist_len, head, skip, no_update, pushed, steps_seen, step_pos;
+  float t, H_diag, gtd, gmax, ys, yy, cg, prev_loss;
   float ro[MAX_S];   // by ring slot
   float cs[MAX_S];   // direction coefficients by ring slot
   float cy[MAX_S];
@@ -110,9 +115,11 @@ __device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b) {
 }
 
 // ---- pass A ---------------------------------------------------------------------------------
-template <int U, bool NT = false, bool PIPE = false>
-__global__ __launch_bounds__(256) void pass_a_kernel(const float* __restrict__ g, const CState* st, CWs w,
-                                                     size_t n, size_t nn, int hist, int nparts, int ntiles, int pgroups) {
+// ITER (stv_lbfgsc_iter): also max|fl32(d*t)| of the previous iteration - torch's step-size stop test - from the
+// s = d*t values this sweep forms anyway (a maximum is order-independent: the value is exact).
+template <int U, bool NT, bool PIPE, bool ITER>
+__device__ __forceinline__ void pass_a_body(const float* __restrict__ g, const CState* st, CWs w,
+                                            size_t n, size_t nn, int hist, int nparts, int ntiles, int pgroups) {
   // blockIdx.x = pair group * ntiles + tile.  A small image has too few tiles to keep enough loads in flight
   // (256^2: 192 workgroups walking 100 pairs one after the other ran at 2.3 TB/s), so the PAIRS of a tile are
   // dealt to `pgroups` workgroups; every (pair, tile, wave) partial still has exactly one writer, and the
@@ -131,7 +138,7 @@ __global__ __launch_bounds__(256) void pass_a_kernel(const float* __restrict__ g
   // overshoots (the reference's L-BFGS has no line search: 5.6e8 -> 8.3e29 in tests/golden/mini_clamp_lbfgs),
   // torch's vector recursion survives that (its y.y = inf only makes H_diag 0) and so must this one -
   // an inf here would turn into 0 * inf = NaN in the coefficient recursion.
-  float gmax = 0.f;
+  float gmax = 0.f, dtmax = 0.f;
   double gl1 = 0.0, gg = 0.0, gs = 0.0, gy = 0.0, sy = 0.0, yy = 0.0;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -144,6 +151,7 @@ __global__ __launch_bounds__(256) void pass_a_kernel(const float* __restrict__ g
       yv[u][e] = gv[u][e] - pg[e];
       sv[u][e] = dv[e] * t;
       gmax = fmaxf(gmax, fabsf(gv[u][e]));
+      if constexpr (ITER) dtmax = fmaxf(dtmax, fabsf(sv[u][e]));
     }
     if (pgrp == 0) {
       *reinterpret_cast<f32x4*>(yc + idx) = yv[u];
@@ -251,6 +259,20 @@ __global__ __launch_bounds__(256) void pass_a_kernel(const float* __restrict__ g
     o[0] = (double)gmax; o[(size_t)nparts] = gl1; o[(size_t)2 * nparts] = gg; o[(size_t)3 * nparts] = gs;
     o[(size_t)4 * nparts] = gy; o[(size_t)5 * nparts] = sy; o[(size_t)6 * nparts] = yy;
   }
+  if constexpr (ITER) {
+    dtmax = wave_max(dtmax);
+    if (lane == 0) w.partd[(size_t)SC_DTMAX * nparts + p] = (double)dtmax;
+  }
+}
+template <int U, bool NT = false, bool PIPE = false>
+__global__ __launch_bounds__(256) void pass_a_kernel(const float* __restrict__ g, const CState* st, CWs w,
+                                                     size_t n, size_t nn, int hist, int nparts, int ntiles, int pgroups) {
+  pass_a_body<U, NT, PIPE, false>(g, st, w, n, nn, hist, nparts, ntiles, pgroups);
+}
+template <int U, bool NT = false, bool PIPE = false>
+__global__ __launch_bounds__(256) void pass_a_iter_kernel(const float* __restrict__ g, const CState* st, CWs w,
+                                                          size_t n, size_t nn, int hist, int nparts, int ntiles, int pgroups) {
+  pass_a_body<U, NT, PIPE, true>(g, st, w, n, nn, hist, nparts, ntiles, pgroups);
 }
 
 // ---- fixed-order reduction of the partials: one workgroup per dot product ----------------------
@@ -263,7 +285,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const CState* st, CWs w, in
   if (dot >= 5 * hist + NSCAL) return;
   const double* __restrict__ src = w.part + (size_t)dot * nparts;                       // history products
   const double* __restrict__ srcd = w.partd + (size_t)(scalar ? dot - 5 * hist : 0) * nparts;   // the step's scalars
-  const bool is_max = dot == 5 * hist;
+  const bool is_max = dot == 5 * hist || dot == 5 * hist + SC_DTMAX;
   double acc = 0.0;
   for (int i = threadIdx.x; i < nparts; i += 256) {
     const double v = scalar ? srcd[i] : src[i];
@@ -289,8 +311,17 @@ __device__ unsigned long long g_solve_stamps[8];
 #define SOLVE_STAMP(k) do { } while (0)
 #endif
 
-__global__ __launch_bounds__(256) void solve_kernel(CState* st, CWs w, int hist, float lr, float tol_grad,
-                                                    float tol_change) {
+// ITER (stv_lbfgsc_iter, call k of the `iters` of one optimizer step): torch's `while n_iter < max_iter` loop with
+// the position inside the step and the live/dead flag kept in the state block.  Before any state is touched:
+//   - the rest of the step is already dead                                   -> nothing changes
+//   - max|g| <= tol_grad (k = 1: torch's early return; k > 1: its in-loop test) -> nothing changes, rest dead
+//   - k > 1: max|fl32(d*t)| <= tol_change or |loss - prev_loss| < tol_change    -> nothing changes, rest dead
+// (a call that changes nothing reports skip = 1, which is what pass B honours), and g.d > -tol_change (no_update)
+// makes the rest dead after the state has been saved.  `loss` is the fp32 total of the evaluation that produced g;
+// the difference is formed in double from the two fp32 values, like float() of an fp32 tensor; NaN never stops.
+template <bool ITER>
+__device__ __forceinline__ void solve_body(CState* st, CWs w, int hist, float lr, float tol_grad, float tol_change,
+                                           const float* __restrict__ loss, int iters) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int S = hist + 1;
   // ONE [m][m] double table in logical order holds both products: T[i][j] = s_i.y_j for i < j (the recursion
@@ -299,7 +330,7 @@ __global__ __launch_bounds__(256) void solve_kernel(CState* st, CWs w, int hist,
   // LDS at history 100.  The odd row pitch keeps row walks across lanes and column walks free of bank conflicts.
   const int P = hist | 1;
   double* sT = reinterpret_cast<double*>(smem_raw);
-  __shared__ int sh_skip, sh_pushed, sh_m, sh_head, sh_cslot, sh_mold;
+  __shared__ int sh_skip, sh_pushed, sh_m, sh_head, sh_cslot, sh_mold, sh_pos;
   __shared__ float sh_newro, sh_H;
   __shared__ double sh_gs[MAX_S], sh_gy[MAX_S], sh_ro[MAX_S];
   __shared__ double sh_bp[2][128];       // partial sums of the second walk (indices below / from 64)
@@ -313,15 +344,28 @@ __global__ __launch_bounds__(256) void solve_kernel(CState* st, CWs w, int hist,
   if (tid == 0) {
     // the 64-byte header is read and written once as a block: a chain of dependent global
     // read-modify-writes on its fields costs ~1 us each on an otherwise idle chip
-    struct Hdr { int n_iter, hist_len, head, skip, no_update, pushed, steps_seen, pad0;
-                 float t, H_diag, gtd, gmax, ys, yy, cg, pad1; };
+    struct Hdr { int n_iter, hist_len, head, skip, no_update, pushed, steps_seen, step_pos;
+                 float t, H_diag, gtd, gmax, ys, yy, cg, prev_loss; };
     static_assert(sizeof(Hdr) == 64, "header layout");
     Hdr h = *reinterpret_cast<const Hdr*>(st);
     h.steps_seen += 1;
     h.gmax = (float)gmax;
     h.no_update = 0;
     h.pushed = 0;
-    const int skip = ((float)gmax <= tol_grad) ? 1 : 0;   // opt_cond: leave every piece of state untouched
+    int skip = ((float)gmax <= tol_grad) ? 1 : 0;   // opt_cond: leave every piece of state untouched
+    int pos = 1;
+    float loss_now = 0.f;
+    if constexpr (ITER) {
+      loss_now = *loss;
+      int done = h.step_pos < 0 ? -h.step_pos : h.step_pos;      // calls of this step so far
+      bool dead = h.step_pos < 0;
+      if (done >= iters) { done = 0; dead = false; }              // (a block left by another iters_per_step)
+      pos = done + 1;
+      if (pos > 1 && !skip)
+        skip = ((float)SC[SC_DTMAX] <= tol_change || fabs((double)loss_now - (double)h.prev_loss) < (double)tol_change) ? 1 : 0;
+      if (dead) skip = 1;
+      h.step_pos = pos >= iters ? 0 : (skip ? -pos : pos);
+    }
     h.skip = skip;
     int pushed = 0;
     const int m_old = h.hist_len;
@@ -351,7 +395,9 @@ __global__ __launch_bounds__(256) void solve_kernel(CState* st, CWs w, int hist,
         h.t = lr;
       }
       h.pushed = pushed;
+      if constexpr (ITER) h.prev_loss = loss_now;
     }
+    sh_pos = pos;
     sh_skip = skip; sh_pushed = pushed; sh_m = h.hist_len; sh_head = h.head; sh_cslot = cslot;
     sh_mold = (h.n_iter == 1) ? 0 : m_old;
     sh_H = h.H_diag;
@@ -603,9 +649,20 @@ __global__ __launch_bounds__(256) void solve_kernel(CState* st, CWs w, int hist,
   if (lane == 0) {
     st->cg = (float)cg;
     st->gtd = (float)gtd;
-    st->no_update = ((float)gtd > -tol_change) ? 1 : 0;
+    const int no_update = ((float)gtd > -tol_change) ? 1 : 0;
+    st->no_update = no_update;
+    if constexpr (ITER)
+      if (no_update && sh_pos < iters) st->step_pos = -sh_pos;      // state saved, image not moved: rest of the step dead
   }
   SOLVE_STAMP(7);
+}
+__global__ __launch_bounds__(256) void solve_kernel(CState* st, CWs w, int hist, float lr, float tol_grad,
+                                                    float tol_change) {
+  solve_body<false>(st, w, hist, lr, tol_grad, tol_change, nullptr, 1);
+}
+__global__ __launch_bounds__(256) void solve_iter_kernel(CState* st, CWs w, int hist, float lr, float tol_grad,
+                                                         float tol_change, const float* __restrict__ loss, int iters) {
+  solve_body<true>(st, w, hist, lr, tol_grad, tol_change, loss, iters);
 }
 
 // ---- pass B: form the direction, move x, remember g ------------------------------------------------
@@ -716,12 +773,10 @@ inline StepGeom step_geom(void* workspace, size_t n, int history) {
   g.w = carve(workspace, n, history, g.nparts);
   return g;
 }
-}  // namespace
 
-// First half of a step: sweep A + the fixed-order reduction.  Leaves every inner product of the step
-// (5 per history pair + NSCAL scalars) as doubles in the workspace, at stv_lbfgsc_dots_offset().
-extern "C" int stv_lbfgsc_dots(const float* grad, void* state, void* workspace, size_t n, int history, int m_max,
-                               void* stream) {
+// iter: the kernels of stv_lbfgsc_iter (sweep A also leaves max|d*t|)
+int launch_dots(const float* grad, void* state, void* workspace, size_t n, int history, int m_max, void* stream,
+                bool iter) {
   if (!grad || !state || !workspace || n == 0) return STV_ERR_ARG;
   if (history < 1 || history > MAX_HIST) return STV_ERR_ARG;
   if (m_max < 0) m_max = 0;
@@ -731,34 +786,41 @@ extern "C" int stv_lbfgsc_dots(const float* grad, void* state, void* workspace, 
   const StepGeom g = step_geom(workspace, n, history);
   static const int nt_mask = getenv("STV_LBFGS_NT") ? atoi(getenv("STV_LBFGS_NT")) : 3;
   static const int pipe_a = getenv("STV_LBFGS_PIPE") ? atoi(getenv("STV_LBFGS_PIPE")) : STV_LBFGS_PIPE_DEFAULT;
-#define STV_LAUNCH_PASS_A(U_)                                                                                                      \
+#define STV_LAUNCH_PASS_A_(K_, U_)                                                                                                 \
   do {                                                                                                                             \
-    if ((nt_mask & 1) && pipe_a) hipLaunchKernelGGL((pass_a_kernel<U_, true, true>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups); \
-    else if (nt_mask & 1) hipLaunchKernelGGL((pass_a_kernel<U_, true>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups); \
-    else hipLaunchKernelGGL((pass_a_kernel<U_, false>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups);          \
+    if ((nt_mask & 1) && pipe_a) hipLaunchKernelGGL((K_<U_, true, true>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups); \
+    else if (nt_mask & 1) hipLaunchKernelGGL((K_<U_, true>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups); \
+    else hipLaunchKernelGGL((K_<U_, false>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups);          \
+  } while (0)
+#define STV_LAUNCH_PASS_A(U_)                              \
+  do {                                                     \
+    if (iter) STV_LAUNCH_PASS_A_(pass_a_iter_kernel, U_);  \
+    else STV_LAUNCH_PASS_A_(pass_a_kernel, U_);            \
   } while (0)
   if (g.tile == 4096) STV_LAUNCH_PASS_A(4);
   else if (g.tile == 2048) STV_LAUNCH_PASS_A(2);
   else STV_LAUNCH_PASS_A(1);
 #undef STV_LAUNCH_PASS_A
+#undef STV_LAUNCH_PASS_A_
   hipLaunchKernelGGL(reduce_kernel, dim3(5 * m_max + NSCAL), dim3(256), 0, st, s, g.w, history, g.nparts);
   STV_CHECK_LAUNCH();
   return STV_OK;
 }
 
-// Second half: torch's control flow + the recursion on coefficients (from the inner products), then
-// sweep B: d, x += t*d, prev_g = g.
-extern "C" int stv_lbfgsc_apply(float* x, const float* grad, void* state, void* workspace, size_t n, int history,
-                                float lr, float tol_grad, float tol_change, void* stream) {
+// loss != NULL: the solve kernel of stv_lbfgsc_iter (call k of `iters` per optimizer step)
+int launch_apply(float* x, const float* grad, const float* loss, void* state, void* workspace, size_t n, int history,
+                 int iters, float lr, float tol_grad, float tol_change, void* stream) {
   if (!x || !grad || !state || !workspace || n == 0) return STV_ERR_ARG;
   if (history < 1 || history > MAX_HIST) return STV_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   CState* s = static_cast<CState*>(state);
   const StepGeom g = step_geom(workspace, n, history);
   const size_t lds = (size_t)history * (size_t)(history | 1) * sizeof(double);
-  if (stv_set_max_lds(reinterpret_cast<const void*>(&solve_kernel), MAX_HIST * (MAX_HIST | 1) * (int)sizeof(double)) != STV_OK)
+  const void* solve_fn = loss ? reinterpret_cast<const void*>(&solve_iter_kernel) : reinterpret_cast<const void*>(&solve_kernel);
+  if (stv_set_max_lds(solve_fn, MAX_HIST * (MAX_HIST | 1) * (int)sizeof(double)) != STV_OK)
     return STV_ERR_LAUNCH;
-  hipLaunchKernelGGL(solve_kernel, dim3(1), dim3(256), lds, st, s, g.w, history, lr, tol_grad, tol_change);
+  if (loss) hipLaunchKernelGGL(solve_iter_kernel, dim3(1), dim3(256), lds, st, s, g.w, history, lr, tol_grad, tol_change, loss, iters);
+  else hipLaunchKernelGGL(solve_kernel, dim3(1), dim3(256), lds, st, s, g.w, history, lr, tol_grad, tol_change);
   // A/B aid: STV_LBFGS_ACC=f32 restores the fp32 accumulation of the direction (less accurate, see pass_b_kernel)
   static const bool acc64 = !(getenv("STV_LBFGS_ACC") && strcmp(getenv("STV_LBFGS_ACC"), "f32") == 0);
   const int tile_b = tile_floats_b(n);
@@ -777,6 +839,21 @@ extern "C" int stv_lbfgsc_apply(float* x, const float* grad, void* state, void* 
   STV_CHECK_LAUNCH();
   return STV_OK;
 }
+}  // namespace
+
+// First half of a step: sweep A + the fixed-order reduction.  Leaves every inner product of the step
+// (5 per history pair + NSCAL scalars) as doubles in the workspace, at stv_lbfgsc_dots_offset().
+extern "C" int stv_lbfgsc_dots(const float* grad, void* state, void* workspace, size_t n, int history, int m_max,
+                               void* stream) {
+  return launch_dots(grad, state, workspace, n, history, m_max, stream, false);
+}
+
+// Second half: torch's control flow + the recursion on coefficients (from the inner products), then
+// sweep B: d, x += t*d, prev_g = g.
+extern "C" int stv_lbfgsc_apply(float* x, const float* grad, void* state, void* workspace, size_t n, int history,
+                                float lr, float tol_grad, float tol_change, void* stream) {
+  return launch_apply(x, grad, nullptr, state, workspace, n, history, 1, lr, tol_grad, tol_change, stream);
+}
 
 // Where the inner products live: byte offset into the workspace of `count` doubles; entry `max_index`
 // is max|g| (combine across shards with MAX), every other entry is a sum (combine with SUM).
@@ -794,6 +871,26 @@ extern "C" int stv_lbfgsc_step(float* x, const float* grad, void* state, void* w
   const int rc = stv_lbfgsc_dots(grad, state, workspace, n, history, m_max, stream);
   if (rc != STV_OK) return rc;
   return stv_lbfgsc_apply(x, grad, state, workspace, n, history, lr, tol_grad, tol_change, stream);
+}
+
+// One iteration of an optimizer step of `iters_per_step` iterations (torch.optim.LBFGS with max_iter > 1, no line
+// search): the same four launches as stv_lbfgsc_step; which call of the step this is, and whether a data-dependent
+// exit has already ended the step, is device state (solve_body), so one captured program serves every call.
+extern "C" int stv_lbfgsc_iter(float* x, const float* grad, const float* loss, void* state, void* workspace, size_t n,
+                               int history, int m_max, int iters_per_step, float lr, float tol_grad, float tol_change,
+                               void* stream) {
+  if (!x || !loss || iters_per_step < 1 || iters_per_step > 32767) return STV_ERR_ARG;
+  const int rc = launch_dots(grad, state, workspace, n, history, m_max, stream, true);
+  if (rc != STV_OK) return rc;
+  return launch_apply(x, grad, loss, state, workspace, n, history, iters_per_step, lr, tol_grad, tol_change, stream);
+}
+
+// A step abandoned midway (the closure raised): the next stv_lbfgsc_iter is call 1 of a new step.  Enqueued, no sync.
+extern "C" int stv_lbfgsc_iter_reset(void* state, void* stream) {
+  if (!state) return STV_ERR_ARG;
+  if (hipMemsetAsync(static_cast<char*>(state) + offsetof(CState, step_pos), 0, sizeof(int), static_cast<hipStream_t>(stream)) != hipSuccess)
+    return STV_ERR_LAUNCH;
+  return STV_OK;
 }
 
 #ifdef STV_SOLVE_STAMPS

@@ -90,6 +90,9 @@ int run_op(const stv_op_t& op, void* st) {
     case STV_OP_LBFGS_STEP:
       return stv_lbfgsc_step(static_cast<float*>(o.q0), static_cast<const float*>(o.p0), o.q1, o.q2, (size_t)o.n, o.cin, o.cout,
                              o.f0, o.f1, o.f2, st);
+    case STV_OP_LBFGS_ITER:   // p1 = loss (device fp32 scalar), taps = iterations per optimizer step
+      return stv_lbfgsc_iter(static_cast<float*>(o.q0), static_cast<const float*>(o.p0), static_cast<const float*>(o.p1), o.q1, o.q2,
+                             (size_t)o.n, o.cin, o.cout, o.taps, o.f0, o.f1, o.f2, st);
     case STV_OP_MEMSET:
       if (hipMemsetAsync(o.q0, 0, (size_t)o.n, static_cast<hipStream_t>(st)) != hipSuccess)
         return STV_ERR_LAUNCH;
@@ -181,7 +184,7 @@ int run_all(stv_program* p, void* st, bool lanes) {
 
 }  // namespace
 
-extern "C" int stv_version(void) { return 102; }
+extern "C" int stv_version(void) { return 103; }
 
 extern "C" int stv_program_create(const stv_op_t* ops, int n_ops, stv_program** out) {
   if (!ops || n_ops <= 0 || !out) return STV_ERR_ARG;

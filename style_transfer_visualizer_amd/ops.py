@@ -503,6 +503,24 @@ def lbfgs_step(x: torch.Tensor, grad: torch.Tensor, state: torch.Tensor, work: t
                   tol_grad, tol_change, _stream()), "stv_lbfgsc_step" if compact else "stv_lbfgs_step")
 
 
+def lbfgs_iter(x: torch.Tensor, grad: torch.Tensor, loss: torch.Tensor, state: torch.Tensor, work: torch.Tensor,
+               history: int, m_max: int, iters_per_step: int, lr: float, tol_grad: float = 1e-7,
+               tol_change: float = 1e-9) -> None:
+    """One iteration of a compact L-BFGS step of ``iters_per_step`` iterations (stv_lbfgsc_iter); ``loss`` is a
+    one-element float32 tensor on the device: the total of the evaluation that produced ``grad``."""
+    if not loss.is_cuda or loss.dtype != torch.float32 or loss.numel() != 1:
+        msg = "lbfgs_iter needs the loss as a one-element float32 GPU tensor"
+        raise RuntimeError(msg)
+    lib = _lib.load()
+    _lib.check(lib.stv_lbfgsc_iter(_ptr(x), _ptr(grad), _ptr(loss), _ptr(state), _ptr(work), x.numel(), history, m_max,
+                                   iters_per_step, lr, tol_grad, tol_change, _stream()), "stv_lbfgsc_iter")
+
+
+def lbfgs_iter_reset(state: torch.Tensor) -> None:
+    """The current step was abandoned midway: the next ``lbfgs_iter`` is call 1 of a new step (an enqueue)."""
+    _lib.check(_lib.load().stv_lbfgsc_iter_reset(_ptr(state), _stream()), "stv_lbfgsc_iter_reset")
+
+
 def lbfgs_dots(grad: torch.Tensor, state: torch.Tensor, work: torch.Tensor, history: int, m_max: int) -> torch.Tensor:
     """First half of a compact L-BFGS step (stv_lbfgsc_dots): this shard's partial inner products.
     Returns a float64 VIEW into ``work`` (5*128 + 8 entries) for the caller to all-reduce."""

@@ -8,7 +8,7 @@ error texts).  Differences, all on the device side:
 * when the model offers ``loss_and_grad`` (the HIP ``StyleContentModel``), a
   step is one fused command-buffer launch that leaves ``input_img.grad``
   populated - no autograd graph, no tiny reduction kernels;
-* the default optimizer for a GPU image is the device-resident ``HipLBFGS``;
+* the optimizer for a GPU image is the device-resident ``HipLBFGS``, for ``lbfgs_max_iter > 1`` too;
 * finite-ness of the losses is checked for EVERY step, like the reference does
   (optimization.py:375-391), but at the ``log_every`` cadence: each flush copies the
   scores of all steps since the previous flush out of the device ring in one
@@ -150,8 +150,11 @@ class OptimizationRunner:
         self._live_scores: bool | None = None
         self._model_kwargs: frozenset[str] = frozenset()
         # optimizers that evaluate the closure exactly once per step: the model may then keep the loss history
-        # itself (one ring slot per evaluation, written by the kernel that combines the scores)
-        self._single_eval = isinstance(self.optimizer, (HipLBFGS, HipAdam))
+        # itself (one ring slot per evaluation, written by the kernel that combines the scores).  HipLBFGS with
+        # max_iter > 1 evaluates several times per step: its records arrive through accumulate(), one per accepted
+        # step with the last evaluation's scores, like any multi-closure optimizer's.
+        self._single_eval = isinstance(self.optimizer, HipAdam) or (
+            isinstance(self.optimizer, HipLBFGS) and self.optimizer.evals_per_step == 1)
         self._producer_logged = False
 
     # ------------------------------------------------------------------ properties
