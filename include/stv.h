@@ -369,12 +369,6 @@ enum {
   STV_OP_GRAM_FINISH, STV_OP_CONTENT_LOSS, STV_OP_CONTENT_GRAD, STV_OP_LOSS_COMBINE,
   STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER
 };
-/* Scheduling hints in stv_op_t.flags (masked off before the kernel sees them):
- * an op with STV_LANE_SIDE may run concurrently with the ops after it: it reads only
- * what earlier ops produced, and what it writes is first read by an op flagged
- * STV_LANE_JOIN (or after the program).  The executor runs such ops on a second
- * stream forked from / joined to the caller's stream with events. */
-enum { STV_LANE_SIDE = 1 << 29, STV_LANE_JOIN = 1 << 30 };
 /* Operands follow the direct entry points' argument order (inputs p0.., outputs q0..).
  * CONV_FIRST_FWD takes the optional stv_conv_first_pack buffer in p3 (and, with q1 set, runs
  * stv_conv_first_fwd_gram with q1 = gram_partials), CONV_FIRST_DGRAD in p2;
@@ -398,6 +392,8 @@ typedef struct {
   const void* p0; const void* p1; const void* p2; const void* p3;
   void* q0; void* q1; void* q2; void* q3;
 } stv_op_t;
+/* Since version 104, stv_op_t.flags holds kernel flags only (the scheduling hints of earlier versions are gone):
+ * the ops of a program run in program order on the caller's stream, so a captured step is a chain of graph nodes. */
 
 typedef struct stv_program stv_program;  /* host object */
 int stv_program_create(const stv_op_t* ops, int n_ops, stv_program** out);

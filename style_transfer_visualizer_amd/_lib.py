@@ -15,7 +15,6 @@ LIB_PATH = os.environ.get("STV_LIB_PATH") or os.path.join(_HERE, "libstv_hip.so"
 STV_F32, STV_BF16, STV_BF16X3 = 0, 1, 2     # STV_BF16X3: fp32 storage, split-bf16 products
 TUNE_BF16X3 = 6     # stv.h STV_TUNE_BF16X3: the `elem_bytes` key of a bf16x3 tile-table entry
 RELU_IN, RELU_OUT, MASK, ACCUM, W_BLOCKED, POOL_IDX, POOL_ROUTE, POOL_ONLY = 1, 2, 4, 8, 16, 32, 64, 128
-LANE_SIDE, LANE_JOIN = 1 << 29, 1 << 30          # scheduling hints of the command-buffer executor
 
 (OP_CONV_FIRST_FWD, OP_CONV_FIRST_DGRAD, OP_CONV, OP_POOL_FWD, OP_POOL_BWD, OP_RELU_FWD,
  OP_RELU_BWD, OP_GRAM_PARTIAL, OP_GRAM_FINISH, OP_CONTENT_LOSS, OP_CONTENT_GRAD,

@@ -348,10 +348,7 @@ class _Engine:
     def _tap_loss_ops(self, tap, *, style_coef: float, coef_dev: torch.Tensor | None, with_seed: bool,
                       content_coef: float | None = None) -> list:
         """Loss-side ops of one tap.  They are spliced in right after the op that produces the tapped
-        activation, while it is still L2 / Infinity-Cache resident.  STV_SIDE_LANE=1 flags them for
-        the executor's second stream (fork after the tapped conv, join at the score combine); measured
-        twice on MI355X, it loses 2-5 % inside the captured graph (6 forks + 1 join cost more than the
-        ~100 us of overlap they buy), so it stays off by default."""
+        activation, while it is still L2 / Infinity-Cache resident."""
         s = self.sched
         if tap.kind == "style":
             cd = coef_dev[tap.order:] if coef_dev is not None else None
@@ -364,11 +361,6 @@ class _Engine:
         else:
             ops_ = [s._op(op=plan.OP_CONTENT_LOSS, p0=tap.buf.act, p1=tap.target,
                           q0=self.parts[tap.parts_off:], n=tap.buf.act.numel())]
-        if os.environ.get("STV_SIDE_LANE", "0") == "1":
-            # loss-side chains only read the tapped activation and write buffers that nothing reads
-            # before the score combine: they may overlap the main chain (executor's second stream)
-            for o in ops_:
-                o.flags |= _lib.LANE_SIDE
         return ops_
 
     def _content_fused(self, tap) -> bool:
@@ -448,11 +440,9 @@ class _Engine:
         """``score_log`` = (ring fp32 [3, capacity], device counter int32 [1][, host-visible record count int32 [1]]):
         the combine kernel also appends the three scores to the caller's history ring (stv_loss_combine_log)."""
         ring, count, seq = (tuple(score_log) + (None,))[:3] if score_log is not None else (None, None, None)
-        op = self.sched._op(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=self.table, p2=self.scale, p3=seq,
-                            q0=self.losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
-                            cin=self.n_style + self.n_content, f0=style_w, f1=content_w)
-        op.flags |= _lib.LANE_JOIN          # first reader of what the loss-side ops wrote
-        return op
+        return self.sched._op(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=self.table, p2=self.scale, p3=seq,
+                              q0=self.losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
+                              cin=self.n_style + self.n_content, f0=style_w, f1=content_w)
 
     def _program(self, key: tuple, builder) -> plan.Program:
         prog = self._programs.get(key)
@@ -593,7 +583,6 @@ class _Engine:
                     # several iterations per optimizer step: the same program replays for each of them (position and
                     # stop flag are device state); the step's loss test reads the total the combine op wrote
                     op.op, op.taps, op.p1 = _lib.OP_LBFGS_ITER, then_step.iters_per_step, self.scores[2:].data_ptr()
-                op.flags |= _lib.LANE_JOIN
                 tail.append(op)
             return (self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w)
                     + [self._combine_op(style_w, content_w, score_log)]

@@ -697,7 +697,6 @@ extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype,
     if (x3 && t.F && (size_t)t.n_pixels * t.channels * 4 >= ((size_t)1 << 31)) return STV_ERR_ARG;
   }
   // partial sums: one launch per tile size present (bf16 with both sizes present: one launch for both)
-  static const bool merge_sizes = !(getenv("STV_GRAM_MERGE") && atoi(getenv("STV_GRAM_MERGE")) == 0);   // A/B aid
   PartialMulti held{};                       // the 64-wide taps, waiting for the 128-wide ones
   for (int TS : {64, 128}) {
     PartialMulti m{};
@@ -714,7 +713,7 @@ extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype,
       m.ksplit[k] = ksplit; m.chunk[k] = chunk; m.pairs[k] = pairs;
       m.block0[k + 1] = m.block0[k] + pairs * ksplit;
     }
-    if (dtype == STV_BF16 && merge_sizes && TS == 64 && m.n) {
+    if (dtype == STV_BF16 && TS == 64 && m.n) {
       bool wide = false;
       for (int i = 0; i < n_taps; ++i) wide |= gram_tile(taps[i].channels) == 128 && taps[i].F != nullptr;
       if (wide) { held = m; continue; }
@@ -760,36 +759,23 @@ extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype,
 #undef STV_SET_LDS
     STV_CHECK_LAUNCH();
   }
-  // finish: one launch (8 slices per element); with STV_GRAM_FIN_MERGE=0 taps with hundreds of slabs get a launch
-  // of their own that walks them with 32 slices per element (1024-thread blocks)
-  for (int deep = 0; deep < 2; ++deep) {
-    FinishMulti f{};
-    for (int i = 0; i < n_taps; ++i) {
-      const stv_gram_tap_t& t = taps[i];
-      const int ksplit = stv_gram_ksplit(t.n_pixels, t.channels);
-      // (one launch for all taps measured faster than a second, 1024-thread launch for the many-slab tap:
-      // 14 + 8 us -> ~15 us at 512^2; STV_GRAM_FIN_MERGE=0 restores the two classes)
-      static const bool one_finish = !(getenv("STV_GRAM_FIN_MERGE") && atoi(getenv("STV_GRAM_FIN_MERGE")) == 0);
-      if (((ksplit >= 128 && !one_finish) ? 1 : 0) != deep) continue;
-      const int k = f.n++;
-      f.partials[k] = t.partials; f.target[k] = t.target; f.gram_out[k] = t.gram_out; f.loss_part[k] = t.loss_part;
-      f.sgrad[k] = t.sgrad; f.coef_dev[k] = t.coef_dev; f.C[k] = t.channels; f.TS[k] = gram_tile(t.channels);
-      f.ksplit[k] = ksplit;
-      f.clamp_max[k] = t.clamp_max; f.norm[k] = t.norm;
-      f.k_grad[k] = t.coef * 4.0f / ((float)t.channels * (float)t.channels * t.norm);
-      f.block0[k + 1] = f.block0[k] + stv_gram_loss_parts(t.channels);
-    }
-    if (!f.n) continue;
-    const dim3 grid(f.block0[f.n]);
-    if (dtype != STV_BF16) {
-      if (deep) hipLaunchKernelGGL((gram_finish_multi_kernel<float, 32>), grid, dim3(FIN_L * 32), 0, st, f);
-      else hipLaunchKernelGGL((gram_finish_multi_kernel<float, 8>), grid, dim3(FIN_L * 8), 0, st, f);
-    } else {
-      if (deep) hipLaunchKernelGGL((gram_finish_multi_kernel<bf16_t, 32>), grid, dim3(FIN_L * 32), 0, st, f);
-      else hipLaunchKernelGGL((gram_finish_multi_kernel<bf16_t, 8>), grid, dim3(FIN_L * 8), 0, st, f);
-    }
-    STV_CHECK_LAUNCH();
+  // finish: one launch for all taps, 8 slices per element (it measured faster than a second, 1024-thread launch with
+  // 32 slices per element for the many-slab tap: 14 + 8 us -> ~15 us at 512^2)
+  FinishMulti f{};
+  for (int i = 0; i < n_taps; ++i) {
+    const stv_gram_tap_t& t = taps[i];
+    const int k = f.n++;
+    f.partials[k] = t.partials; f.target[k] = t.target; f.gram_out[k] = t.gram_out; f.loss_part[k] = t.loss_part;
+    f.sgrad[k] = t.sgrad; f.coef_dev[k] = t.coef_dev; f.C[k] = t.channels; f.TS[k] = gram_tile(t.channels);
+    f.ksplit[k] = stv_gram_ksplit(t.n_pixels, t.channels);
+    f.clamp_max[k] = t.clamp_max; f.norm[k] = t.norm;
+    f.k_grad[k] = t.coef * 4.0f / ((float)t.channels * (float)t.channels * t.norm);
+    f.block0[k + 1] = f.block0[k] + stv_gram_loss_parts(t.channels);
   }
+  const dim3 grid(f.block0[f.n]);
+  if (dtype != STV_BF16) hipLaunchKernelGGL((gram_finish_multi_kernel<float, 8>), grid, dim3(FIN_L * 8), 0, st, f);
+  else hipLaunchKernelGGL((gram_finish_multi_kernel<bf16_t, 8>), grid, dim3(FIN_L * 8), 0, st, f);
+  STV_CHECK_LAUNCH();
   return STV_OK;
 }
 

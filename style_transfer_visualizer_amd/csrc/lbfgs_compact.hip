@@ -19,15 +19,10 @@
 // HBM traffic per step: (4m + 8) vectors instead of ~(8m) with 2m+4 launches.
 #include <stddef.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <type_traits>
 
 #include "stv_common.h"
-
-#ifndef STV_LBFGS_PIPE_DEFAULT
-#define STV_LBFGS_PIPE_DEFAULT 0      // sweep A with the next pair's loads in flight (STV_LBFGS_PIPE=1); set from the measurement
-#endif
 
 namespace {
 
@@ -99,15 +94,12 @@ __device__ __forceinline__ f32x4 ld4_guard(const float* __restrict__ p, size_t i
   if (idx + 2 < n) v[2] = p[idx + 2];
   return v;
 }
-// History loads: NT = non-temporal (`global_load ... nt`).  The 2m history vectors are streamed once per sweep and not
+// History loads are non-temporal (`global_load ... nt`).  The 2m history vectors are streamed once per sweep and not
 // touched again before the next closure has turned every cache over; loading them non-temporally in BOTH sweeps measured
 // -2.0 % step time at 512^2 (0.907 -> 0.888 ms, two alternating runs each on one box), within noise at 1024^2 (2.643 ->
 // 2.627); either sweep alone: nothing (A) / -1 % (B).  Same values, same order: bit-identical results.
-// STV_LBFGS_NT: bit 0 = sweep A, bit 1 = sweep B (default 3).
-template <bool NT>
 __device__ __forceinline__ f32x4 ldh4(const float* __restrict__ p) {
-  if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-  else return *reinterpret_cast<const f32x4*>(p);
+  return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
 }
 typedef float pk2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b) {
@@ -117,7 +109,7 @@ __device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b) {
 // ---- pass A ---------------------------------------------------------------------------------
 // ITER (stv_lbfgsc_iter): also max|fl32(d*t)| of the previous iteration - torch's step-size stop test - from the
 // s = d*t values this sweep forms anyway (a maximum is order-independent: the value is exact).
-template <int U, bool NT, bool PIPE, bool ITER>
+template <int U, bool ITER>
 __device__ __forceinline__ void pass_a_body(const float* __restrict__ g, const CState* st, CWs w,
                                             size_t n, size_t nn, int hist, int nparts, int ntiles, int pgroups) {
   // blockIdx.x = pair group * ntiles + tile.  A small image has too few tiles to keep enough loads in flight
@@ -177,78 +169,31 @@ __device__ __forceinline__ void pass_a_body(const float* __restrict__ g, const C
   // (the fourth product of a pair, y_j . s_c, fills the table entry s_c . y_j of a NEWER s with an OLDER y - an entry the
   //  recursion never reads (solve_kernel: only s_i . y_j with i older than j) - so it is not computed: its slot in the
   //  5-per-pair layout stays, as a zero)
-  // PIPE: the next pair's loads are in flight while this pair is multiplied (two register sets; affordable since the
-  // unused product went: 160 registers = the three waves per SIMD the grid gives anyway).
-  auto load_pair = [&](int jj, f32x4 (&s4)[U], f32x4 (&y4)[U]) {
+  for (int jj = pgrp * per; jj < j_end; ++jj) {
     const int slot = (head + jj) % S;
     const float* __restrict__ sj = w.S + (size_t)slot * nn;
     const float* __restrict__ yj = w.Y + (size_t)slot * nn;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a4 = 0.0;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const size_t idx = base + (size_t)(u * 256 + tid) * 4;
-      s4[u] = ldh4<NT>(sj + idx);
-      y4[u] = ldh4<NT>(yj + idx);
-    }
-  };
-  auto dot_pair = [&](int jj, const f32x4 (&s4)[U], const f32x4 (&y4)[U]) {
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a4 = 0.0;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
+      const f32x4 s4 = ldh4(sj + idx);
+      const f32x4 y4 = ldh4(yj + idx);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const double sd = (double)s4[u][e], yd = (double)y4[u][e];
+        const double sd = (double)s4[e], yd = (double)y4[e];
         const double gd = (double)gv[u][e], cd = (double)yv[u][e];
         a0 = fma(sd, gd, a0);   // s_j . g
         a1 = fma(yd, gd, a1);   // y_j . g
         a2 = fma(sd, cd, a2);   // s_j . y_c
         a4 = fma(yd, cd, a4);   // y_j . y_c
       }
+    }
     a0 = wave_sum_d_dpp(a0); a1 = wave_sum_d_dpp(a1); a2 = wave_sum_d_dpp(a2); a4 = wave_sum_d_dpp(a4);
     if (lane == 0) {
       double* o = w.part + (size_t)(jj * 5) * nparts + p;
       o[0] = a0; o[(size_t)nparts] = a1; o[(size_t)2 * nparts] = a2; o[(size_t)3 * nparts] = 0.0;
       o[(size_t)4 * nparts] = a4;
-    }
-  };
-  if constexpr (PIPE) {
-    f32x4 sA[U], yA[U], sB[U], yB[U];
-    int jj = pgrp * per;
-    if (jj < j_end) load_pair(jj, sA, yA);
-    for (; jj < j_end; jj += 2) {
-      if (jj + 1 < j_end) load_pair(jj + 1, sB, yB);
-      dot_pair(jj, sA, yA);
-      if (jj + 1 < j_end) {
-        if (jj + 2 < j_end) load_pair(jj + 2, sA, yA);
-        dot_pair(jj + 1, sB, yB);
-      }
-    }
-  } else {
-    for (int jj = pgrp * per; jj < j_end; ++jj) {
-      const int slot = (head + jj) % S;
-      const float* __restrict__ sj = w.S + (size_t)slot * nn;
-      const float* __restrict__ yj = w.Y + (size_t)slot * nn;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a4 = 0.0;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const size_t idx = base + (size_t)(u * 256 + tid) * 4;
-        const f32x4 s4 = ldh4<NT>(sj + idx);
-        const f32x4 y4 = ldh4<NT>(yj + idx);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const double sd = (double)s4[e], yd = (double)y4[e];
-          const double gd = (double)gv[u][e], cd = (double)yv[u][e];
-          a0 = fma(sd, gd, a0);   // s_j . g
-          a1 = fma(yd, gd, a1);   // y_j . g
-          a2 = fma(sd, cd, a2);   // s_j . y_c
-          a4 = fma(yd, cd, a4);   // y_j . y_c
-        }
-      }
-      a0 = wave_sum_d_dpp(a0); a1 = wave_sum_d_dpp(a1); a2 = wave_sum_d_dpp(a2); a4 = wave_sum_d_dpp(a4);
-      if (lane == 0) {
-        double* o = w.part + (size_t)(jj * 5) * nparts + p;
-        o[0] = a0; o[(size_t)nparts] = a1; o[(size_t)2 * nparts] = a2; o[(size_t)3 * nparts] = 0.0;
-        o[(size_t)4 * nparts] = a4;
-      }
     }
   }
   if (pgrp != 0) return;
@@ -264,15 +209,15 @@ __device__ __forceinline__ void pass_a_body(const float* __restrict__ g, const C
     if (lane == 0) w.partd[(size_t)SC_DTMAX * nparts + p] = (double)dtmax;
   }
 }
-template <int U, bool NT = false, bool PIPE = false>
+template <int U>
 __global__ __launch_bounds__(256) void pass_a_kernel(const float* __restrict__ g, const CState* st, CWs w,
                                                      size_t n, size_t nn, int hist, int nparts, int ntiles, int pgroups) {
-  pass_a_body<U, NT, PIPE, false>(g, st, w, n, nn, hist, nparts, ntiles, pgroups);
+  pass_a_body<U, false>(g, st, w, n, nn, hist, nparts, ntiles, pgroups);
 }
-template <int U, bool NT = false, bool PIPE = false>
+template <int U>
 __global__ __launch_bounds__(256) void pass_a_iter_kernel(const float* __restrict__ g, const CState* st, CWs w,
                                                           size_t n, size_t nn, int hist, int nparts, int ntiles, int pgroups) {
-  pass_a_body<U, NT, PIPE, true>(g, st, w, n, nn, hist, nparts, ntiles, pgroups);
+  pass_a_body<U, true>(g, st, w, n, nn, hist, nparts, ntiles, pgroups);
 }
 
 // ---- fixed-order reduction of the partials: one workgroup per dot product ----------------------
@@ -671,9 +616,9 @@ __global__ __launch_bounds__(256) void solve_iter_kernel(CState* st, CWs w, int 
 // the history is walked).  Accumulated in fp32 the direction was 7-10x further from the float64 update than
 // torch's fp32 vector recursion once m > 60 (tests/test_gpu_lbfgs_long.py; CPU emulation of this algorithm:
 // fp64 inner products change nothing, fp64 accumulation HERE brings it to the reference's own level), so the
-// accumulators are double (ACC64): every product of two floats is exact in double, the sum is rounded to
+// accumulators are double: every product of two floats is exact in double, the sum is rounded to
 // fp32 once.  The sweep stays bandwidth-bound: 2 conversions + 2 DP FMAs per element and pair beside 8 bytes.
-template <int U, bool ACC64, bool NT = false>
+template <int U>
 __global__ __launch_bounds__(256) void pass_b_kernel(float* __restrict__ x, const float* __restrict__ g,
                                                      const CState* st, CWs w, size_t n, size_t nn, int hist) {
   if (st->skip) return;
@@ -683,33 +628,29 @@ __global__ __launch_bounds__(256) void pass_b_kernel(float* __restrict__ x, cons
   const int m = st->hist_len, head = st->head;
   const float cg = st->cg, t = st->t;
   const bool move = st->no_update == 0;
-  using acc_t = typename std::conditional<ACC64, double, float>::type;
-  acc_t acc[U][4];
+  double acc[U][4];
   f32x4 gv[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const size_t idx = base + (size_t)(u * 256 + tid) * 4;
     gv[u] = ld4_guard(g, idx, n);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[u][e] = (acc_t)cg * (acc_t)gv[u][e];
+    for (int e = 0; e < 4; ++e) acc[u][e] = (double)cg * (double)gv[u][e];
   }
   // newest pair first: pass A walked the history oldest-to-newest just before, so its tail is what
   // the Infinity Cache still holds
   for (int jj = m - 1; jj >= 0; --jj) {
     const int slot = (head + jj) % S;
-    const acc_t cs = (acc_t)st->cs[slot], cy = (acc_t)st->cy[slot];
+    const double cs = (double)st->cs[slot], cy = (double)st->cy[slot];
     const float* __restrict__ sj = w.S + (size_t)slot * nn;
     const float* __restrict__ yj = w.Y + (size_t)slot * nn;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const size_t idx = base + (size_t)(u * 256 + tid) * 4;
-      const f32x4 s4 = ldh4<NT>(sj + idx);
-      const f32x4 y4 = ldh4<NT>(yj + idx);
+      const f32x4 s4 = ldh4(sj + idx);
+      const f32x4 y4 = ldh4(yj + idx);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if constexpr (ACC64) acc[u][e] = fma(cs, (double)s4[e], fma(cy, (double)y4[e], acc[u][e]));
-        else acc[u][e] = fmaf(cs, s4[e], fmaf(cy, y4[e], acc[u][e]));
-      }
+      for (int e = 0; e < 4; ++e) acc[u][e] = fma(cs, (double)s4[e], fma(cy, (double)y4[e], acc[u][e]));
     }
   }
 #pragma unroll
@@ -774,6 +715,10 @@ inline StepGeom step_geom(void* workspace, size_t n, int history) {
   return g;
 }
 
+// a sweep's kernel for tiles of 1024 / 2048 / 4096 floats (K<1>, K<2>, K<4>)
+template <typename K>
+inline K by_tile(int tile, K k1, K k2, K k4) { return tile == 4096 ? k4 : tile == 2048 ? k2 : k1; }
+
 // iter: the kernels of stv_lbfgsc_iter (sweep A also leaves max|d*t|)
 int launch_dots(const float* grad, void* state, void* workspace, size_t n, int history, int m_max, void* stream,
                 bool iter) {
@@ -784,24 +729,10 @@ int launch_dots(const float* grad, void* state, void* workspace, size_t n, int h
   hipStream_t st = static_cast<hipStream_t>(stream);
   CState* s = static_cast<CState*>(state);
   const StepGeom g = step_geom(workspace, n, history);
-  static const int nt_mask = getenv("STV_LBFGS_NT") ? atoi(getenv("STV_LBFGS_NT")) : 3;
-  static const int pipe_a = getenv("STV_LBFGS_PIPE") ? atoi(getenv("STV_LBFGS_PIPE")) : STV_LBFGS_PIPE_DEFAULT;
-#define STV_LAUNCH_PASS_A_(K_, U_)                                                                                                 \
-  do {                                                                                                                             \
-    if ((nt_mask & 1) && pipe_a) hipLaunchKernelGGL((K_<U_, true, true>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups); \
-    else if (nt_mask & 1) hipLaunchKernelGGL((K_<U_, true>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups); \
-    else hipLaunchKernelGGL((K_<U_, false>), dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles, g.pgroups);          \
-  } while (0)
-#define STV_LAUNCH_PASS_A(U_)                              \
-  do {                                                     \
-    if (iter) STV_LAUNCH_PASS_A_(pass_a_iter_kernel, U_);  \
-    else STV_LAUNCH_PASS_A_(pass_a_kernel, U_);            \
-  } while (0)
-  if (g.tile == 4096) STV_LAUNCH_PASS_A(4);
-  else if (g.tile == 2048) STV_LAUNCH_PASS_A(2);
-  else STV_LAUNCH_PASS_A(1);
-#undef STV_LAUNCH_PASS_A
-#undef STV_LAUNCH_PASS_A_
+  const auto sweep_a = iter ? by_tile(g.tile, pass_a_iter_kernel<1>, pass_a_iter_kernel<2>, pass_a_iter_kernel<4>)
+                            : by_tile(g.tile, pass_a_kernel<1>, pass_a_kernel<2>, pass_a_kernel<4>);
+  hipLaunchKernelGGL(sweep_a, dim3(g.ntiles * g.pgroups), dim3(256), 0, st, grad, s, g.w, n, g.nn, history, g.nparts, g.ntiles,
+                     g.pgroups);
   hipLaunchKernelGGL(reduce_kernel, dim3(5 * m_max + NSCAL), dim3(256), 0, st, s, g.w, history, g.nparts);
   STV_CHECK_LAUNCH();
   return STV_OK;
@@ -821,21 +752,9 @@ int launch_apply(float* x, const float* grad, const float* loss, void* state, vo
     return STV_ERR_LAUNCH;
   if (loss) hipLaunchKernelGGL(solve_iter_kernel, dim3(1), dim3(256), lds, st, s, g.w, history, lr, tol_grad, tol_change, loss, iters);
   else hipLaunchKernelGGL(solve_kernel, dim3(1), dim3(256), lds, st, s, g.w, history, lr, tol_grad, tol_change);
-  // A/B aid: STV_LBFGS_ACC=f32 restores the fp32 accumulation of the direction (less accurate, see pass_b_kernel)
-  static const bool acc64 = !(getenv("STV_LBFGS_ACC") && strcmp(getenv("STV_LBFGS_ACC"), "f32") == 0);
   const int tile_b = tile_floats_b(n);
-  const int ntiles_b = (int)(g.nn / tile_b);
-  static const int nt_mask_b = getenv("STV_LBFGS_NT") ? atoi(getenv("STV_LBFGS_NT")) : 3;
-#define STV_LAUNCH_PASS_B(U_)                                                                                              \
-  do {                                                                                                                     \
-    if (acc64 && (nt_mask_b & 2)) hipLaunchKernelGGL((pass_b_kernel<U_, true, true>), dim3(ntiles_b), dim3(256), 0, st, x, grad, s, g.w, n, g.nn, history); \
-    else if (acc64) hipLaunchKernelGGL((pass_b_kernel<U_, true>), dim3(ntiles_b), dim3(256), 0, st, x, grad, s, g.w, n, g.nn, history); \
-    else hipLaunchKernelGGL((pass_b_kernel<U_, false>), dim3(ntiles_b), dim3(256), 0, st, x, grad, s, g.w, n, g.nn, history);      \
-  } while (0)
-  if (tile_b == 4096) STV_LAUNCH_PASS_B(4);
-  else if (tile_b == 2048) STV_LAUNCH_PASS_B(2);
-  else STV_LAUNCH_PASS_B(1);
-#undef STV_LAUNCH_PASS_B
+  hipLaunchKernelGGL(by_tile(tile_b, pass_b_kernel<1>, pass_b_kernel<2>, pass_b_kernel<4>), dim3((int)(g.nn / tile_b)), dim3(256),
+                     0, st, x, grad, s, g.w, n, g.nn, history);
   STV_CHECK_LAUNCH();
   return STV_OK;
 }

@@ -410,3 +410,28 @@ def test_fresh_content_targets_are_never_served_from_a_stale_cache(monkeypatch):
         del fresh
     # (on the caching allocator the later targets reuse the first one's address: the case the cache key alone missed)
     print(f"distinct target addresses over 4 assignments: {len(seen)}")
+
+
+# ------------------------------------------------------------------------------ executor: re-capture on another stream
+def test_program_recaptures_when_the_stream_changes():
+    """A captured program belongs to the stream it was captured on: run under another stream it destroys its graph and
+    captures again (warm-up + capture, then replays), and going back does the same once more."""
+    from style_transfer_visualizer_amd import _lib, plan
+
+    n = 4096
+    x = torch.empty(n, device=DEV, dtype=torch.float32)
+    out = torch.empty(n, device=DEV, dtype=torch.float32)
+    clear, relu = _lib.StvOp(), _lib.StvOp()
+    clear.op, clear.q0, clear.n = _lib.OP_MEMSET, out.data_ptr(), out.numel() * out.element_size()
+    relu.op, relu.dtype, relu.p0, relu.q0, relu.n = _lib.OP_RELU_FWD, _lib.STV_F32, x.data_ptr(), out.data_ptr(), n
+    prog = plan.Program([clear, relu], [x, out])
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    for stream in (a, a, a, b, b, a):
+        with torch.cuda.stream(stream):
+            x.copy_(torch.randn(n, device=DEV, generator=gen))      # fresh values: a run that did nothing shows
+            prog.run(use_graph=True)
+        stream.synchronize()
+        assert torch.equal(out, torch.relu(x))
+    del prog

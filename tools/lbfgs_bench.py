@@ -1,7 +1,7 @@
 """Steady-state (m = history) time of one device L-BFGS step, isolated (diagnostic).
 
 python tools/lbfgs_bench.py [size ...]   ->  ms per stv_lbfgsc_step at n = 3*size^2, history 100, ring full.
-A/B switches are read by the library at load time (e.g. STV_LBFGS_ACC=f32)."""
+Tuning aids are read by the library at load time (e.g. STV_LBFGS_TILE=2048)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -30,4 +30,4 @@ for size in [int(a) for a in sys.argv[1:]] or [512, 1024]:
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / reps
     gb = (4 * hist + 8) * n * 4 / 1e9
-    print(f"size {size}: {ms:.4f} ms per L-BFGS step at m={hist}  ({gb / ms:.2f} TB/s of the (4m+8) n 4 B model)  acc={os.environ.get('STV_LBFGS_ACC', 'f64')}")
+    print(f"size {size}: {ms:.4f} ms per L-BFGS step at m={hist}  ({gb / ms:.2f} TB/s of the (4m+8) n 4 B model)")

@@ -8,10 +8,8 @@ for S in 512 1024; do
   python tools/lbfgs_bench.py $S 2>/dev/null >> $L
   for T in 1024 2048 4096; do
     for PG in 1 2 3 4; do
-      for PI in 0 1; do
-        echo -n "A tile=$T pgroups=$PG pipe=$PI  " >> $L
-        STV_LBFGS_TILE=$T STV_LBFGS_PGROUPS=$PG STV_LBFGS_PIPE=$PI python tools/lbfgs_bench.py $S 2>/dev/null >> $L
-      done
+      echo -n "A tile=$T pgroups=$PG  " >> $L
+      STV_LBFGS_TILE=$T STV_LBFGS_PGROUPS=$PG python tools/lbfgs_bench.py $S 2>/dev/null >> $L
     done
   done
   for TB in 1024 2048 4096; do
