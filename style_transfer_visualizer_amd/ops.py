@@ -277,8 +277,10 @@ def conv_igemm_route(dy: torch.Tensor, w: torch.Tensor, pool_idx: torch.Tensor, 
 
 
 def gram_multi(feats: list[torch.Tensor], targets: list[torch.Tensor], *, coef: float = 1.0,
-               clamp_max: float = 5e5) -> tuple[list[torch.Tensor], list[torch.Tensor], list[torch.Tensor]]:
-    """Batched Gram chain (stv_gram_multi) over NHWC feature maps: returns (grams, loss partials, seeds) per tap."""
+               clamp_max: float = 5e5, coef_dev: torch.Tensor | None = None,
+               ) -> tuple[list[torch.Tensor], list[torch.Tensor], list[torch.Tensor]]:
+    """Batched Gram chain (stv_gram_multi) over NHWC feature maps: returns (grams, loss partials, seeds) per tap.
+    ``coef_dev``: a one-element fp32 device tensor every tap's seed is multiplied by."""
     lib = _lib.load()
     table = (_lib.StvGramTap * len(feats))()
     keep, grams, parts, seeds = [], [], [], []
@@ -293,7 +295,7 @@ def gram_multi(feats: list[torch.Tensor], targets: list[torch.Tensor], *, coef: 
         grams.append(g); parts.append(lp); seeds.append(sg)
         e.F, e.partials, e.target, e.gram_out, e.loss_part, e.sgrad = (_ptr(f), _ptr(partials), _ptr(t), _ptr(g), _ptr(lp),
                                                                       _ptr(sg))
-        e.coef_dev = None
+        e.coef_dev = _ptr(coef_dev)
         e.n_pixels, e.channels = n, C
         e.clamp_max, e.norm, e.coef = clamp_max, float(C * n), coef
     _lib.check(lib.stv_gram_multi(ctypes.addressof(table), len(feats), dtype_code(feats[0].dtype), _stream()),
@@ -448,6 +450,20 @@ def loss_combine(parts: torch.Tensor, table: torch.Tensor, scale: torch.Tensor, 
     lib = _lib.load()
     _lib.check(lib.stv_loss_combine(_ptr(parts), _ptr(table), _ptr(scale), table.shape[0], style_w, content_w,
                                     _ptr(losses), _ptr(scores), _stream()), "stv_loss_combine")
+
+
+def loss_combine_log(parts: torch.Tensor, table: torch.Tensor, scale: torch.Tensor, style_w: float,
+                     content_w: float, losses: torch.Tensor, scores: torch.Tensor, ring: torch.Tensor,
+                     count: torch.Tensor, seq: torch.Tensor | None = None) -> None:
+    """:func:`loss_combine` that also appends the three scores to ``ring`` [3, capacity] fp32 at slot
+    ``count % capacity`` and adds one to ``count`` ([1] int32, device).  With ``seq`` ([1] int32) ring and seq are
+    views of a :class:`HostMailbox`, whose host pointer is the device's; the record count is published there."""
+    lib = _lib.load()
+    host = seq is not None
+    ring_p = ring.data_ptr() if host else _ptr(ring)
+    _lib.check(lib.stv_loss_combine_log(_ptr(parts), _ptr(table), _ptr(scale), table.shape[0], style_w, content_w,
+                                        _ptr(losses), _ptr(scores), ring_p, ring.shape[1], _ptr(count),
+                                        seq.data_ptr() if host else None, _stream()), "stv_loss_combine_log")
 
 
 # ---- frame / PNG export ---------------------------------------------------------
