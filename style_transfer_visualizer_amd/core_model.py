@@ -314,7 +314,9 @@ class _Engine:
         self.layers, self.style_at, self.content_at = layers, style_at, content_at
         self.H, self.W, self.dtype, self.device = H, W, dtype, device
         self.split = split
-        self.sched = plan.Schedule(layers, style_at, content_at, H, W, dtype, device, with_grad=True, split=split)
+        self.switches = plan.Switches.from_env()      # the A/B switches as they stand now, for every program of this engine
+        self.sched = plan.Schedule(layers, style_at, content_at, H, W, dtype, device, with_grad=True, split=split,
+                                   switches=self.switches)
         s = self.sched
         self.n_style, self.n_content = len(s.style_taps), len(s.content_taps)
         n_terms = self.n_style + self.n_content
@@ -338,7 +340,7 @@ class _Engine:
         self.scores = torch.zeros(4, device=device, dtype=torch.float32)
         self.coef_buf = torch.ones(max(n_terms, 1), device=device, dtype=torch.float32)
         self._programs: dict = {}
-        self.use_graph = os.environ.get("STV_HIP_GRAPH", "1") != "0"
+        self.use_graph = self.switches.hip_graph
         # Every evaluation overwrites the shared activation buffers; an autograd backward is only
         # valid against the forward that filled them last.  `generation` counts evaluations.
         self.generation = 0
@@ -365,7 +367,7 @@ class _Engine:
 
     def _content_fused(self, tap) -> bool:
         """One content tap per buffer, nothing else writing that buffer's gradient first (A/B: STV_FUSE_CONTENT=0)."""
-        return (os.environ.get("STV_FUSE_CONTENT", "1") != "0" and tap.buf.grad is not None
+        return (self.switches.fuse_content and tap.buf.grad is not None
                 and sum(1 for t in tap.buf.taps if t.kind == "content") == 1)
 
     def _forward_with_losses(self, x: torch.Tensor, *, style_coef: float, with_seed: bool,
@@ -378,13 +380,13 @@ class _Engine:
         # right behind their producer.  512^2: all five taps batched; 1024^2: the three deep ones.
         # Same arithmetic and summation order either way (the batched kernels run the per-tap bodies).
         s = self.sched
-        mode = os.environ.get("STV_LOSS_BATCH", "auto")
+        mode = self.switches.loss_batch
         limit = 48 * 2 ** 20
 
         def small(tap) -> bool:
             return tap.buf.act.numel() * tap.buf.act.element_size() <= limit
         deferred = [tap for tap in s.style_taps if mode == "1" or (mode == "auto" and small(tap))]
-        if len(deferred) < 2 or len(deferred) > 8 or not x.is_cuda:
+        if len(deferred) < 2 or len(deferred) > 8 or not s.device_form:
             deferred = []
         held = {id(tap) for tap in deferred}
         # Round 4: a LARGE tap keeps only its partial-sum pass behind its producer (that pass reads the activation:
@@ -392,49 +394,39 @@ class _Engine:
         # launch at the end of the forward pass instead of being a 6-7 us launch of its own (two launches fewer at
         # 1024^2; STV_GRAM_FIN_LATE=0: finish right behind the partial sums, as before).  Same kernels' bodies, same
         # summation order per tap up to the grouping of a many-slab tap's slabs (8 instead of 32 per partial sum).
-        late: list = []
-        fin_late = bool(deferred) and os.environ.get("STV_GRAM_FIN_LATE", "1") != "0" and len(s.style_taps) <= 8
-
-        def batched_tail() -> list:
-            # built AFTER the forward ops: whether the first layer leaves its own Gram slabs
-            # (tap.partials_fused) is decided while those are emitted
-            if not deferred:
-                return []
-            members = sorted(deferred + late, key=lambda t: t.order)
+        late = []
+        if deferred and self.switches.gram_fin_late and len(s.style_taps) <= 8:
+            late = [tap for tap in s.style_taps if id(tap) not in held]
+        tail = []
+        if deferred:
             specs = [dict(tap=tap, target=tap.target, loss_part=self.parts[tap.parts_off:],
                           sgrad=tap.sgrad if with_seed else None, coef=style_coef,
-                          partials_ready=any(tap is t for t in late)) for tap in members]
-            return [s.gram_multi_op(specs)]
+                          partials_ready=id(tap) not in held) for tap in (s.style_taps if late else deferred)]
+            tail = [s.gram_multi_op(specs)]
         if deferred and len(deferred) == len(s.style_taps):
-            fwd = s.forward_ops(x)
-            tail = batched_tail()
             for tap in s.content_taps:
                 tail += self._tap_loss_ops(tap, style_coef=style_coef, coef_dev=None, with_seed=with_seed,
                                            content_coef=content_coef)
-            return fwd + tail
+            return s.forward_ops(x) + tail
 
         def after(node):
             out = []
             for tap in node.dst.taps:
                 if id(tap) in held:
                     continue
-                if fin_late and tap.kind == "style":
-                    if not tap.partials_fused:      # (a first layer that left its own slabs has nothing to do here)
-                        out += s.gram_ops(tap, gram_out=None, target=None, loss_part=None, sgrad=None, coef=0.0,
-                                          coef_dev=None, finish=False)
-                    late.append(tap)
+                if late and tap.kind == "style":     # partial sums here (unless the first layer left them itself), finish in the tail
+                    out += s.gram_ops(tap, gram_out=None, target=None, loss_part=None, sgrad=None, coef=0.0,
+                                      coef_dev=None, finish=False)
                     continue
                 out += self._tap_loss_ops(tap, style_coef=style_coef, coef_dev=None, with_seed=with_seed,
                                           content_coef=content_coef)
             return out
-        if os.environ.get("STV_LOSS_INTERLEAVE", "1") == "1":
-            fwd = self.sched.forward_ops(x, after_node=after)
-            return fwd + batched_tail()
-        fwd = self.sched.forward_ops(x)
+        if self.switches.loss_interleave:
+            return s.forward_ops(x, after_node=after) + tail
         inline = []
-        for node in self.sched.nodes:
+        for node in s.nodes:
             inline += after(node)
-        return fwd + inline + batched_tail()
+        return s.forward_ops(x) + inline + tail
 
     def _combine_op(self, style_w: float, content_w: float, score_log: tuple | None = None):
         """``score_log`` = (ring fp32 [3, capacity], device counter int32 [1][, host-visible record count int32 [1]]):
@@ -492,7 +484,7 @@ class _Engine:
         Hs, Ws = x.shape[-2:]
         sched = (self.sched if (Hs, Ws) == (self.H, self.W) else
                  plan.Schedule(self.layers, self.style_at, self.content_at, Hs, Ws, self.dtype, self.device,
-                               with_grad=False, split=self.split))
+                               with_grad=False, split=self.split, switches=self.switches))
         grams = []
 
         def build():
@@ -586,8 +578,7 @@ class _Engine:
                 tail.append(op)
             return (self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w)
                     + [self._combine_op(style_w, content_w, score_log)]
-                    + s.backward_ops(grad, style_coef=style_w, content_coef=content_w, coef_dev=None,
-                                     prewritten=fused_content)
+                    + s.backward_ops(grad, content_coef=content_w, coef_dev=None, prewritten=fused_content)
                     + tail)
         self._program(key, build).run(self.use_graph)
 
@@ -610,7 +601,7 @@ class _Engine:
             for tap in s.style_taps:   # recompute the seeds with the upstream coefficients
                 seeds += s.gram_ops(tap, gram_out=None, target=tap.target, loss_part=None, sgrad=tap.sgrad,
                                     coef=1.0, coef_dev=self.coef_buf[tap.order:], partial=False)
-            return seeds + s.backward_ops(grad, style_coef=1.0, content_coef=1.0, coef_dev=self.coef_buf)
+            return seeds + s.backward_ops(grad, content_coef=1.0, coef_dev=self.coef_buf)
         self._program(key, build).run(self.use_graph)
 
 

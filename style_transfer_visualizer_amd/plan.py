@@ -15,6 +15,11 @@ optimization.py:292-313):
   (Gram product, content difference) accumulate on top;
 * Gram backward is ``dF = F . S`` with the symmetric seed ``S`` produced by
   ``stv_gram_finish``; it runs as a 1x1 conv on the matrix cores.
+
+Which ops are fused is decided once, in ``Schedule._decide``, from the ``Switches`` the schedule was
+constructed with and from whether it runs on the GPU; the result lives in fields of ``Node``, ``Buf`` and
+``Tap``.  ``forward_ops``, ``alloc_grads``, ``backward_ops`` and the Gram emitters only read those fields,
+so the op lists of one schedule do not depend on the order, or the number of times, they are built.
 """
 from __future__ import annotations
 
@@ -32,6 +37,43 @@ from ._lib import (ACCUM, MASK, POOL_IDX, POOL_ONLY, POOL_ROUTE, W_BLOCKED, OP_G
                    OP_POOL_FWD, OP_RELU_BWD, OP_RELU_FWD, RELU_IN, RELU_OUT, StvOp)
 
 GRAM_CLAMP_MAX = 5e5  # reference constants.py:15
+
+
+@dataclass(frozen=True)
+class Switches:
+    """The step-level A/B switches, read once: when a ``Schedule`` or an engine is constructed."""
+
+    fuse_pool: bool = True            # STV_FUSE_POOL
+    pool_idx: bool = True             # STV_POOL_IDX
+    fuse_gram_first: int = 1          # STV_FUSE_GRAM_FIRST: 0 never, 1 where it pays, 2 always
+    skip_prepool: bool = True         # STV_SKIP_PREPOOL
+    fuse_pool_bwd: bool = True        # STV_FUSE_POOL_BWD
+    fuse_gram: bool = True            # STV_FUSE_GRAM
+    w_blocked: bool = True            # STV_W_BLOCKED
+    grad_arena: int = 1               # STV_GRAD_ARENA: 0 one tensor per gradient, 1 slabs, 2 slabs also for host tensors
+    fuse_content: bool = True         # STV_FUSE_CONTENT
+    loss_batch: str = "auto"          # STV_LOSS_BATCH: "1" every style tap, "auto" the small ones, anything else none
+    gram_fin_late: bool = True        # STV_GRAM_FIN_LATE
+    loss_interleave: bool = True      # STV_LOSS_INTERLEAVE
+    hip_graph: bool = True            # STV_HIP_GRAPH
+
+    @classmethod
+    def from_env(cls) -> Switches:
+        def level(value: str) -> int:
+            return {"0": 0, "2": 2}.get(value, 1)
+        return cls(fuse_pool=os.environ.get("STV_FUSE_POOL", "1") != "0",
+                   pool_idx=os.environ.get("STV_POOL_IDX", "1") != "0",
+                   fuse_gram_first=level(os.environ.get("STV_FUSE_GRAM_FIRST", "1")),
+                   skip_prepool=os.environ.get("STV_SKIP_PREPOOL", "1") != "0",
+                   fuse_pool_bwd=os.environ.get("STV_FUSE_POOL_BWD", "1") != "0",
+                   fuse_gram=os.environ.get("STV_FUSE_GRAM", "1") != "0",
+                   w_blocked=os.environ.get("STV_W_BLOCKED", "1") != "0",
+                   grad_arena=level(os.environ.get("STV_GRAD_ARENA", "1")),
+                   fuse_content=os.environ.get("STV_FUSE_CONTENT", "1") != "0",
+                   loss_batch=os.environ.get("STV_LOSS_BATCH", "auto"),
+                   gram_fin_late=os.environ.get("STV_GRAM_FIN_LATE", "1") != "0",
+                   loss_interleave=os.environ.get("STV_LOSS_INTERLEAVE", "1") == "1",
+                   hip_graph=os.environ.get("STV_HIP_GRAPH", "1") != "0")
 
 
 @dataclass
@@ -59,7 +101,11 @@ class Node:
     wb: torch.Tensor | None = None
     bias: torch.Tensor | None = None
     cin: int = 0
+    # fixed by Schedule._decide:
+    fused: bool = False                 # pool nodes: the work rides in the preceding conv's epilogue
     idx: torch.Tensor | None = None     # pool nodes fused into a conv: arg-max byte map for the backward
+    route: Node | None = None           # conv nodes: the pool node whose backward rides in this conv's dgrad
+    gram: Tap | None = None             # conv nodes: the style tap whose dF = F.S rides in this conv's dgrad
 
 
 @dataclass
@@ -106,7 +152,8 @@ class Schedule:
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  H: int, W: int, dtype: torch.dtype, device: torch.device, *, with_grad: bool, halo: int = 0,
-                 split: bool = False) -> None:
+                 split: bool = False, switches: Switches | None = None, fuse_first_gram: bool = True,
+                 assume_device: bool = False) -> None:
         """``halo`` = 1: the schedule of one ROW STRIP of a larger image (spatial.py).  ``H`` is the
         strip's own row count; every activation (and the image) carries ``halo`` extra rows above and
         below that the owner fills before each 3x3 convolution reads them (neighbour's rows, or zeros
@@ -114,20 +161,25 @@ class Schedule:
         from split bf16 operands (STV_BF16X3, weights pre-split at packing); every other op runs as in fp32.
         Convolutions run over the whole buffer - their output in the halo
         rows is meaningless and is replaced by the next exchange - while pooling works on the
-        strip's own rows only (strip heights are multiples of 16, so no window straddles two strips)."""
+        strip's own rows only (strip heights are multiples of 16, so no window straddles two strips).
+        ``fuse_first_gram=False``: the Gram of a tapped first layer runs over a sub-range of its buffer
+        (spatial.SpatialShard), so the first-layer kernel must not leave slabs of the whole map.
+        ``assume_device``: take the decisions of a GPU schedule on host tensors - to be inspected, never run."""
         self.H, self.W, self.dtype, self.device = H, W, dtype, device
         if split and (dtype != torch.float32 or halo):
             msg = "bf16x3 (split-bf16 products) runs on fp32 storage and whole images only (no row strips)"
             raise ValueError(msg)
         self.split = split
         self.halo = halo
-        self.fuse_first_gram = True      # off where the Gram runs over a sub-range of the buffer (spatial.SpatialShard)
+        self.switches = switches if switches is not None else Switches.from_env()
+        self.device_form = assume_device or device.type == "cuda"      # the fusions below exist as GPU kernels only
         self.nodes: list[Node] = []
         self.style_taps: list[Tap] = []
         self.content_taps: list[Tap] = []
         self.with_grad = with_grad
         self._keep: list = []      # tensors referenced by raw pointer from op arrays
         self._lower_forward(layers, style_at, content_at)
+        self._decide(fuse_first_gram)
 
     # ------------------------------------------------------------------ forward walk
     def _new_buf(self, H: int, W: int, C: int) -> Buf:
@@ -164,14 +216,14 @@ class Schedule:
                         msg = "a ReLU in front of the first convolution is not supported"
                         raise RuntimeError(msg)
                     node = Node("conv_first", None, dst, layer=i, wf=ops.pack_weights_fwd(w), bias=bias, cin=cin)
-                    if w.is_cuda:
+                    if self.device.type == "cuda":
                         node.wb = ops.conv_first_pack(node.wf)   # frozen weights: kernel-side packing, once
                 else:
                     wf = ops.pack_weights_fwd(w).to(self.dtype)
                     wb = ops.pack_weights_bwd(w).to(self.dtype) if self.with_grad else None
                     # matrix-core shapes take K-blocked weights (W_BLOCKED is derived from w.dim() == 4)
                     # A/B knob (bf16x3: always blocked - its 3x3 kernels read pre-split K-blocked weights only)
-                    blocked = self.split or os.environ.get("STV_W_BLOCKED", "1") != "0"
+                    blocked = self.split or self.switches.w_blocked
                     if blocked and ops.conv_uses_mfma(H, W, cin, cout, self.dtype, split=self.split):
                         wf = ops.block_weights(wf)
                         if self.split:     # frozen weights: split into bf16 hi / lo once, here
@@ -180,7 +232,7 @@ class Schedule:
                         wb = ops.block_weights(wb)
                         if self.split:
                             wb = ops.split_weights(wb)
-                    if w.is_cuda:      # measure the tile configurations of this layer's shapes once
+                    if self.device.type == "cuda":      # measure the tile configurations of this layer's shapes once
                         ops.conv_tune(H, W, cin, cout, 9, self.dtype, split=self.split)
                         if self.with_grad:
                             ops.conv_tune(H, W, cout, cin, 9, self.dtype, split=self.split)
@@ -231,6 +283,76 @@ class Schedule:
                     self.content_taps.append(tap)
             i = out_idx + 1
 
+    # ------------------------------------------------------------------ fusion decisions
+    def _decide(self, fuse_first_gram: bool) -> None:
+        """Every fusion of the step, fixed before any op is emitted, with the buffers each one needs.  All of them exist
+        as GPU kernels only (``device_form``); row strips pool their own rows and sum their own Gram ranges."""
+        sw = self.switches
+        whole = self.device_form and not self.halo
+        for k, nd in enumerate(self.nodes):
+            d = nd.dst
+            nxt = self.nodes[k + 1] if k + 1 < len(self.nodes) else None
+            tap = next((t for t in d.taps if t.kind == "style"), None)
+            # a tapped first layer leaves the Gram slabs of its own output (no second pass over the map).
+            # One slab per workgroup: pays once a workgroup walks >= 4 tiles of 8 x 32 pixels (1024^2: 8,
+            # -11 us; at 512^2, 2 tiles each, the slab reduction costs what the separate pass did)
+            if (nd.kind == "conv_first" and tap is not None and whole and fuse_first_gram and sw.fuse_gram_first
+                    and ops.conv_first_gram_supported(d.H, d.W, nd.cin, d.C, self.dtype)
+                    and (sw.fuse_gram_first == 2 or d.H * d.W >= 4 * 256 * ops.gram_ksplit(d.H * d.W, d.C))):
+                tap.partials_fused = True
+                self._partials(tap)
+            # conv (ReLU in its epilogue) -> pool: one launch writes both maps.  Only where the conv
+            # runs on the matrix cores, and not when the conv output itself is tapped pre-ReLU.
+            if (nd.kind == "conv" and whole and sw.fuse_pool and nxt is not None and nxt.kind == "pool"
+                    and d.relu_fused and nd.wf.dim() == 4):
+                nxt.fused = True
+                # the fused epilogue also leaves the arg-max map the pooling backward needs: one byte
+                # per pooled element instead of re-reading the full-resolution activation
+                if self.with_grad and sw.pool_idx:
+                    nxt.idx = torch.empty(nxt.dst.H, nxt.dst.W, nxt.dst.C, device=self.device, dtype=torch.uint8)
+                # The full-resolution map of a conv with the pool in its epilogue is dead in the bf16 step: the forward
+                # pass continues from the pooled map, the backward pass routes through the arg-max byte map (its bit 2 is
+                # the ReLU mask), and no tap sits on it - so it is not stored (conv1_2 at 1024^2: 134 MB of the
+                # kernel's 312; STV_SKIP_PREPOOL=0 stores it, e.g. for the tests that look at every stored tensor).
+                # fp32 (parity mode) keeps it: the parity tests read ReLU / arg-max decisions off the stored maps.
+                d.stored = not (sw.skip_prepool and not d.taps and self.dtype == torch.bfloat16
+                                and (not self.with_grad or nxt.idx is not None))
+        if not self.with_grad:
+            return
+        for k, nd in enumerate(self.nodes):
+            s = nd.src
+            if nd.kind != "conv" or nd.wb.dim() != 4 or not self.device_form:
+                continue
+            # A Gram tap on the pre-ReLU output s: its gradient term F.S lands on the same buffer
+            # as this dgrad.  One launch computes mask * dgrad + F.S (stv_conv_igemm_dual) instead
+            # of a second launch that re-reads and re-writes s.grad.
+            if sw.fuse_gram and not (s.relu_fused and s.taps) and s.C % (32 // s.act.element_size()) == 0:
+                nd.gram = next((t for t in s.taps if t.kind == "style"), None)
+            # s is a pooled map (arg-max byte map available, nothing else contributes to its gradient):
+            # the dgrad's epilogue routes straight into the pre-pool gradient - no pooled-resolution
+            # gradient, no pooling-backward pass.  Never into a buffer with a content tap: that gradient
+            # may already hold the content term (stv_content_loss_grad), and a routed dgrad stores.
+            pool_nd = self.nodes[k - 1]
+            if self._routable(nd, pool_nd) and not any(t.kind == "content" for t in pool_nd.src.taps):
+                nd.route = pool_nd
+
+    def _routable(self, nd: Node, pool_nd: Node) -> bool:
+        """The backward of `pool_nd`, the producer of conv `nd`'s input, can ride in `nd`'s dgrad: the input is a pooled
+        map with an arg-max byte map, no tap on it, no mask, no Gram term on this launch."""
+        s, d = nd.src, nd.dst
+        return (self.switches.fuse_pool_bwd and pool_nd.kind == "pool" and pool_nd.idx is not None
+                and self.dtype == torch.bfloat16 and not s.taps and not nd.relu_in and not s.relu_fused
+                and pool_nd.src.H == 2 * s.H and pool_nd.src.W == 2 * s.W
+                and 4 * s.act.numel() * s.act.element_size() < 2 ** 31
+                and d.act.numel() * d.act.element_size() < 2 ** 31)
+
+    def _partials(self, tap: Tap) -> torch.Tensor:
+        """The split-K Gram slabs of a style tap (scratch, allocated at first use)."""
+        if tap.partials is None:
+            b = tap.buf
+            tap.partials = torch.empty(ops.gram_ksplit(b.H * b.W, b.C), b.C, b.C, device=self.device, dtype=torch.float32)
+        return tap.partials
+
     # ------------------------------------------------------------------ op emission
     def _op(self, **kw) -> StvOp:
         op = StvOp()
@@ -247,61 +369,24 @@ class Schedule:
         """Forward schedule; ``after_node(node)`` may return extra ops to splice in right after a
         node's op (loss-side work that only needs that node's output)."""
         out = []
-        fuse_pool = os.environ.get("STV_FUSE_POOL", "1") != "0" and not self.halo     # A/B knob; strips pool their own rows
-        fused: set[int] = set()          # pool nodes whose work rides in the preceding conv's epilogue
         for k, nd in enumerate(self.nodes):
             d = nd.dst
-            # conv (ReLU in its epilogue) -> pool: one launch writes both maps.  Only where the conv
-            # runs on the matrix cores, and not when the conv output itself is tapped pre-ReLU.
-            nxt = self.nodes[k + 1] if k + 1 < len(self.nodes) else None
-            pool_dst = None
-            if (fuse_pool and nd.kind == "conv" and nxt is not None and nxt.kind == "pool" and nxt.src is d
-                    and d.relu_fused and nd.wf.dim() == 4 and d.act.is_cuda):
-                pool_dst = nxt.dst.act
-                fused.add(id(nxt))
-                # the fused epilogue also leaves the arg-max map the pooling backward needs: one byte
-                # per pooled element instead of re-reading the full-resolution activation
-                if self.with_grad and nxt.idx is None and os.environ.get("STV_POOL_IDX", "1") != "0":
-                    nxt.idx = torch.empty(nxt.dst.H, nxt.dst.W, nxt.dst.C, device=self.device, dtype=torch.uint8)
-            if id(nd) in fused:
+            if nd.fused:                 # its work rides in the preceding conv's epilogue
                 if after_node is not None:
                     out += after_node(nd)
                 continue
             if nd.kind == "conv_first":
-                # a tapped first layer leaves the Gram slabs of its own output (no second pass over the map)
-                slabs = None
                 tap = next((t for t in d.taps if t.kind == "style"), None)
-                if (tap is not None and nd.wb is not None and d.act.is_cuda and not self.halo and self.fuse_first_gram
-                        and os.environ.get("STV_FUSE_GRAM_FIRST", "1") != "0"
-                        and ops.conv_first_gram_supported(d.H, d.W, nd.cin, d.C, self.dtype)
-                        # one slab per workgroup: pays once a workgroup walks >= 4 tiles of 8 x 32 pixels (1024^2: 8,
-                        # -11 us; at 512^2, 2 tiles each, the slab reduction costs what the separate pass did)
-                        and (os.environ.get("STV_FUSE_GRAM_FIRST") == "2"
-                             or d.H * d.W >= 4 * 256 * ops.gram_ksplit(d.H * d.W, d.C))):
-                    if tap.partials is None:
-                        tap.partials = torch.empty(ops.gram_ksplit(d.H * d.W, d.C), d.C, d.C, device=self.device,
-                                                   dtype=torch.float32)
-                    slabs = tap.partials
-                if tap is not None:
-                    tap.partials_fused = slabs is not None      # (re-decided per build: the switch may have changed)
+                slabs = tap.partials if tap is not None and tap.partials_fused else None
                 out.append(self._op(op=OP_CONV_FIRST_FWD, p0=x, p1=nd.wf, p2=nd.bias, p3=nd.wb, q0=d.act, q1=slabs,
                                     H=d.H, W=d.W, cin=nd.cin, cout=d.C))
             elif nd.kind == "conv":
+                pool = self.nodes[k + 1] if k + 1 < len(self.nodes) and self.nodes[k + 1].fused else None
                 flags = ((RELU_IN if nd.relu_in else 0) | (RELU_OUT if d.relu_fused else 0)
-                         | (W_BLOCKED if nd.wf.dim() == 4 else 0))
-                # The full-resolution map of a conv with the pool in its epilogue is dead in the bf16 step: the forward
-                # pass continues from the pooled map, the backward pass routes through the arg-max byte map (its bit 2 is
-                # the ReLU mask), and no tap sits on it - so it is not stored (conv1_2 at 1024^2: 134 MB of the
-                # kernel's 312; STV_SKIP_PREPOOL=0 stores it, e.g. for the tests that look at every stored tensor).
-                # fp32 (parity mode) keeps it: the parity tests read ReLU / arg-max decisions off the stored maps.
-                d.stored = True
-                if (pool_dst is not None and not d.taps and self.dtype == torch.bfloat16
-                        and (not self.with_grad or nxt.idx is not None)
-                        and os.environ.get("STV_SKIP_PREPOOL", "1") != "0"):
-                    flags |= POOL_ONLY
-                    d.stored = False
-                out.append(self._op(op=OP_CONV, p0=nd.src.act, p1=nd.wf, p2=nd.bias, q0=d.act, q1=pool_dst,
-                                    q2=nxt.idx if pool_dst is not None else None, H=d.H,
+                         | (W_BLOCKED if nd.wf.dim() == 4 else 0) | (0 if d.stored else POOL_ONLY))
+                out.append(self._op(op=OP_CONV, p0=nd.src.act, p1=nd.wf, p2=nd.bias, q0=d.act,
+                                    q1=pool.dst.act if pool is not None else None,
+                                    q2=pool.idx if pool is not None else None, H=d.H,
                                     W=d.W, cin=nd.cin, cout=d.C, taps=9, flags=flags))
             elif nd.kind == "pool":
                 src_i = self.interior(nd.src.act)
@@ -317,14 +402,12 @@ class Schedule:
                  coef_dev: torch.Tensor | None, partial: bool = True, finish: bool = True) -> list[StvOp]:
         b = tap.buf
         n = b.H * b.W
-        if tap.partials is None:
-            tap.partials = torch.empty(ops.gram_ksplit(n, b.C), b.C, b.C, device=self.device, dtype=torch.float32)
         out = []
         if partial and not tap.partials_fused:
-            out.append(self._op(op=OP_GRAM_PARTIAL, p0=b.act, q0=tap.partials, n=n, cin=b.C))
+            out.append(self._op(op=OP_GRAM_PARTIAL, p0=b.act, q0=self._partials(tap), n=n, cin=b.C))
         if not finish:          # (the finish pass runs later, in a batched launch: gram_multi_op with partials_ready)
             return out
-        out.append(self._op(op=OP_GRAM_FINISH, p0=tap.partials, p1=target, p2=coef_dev, q0=gram_out, q1=loss_part,
+        out.append(self._op(op=OP_GRAM_FINISH, p0=self._partials(tap), p1=target, p2=coef_dev, q0=gram_out, q1=loss_part,
                             q2=sgrad, n=n, cin=b.C, f0=GRAM_CLAMP_MAX, f1=float(b.C * n), f2=coef))
         return out
 
@@ -342,32 +425,13 @@ class Schedule:
             tap = sp["tap"]
             b = tap.buf
             n = b.H * b.W
-            if tap.partials is None:
-                tap.partials = torch.empty(ops.gram_ksplit(n, b.C), b.C, b.C, device=self.device, dtype=torch.float32)
-            e.F, e.partials = (None if (tap.partials_fused or sp.get("partials_ready")) else ptr(b.act)), ptr(tap.partials)
+            e.F, e.partials = (None if (tap.partials_fused or sp.get("partials_ready")) else ptr(b.act)), ptr(self._partials(tap))
             e.target, e.gram_out, e.loss_part = ptr(sp.get("target")), ptr(sp.get("gram_out")), ptr(sp.get("loss_part"))
             e.sgrad, e.coef_dev = ptr(sp.get("sgrad")), ptr(sp.get("coef_dev"))
             e.n_pixels, e.channels = n, b.C
             e.clamp_max, e.norm, e.coef = GRAM_CLAMP_MAX, float(b.C * n), float(sp.get("coef", 0.0))
         self._keep.append(table)                    # the host array must outlive stv_program_create
         return self._op(op=OP_GRAM_MULTI, p0=ctypes.addressof(table), n=len(specs))
-
-    def _route_candidate(self, nd: Node, producer: dict) -> Node | None:
-        """The pool node whose backward can ride in the dgrad of conv `nd` (everything about that decision that does
-        not depend on what has been written so far): `nd`'s input is a pooled map with an arg-max byte map, no tap on
-        it, no mask, no Gram term on this launch (`backward_ops` adds: nothing wrote the pre-pool gradient yet)."""
-        s, d = nd.src, nd.dst
-        if nd.kind != "conv" or s is None or os.environ.get("STV_FUSE_POOL_BWD", "1") == "0":
-            return None
-        mask_src = nd.relu_in or (s.relu_fused and not s.taps)
-        pool_nd = producer.get(id(s))
-        if (pool_nd is None or pool_nd.kind != "pool" or pool_nd.idx is None or self.dtype != torch.bfloat16
-                or nd.wb is None or nd.wb.dim() != 4 or s.taps or mask_src
-                or pool_nd.src.H != 2 * s.H or pool_nd.src.W != 2 * s.W
-                or 4 * s.act.numel() * s.act.element_size() >= 2 ** 31
-                or d.act.numel() * d.act.element_size() >= 2 ** 31):
-            return None
-        return pool_nd
 
     def alloc_grads(self) -> None:
         """Gradient storage of every activation.  The reverse schedule is a chain - the op of node i reads the gradient
@@ -385,15 +449,14 @@ class Schedule:
         if not todo:
             return
         chain = all(nd.src is self.nodes[i - 1].dst for i, nd in enumerate(self.nodes) if i > 0)
-        mode = os.environ.get("STV_GRAD_ARENA", "1")          # "2": also for host tensors (the host tests walk the allocator)
-        arena = (mode != "0" and not self.halo and chain and len(todo) == len(self.nodes)
-                 and (mode == "2" or all(nd.dst.act.is_cuda for nd in self.nodes)))
+        mode = self.switches.grad_arena          # 2: also for host tensors (the host tests walk the allocator)
+        arena = (mode != 0 and not self.halo and chain and len(todo) == len(self.nodes)
+                 and (mode == 2 or self.device_form))
         if not arena:
             for nd in todo:              # strips: halo rows are read before anything wrote them -> start finite
                 nd.dst.grad = torch.zeros_like(nd.dst.act) if self.halo else torch.empty_like(nd.dst.act)
             return
         own = {id(t.buf) for t in self.content_taps}
-        producer = {id(n.dst): n for n in self.nodes}
         slab_of: dict[int, int] = {}       # id(buf) -> slab number
         free: list[int] = []               # released slabs, the most recently released last
         n_slabs = 0
@@ -412,21 +475,14 @@ class Schedule:
             if id(buf) in slab_of:
                 free.append(slab_of[id(buf)])
 
-        routed: set[int] = set()
-        unused: set[int] = set()
+        unused = {id(nd.route.dst) for nd in self.nodes if nd.route is not None}     # pooled maps whose gradient is never formed
         for nd in reversed(self.nodes):
             d = nd.dst
-            if id(nd) in routed:           # the pooled map's gradient is never formed
-                unused.add(id(d))
+            if id(d) in unused:
                 continue
             take(d)                        # (the deepest activation: first written by its own taps)
             if nd.kind != "conv_first":
-                pool_nd = self._route_candidate(nd, producer)
-                if pool_nd is not None and not any(t.kind == "content" for t in pool_nd.src.taps):
-                    take(pool_nd.src)
-                    routed.add(id(pool_nd))
-                else:
-                    take(nd.src)
+                take(nd.route.src if nd.route is not None else nd.src)
             release(d)
         rot = [nd.dst for nd in self.nodes if id(nd.dst) in slab_of]
         nbytes = max((b.act.numel() * b.act.element_size() for b in rot), default=0)
@@ -443,7 +499,7 @@ class Schedule:
             else:
                 b.grad = torch.empty_like(b.act)
 
-    def backward_ops(self, x_grad: torch.Tensor, *, style_coef: float, content_coef: float,
+    def backward_ops(self, x_grad: torch.Tensor, *, content_coef: float,
                      coef_dev: torch.Tensor | None, prewritten: tuple = ()) -> list[StvOp]:
         """Reverse schedule.  ``coef_dev`` (optional fp32 device vector, style terms
         first) holds upstream d(total)/d(loss_k) for the autograd path.  ``prewritten``: content taps whose
@@ -458,10 +514,9 @@ class Schedule:
             return ACCUM if id(buf) in written else 0
 
         n_style = len(self.style_taps)
-        fuse_gram = os.environ.get("STV_FUSE_GRAM", "1") != "0"      # A/B knob
-        fused_taps: set[int] = set()     # style taps whose dF = F.S rides in the dgrad that shares their buffer
-        routed: set[int] = set()         # pool nodes whose backward rides in the dgrad of the conv behind them
-        producer = {id(n.dst): n for n in self.nodes}
+        tune = self.device.type == "cuda"      # (conv_tune measures on the device; its result is cached per shape)
+        fused_taps = {id(nd.gram) for nd in self.nodes if nd.gram is not None}     # their dF = F.S rides in a dgrad
+        routed = {id(nd.route) for nd in self.nodes if nd.route is not None}      # their backward rides in a dgrad
         # gradients that share a slab (alloc_grads): whoever reads one must find its own writer's data there
         slab_of = getattr(self, "_grad_slab_of", {})
         holder: dict[int, int] = {}      # slab -> id(buf) of its last writer
@@ -486,8 +541,8 @@ class Schedule:
                 if id(tap) in fused_taps or id(tap) in pre:
                     continue
                 if tap.kind == "style":
-                    if d.act.is_cuda:
-                        ops.conv_tune(d.H, d.W, d.C, d.C, 1, self.dtype, split=self.split)     # cached per shape
+                    if tune:
+                        ops.conv_tune(d.H, d.W, d.C, d.C, 1, self.dtype, split=self.split)
                     out.append(self._op(op=OP_CONV, p0=d.act, p1=tap.sgrad, q0=wr(d), H=d.H, W=d.W,
                                         cin=d.C, cout=d.C, taps=1, flags=acc_flag(d)))
                 else:
@@ -509,32 +564,19 @@ class Schedule:
             mask_src = nd.relu_in or (s.relu_fused and not s.taps)
             if nd.kind == "conv":
                 flags = (MASK if mask_src else 0) | acc_flag(s) | (W_BLOCKED if nd.wb.dim() == 4 else 0)
-                # A Gram tap on the pre-ReLU output s: its gradient term F.S lands on the same buffer
-                # as this dgrad.  One launch computes mask * dgrad + F.S (stv_conv_igemm_dual) instead
-                # of a second launch that re-reads and re-writes s.grad.
-                gram = None
-                if (fuse_gram and nd.wb.dim() == 4 and s.act.is_cuda and not (s.relu_fused and s.taps)
-                        and s.C % (32 // s.act.element_size()) == 0):
-                    gram = next((t for t in s.taps if t.kind == "style" and t.sgrad is not None), None)
-                # s is a pooled map (arg-max byte map available, nothing else contributes to its gradient):
-                # the dgrad's epilogue routes straight into the pre-pool gradient - no pooled-resolution
-                # gradient, no pooling-backward pass
-                pool_nd = self._route_candidate(nd, producer)
-                if (gram is None and pool_nd is not None and id(s) not in written and id(pool_nd.src) not in written):
-                    ps = pool_nd.src
-                    if d.act.is_cuda:
-                        ops.conv_tune(s.H, s.W, d.C, s.C, ops.TUNE_ROUTE, self.dtype)     # cached per shape
+                if nd.route is not None:      # (s's own gradient is never formed)
+                    ps = nd.route.src
+                    if tune:
+                        ops.conv_tune(s.H, s.W, d.C, s.C, ops.TUNE_ROUTE, self.dtype)
                     rflags = (MASK if (ps.relu_fused and not ps.taps) else 0) | W_BLOCKED | POOL_ROUTE
-                    out.append(self._op(op=OP_CONV, p0=rd(d), p1=nd.wb, p2=pool_nd.idx, q1=wr(ps), H=s.H, W=s.W,
+                    out.append(self._op(op=OP_CONV, p0=rd(d), p1=nd.wb, p2=nd.route.idx, q1=wr(ps), H=s.H, W=s.W,
                                         cin=d.C, cout=s.C, taps=9, flags=rflags))
-                    routed.add(id(pool_nd))
                     written.add(id(s))
                     written.add(id(ps))
                     continue
-                if gram is not None:
-                    fused_taps.add(id(gram))
+                if nd.gram is not None:
                     out.append(self._op(op=OP_CONV, p0=rd(d), p1=nd.wb, p3=s.act if mask_src else None, q0=wr(s),
-                                        q2=s.act, q3=gram.sgrad, n=s.C, H=s.H, W=s.W, cin=d.C, cout=s.C, taps=9,
+                                        q2=s.act, q3=nd.gram.sgrad, n=s.C, H=s.H, W=s.W, cin=d.C, cout=s.C, taps=9,
                                         flags=flags))
                 else:
                     out.append(self._op(op=OP_CONV, p0=rd(d), p1=nd.wb, p3=s.act if mask_src else None, q0=wr(s),
@@ -552,7 +594,6 @@ class Schedule:
                 out.append(self._op(op=OP_RELU_BWD, p0=s.act, p1=rd(d), q0=wr(s), n=s.act.numel(),
                                     flags=acc_flag(s)))
             written.add(id(s))
-        _ = style_coef
         return out
 
 

@@ -59,8 +59,8 @@ class SpatialShard:
         self.c0, self.c1, self.e0, self.e1 = strip_rows(H, self.rank, self.world)
         self.style_w, self.content_w = float(style_w), float(content_w)
         He = self.e1 - self.e0
-        self.sched = s = plan.Schedule(layers, style_at, content_at, He, W, dtype, dev, with_grad=True)
-        s.fuse_first_gram = False        # the Gram sums run over the strip's core rows only (below)
+        self.sched = s = plan.Schedule(layers, style_at, content_at, He, W, dtype, dev, with_grad=True,
+                                       fuse_first_gram=False)      # the Gram sums run over the strip's core rows only (below)
         self.x_ext = torch.zeros(1, 3, He, W, device=dev)
         self.g_ext = torch.zeros(1, 3, He, W, device=dev)
 
@@ -139,7 +139,7 @@ class SpatialShard:
         self.scale = torch.tensor(scale, dtype=torch.float32, device=dev)
         p2.append(s._op(op=plan.OP_LOSS_COMBINE, p0=self.parts2, p1=self.table, p2=self.scale, q0=self.losses,
                         q1=self.scores, cin=n_terms, f0=self.style_w, f1=self.content_w))
-        bwd = s.backward_ops(self.g_ext, style_coef=self.style_w, content_coef=self.content_w, coef_dev=None)
+        bwd = s.backward_ops(self.g_ext, content_coef=self.content_w, coef_dev=None)
         ci = 0
         for o in bwd:     # content gradient is normalised by the GLOBAL element count
             if o.op == plan.OP_CONTENT_GRAD:
@@ -343,7 +343,7 @@ class HaloShard:
         p2.append(s._op(op=plan.OP_LOSS_COMBINE, p0=self.parts2, p1=self.table, p2=self.scale, q0=self.losses,
                         q1=self.scores, cin=n_terms, f0=self.style_w, f1=self.content_w))
         self.p2 = plan.Program(p2, s._keep)
-        bwd = s.backward_ops(self.g_ext, style_coef=self.style_w, content_coef=self.content_w, coef_dev=None)
+        bwd = s.backward_ops(self.g_ext, content_coef=self.content_w, coef_dev=None)
         ci = 0
         for o in bwd:
             if o.op == plan.OP_CONTENT_GRAD:

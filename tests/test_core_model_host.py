@@ -2,6 +2,8 @@
 and the loud failure of the HIP path on CPU tensors."""
 from __future__ import annotations
 
+import functools
+
 import pytest
 import torch
 from torch import nn
@@ -80,6 +82,7 @@ def test_precision_selection(monkeypatch):
         core_model.resolve_precision("fp8")
 
 
+@functools.cache
 def _layers():
     return list(core_model.build_vgg_features().eval().children())
 
@@ -106,7 +109,7 @@ def test_schedule_lowering_for_default_vgg19():
         tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C)
     for tap in s.content_taps:
         tap.target = torch.zeros_like(tap.buf.act)
-    bwd = s.backward_ops(torch.zeros_like(x), style_coef=1.0, content_coef=1.0, coef_dev=None)
+    bwd = s.backward_ops(torch.zeros_like(x), content_coef=1.0, coef_dev=None)
     ops_ = [o.op for o in bwd]
     assert ops_.count(_lib.OP_CONV) == 12 + 5               # 12 dgrads + 5 Gram products (1x1)
     assert ops_.count(_lib.OP_POOL_BWD) == 4 and ops_.count(_lib.OP_CONTENT_GRAD) == 1
@@ -352,14 +355,24 @@ def test_gradient_slabs_follow_the_reverse_schedule(style_at, content_at, monkey
     conv; taps on conv / ReLU / pool outputs): buffers with a content tap keep a tensor of their own; two gradients one
     op reads and writes never share a slab; `backward_ops` itself re-checks op by op that every reader finds its writer's
     data (it raises otherwise); the per-node form gives the same op list."""
+    for device_form in (False, True):
+        _check_gradient_slabs(style_at, content_at, monkeypatch, device_form)
+
+
+def _check_gradient_slabs(style_at, content_at, monkeypatch, device_form):
+    """``device_form``: the schedule the GPU runs (bf16: pools in the conv epilogues, pooling backward routed in the
+    dgrads), built on host tensors - the routed / never-formed branches of the allocator.  There, in addition: the pooled
+    gradient a routed dgrad skips is never formed, and the gradients that dgrad reads and writes are real, distinct slabs."""
+    dtype = torch.bfloat16 if device_form else torch.float32
+
     def build(arena):
         monkeypatch.setenv("STV_GRAD_ARENA", arena)
-        s = plan.Schedule(_layers(), style_at, content_at, 32, 32, torch.float32, CPU, with_grad=True)
+        s = plan.Schedule(_layers(), style_at, content_at, 32, 32, dtype, CPU, with_grad=True, assume_device=device_form)
         for tap in s.style_taps:
-            tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C)
+            tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C, dtype=dtype)
         for tap in s.content_taps:
             tap.target = torch.zeros_like(tap.buf.act)
-        ops_ = s.backward_ops(torch.zeros(1, 3, 32, 32), style_coef=1.0, content_coef=1.0, coef_dev=None)
+        ops_ = s.backward_ops(torch.zeros(1, 3, 32, 32), content_coef=1.0, coef_dev=None)
         return s, ops_
     s, ops_a = build("2")
     s0, ops_0 = build("0")
@@ -368,8 +381,13 @@ def test_gradient_slabs_follow_the_reverse_schedule(style_at, content_at, monkey
     assert 1 <= slabs.shape[0] <= 3
     base = slabs.untyped_storage().data_ptr()
     own = {id(t.buf) for t in s.content_taps}
+    skipped = {id(nd.route.dst) for nd in s.nodes if nd.route is not None}
+    assert device_form or not skipped
     for i, nd in enumerate(s.nodes):
         b = nd.dst
+        if id(b) in skipped:                 # the routed dgrad writes the pre-pool gradient: this one is never formed
+            assert b.grad.numel() == 0 and id(b) not in slab_of
+            continue
         assert b.grad.shape == b.act.shape and b.grad.dtype == b.act.dtype
         if id(b) in own:
             assert b.grad.untyped_storage().data_ptr() != base and id(b) not in slab_of
@@ -378,8 +396,117 @@ def test_gradient_slabs_follow_the_reverse_schedule(style_at, content_at, monkey
             assert b.grad.data_ptr() == slabs[slab_of[id(b)]].data_ptr()
         if i > 0 and id(b) in slab_of and id(nd.src) in slab_of:      # the op of node i reads b's gradient and writes src's
             assert slab_of[id(b)] != slab_of[id(nd.src)]
-    per_node = sum(nd.dst.act.numel() * 4 for nd in s0.nodes)
+        if nd.route is not None:             # ... or, routed, the gradient in front of the pool: a real slab, not the reader's
+            ps = nd.route.src
+            assert id(ps) in slab_of and slab_of[id(ps)] != slab_of[id(b)] and ps.grad.shape == ps.act.shape
+    routed_ops = [o for o in ops_a if o.op == _lib.OP_CONV and o.flags & _lib.POOL_ROUTE]
+    assert len(routed_ops) == len(skipped)
+    assert sorted(o.q1 for o in routed_ops) == sorted(nd.route.src.grad.data_ptr() for nd in s.nodes if nd.route is not None)
+    per_node = sum(nd.dst.act.numel() * nd.dst.act.element_size() for nd in s0.nodes)
     assert slabs.numel() < per_node
     # a second build of the reverse schedule (the autograd path builds its own program) reuses the assignment
-    again = s.backward_ops(torch.zeros(1, 3, 32, 32), style_coef=1.0, content_coef=1.0, coef_dev=None)
+    again = s.backward_ops(torch.zeros(1, 3, 32, 32), content_coef=1.0, coef_dev=None)
     assert len(again) == len(ops_a) and s._grad_slabs is slabs
+
+
+# ------------------------------------------------------------------ the schedule the GPU runs, decided on host tensors
+def _device_form(dtype, H, W, style_at, content_at, **kw):
+    s = plan.Schedule(_layers(), style_at, content_at, H, W, dtype, CPU, with_grad=True, assume_device=True, **kw)
+    for tap in s.style_taps:
+        tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C, dtype=dtype)
+    for tap in s.content_taps:
+        tap.target = torch.zeros_like(tap.buf.act)
+    return s
+
+
+@functools.cache
+def _image(H, W, which):
+    return torch.zeros(1, 3, H, W)
+
+
+def _fwd(s):
+    return s.forward_ops(_image(s.H, s.W, "x"))
+
+
+def _bwd(s):
+    return s.backward_ops(_image(s.H, s.W, "x.grad"), content_coef=1.0, coef_dev=None)
+
+
+def _sig(op_list, pointers=False):
+    names = ["op", "dtype", "flags", "taps", "H", "W", "cin", "cout", "n", "f0", "f1", "f2", "f3"]
+    names += ["p0", "p1", "p2", "p3", "q0", "q1", "q2", "q3"] if pointers else []
+    return [tuple(getattr(o, k) for k in names) for o in op_list]
+
+
+def _census(s):
+    fwd, bwd = _fwd(s), _bwd(s)
+    convs = [o for o in fwd if o.op == _lib.OP_CONV]
+    dgrads = [o for o in bwd if o.op == _lib.OP_CONV and o.taps == 9]
+    pool_bwd = [o for o in bwd if o.op == _lib.OP_POOL_BWD]
+    return dict(fwd=len(fwd), pool_fwd=sum(o.op == _lib.OP_POOL_FWD for o in fwd), fused_pool=sum(bool(o.q1) for o in convs),
+                pool_only=sum(bool(o.flags & _lib.POOL_ONLY) for o in convs),
+                unstored=[nd.layer for nd in s.nodes if not nd.dst.stored],
+                bwd=len(bwd), pool_bwd=len(pool_bwd), pool_bwd_idx=sum(bool(o.flags & _lib.POOL_IDX) for o in pool_bwd),
+                routed=sum(bool(o.flags & _lib.POOL_ROUTE) for o in dgrads), dual=sum(o.n > 0 for o in dgrads),
+                gram_1x1=sum(o.op == _lib.OP_CONV and o.taps == 1 for o in bwd), slabs=s._grad_slabs.shape[0])
+
+
+DEFAULT_TAPS = ([0, 5, 10, 19, 28], [21])
+
+
+@pytest.mark.parametrize("dtype,H,W,taps,want", [
+    (torch.bfloat16, 64, 64, DEFAULT_TAPS,       # what bench.py measures (at 512^2): no pool op in either direction
+     dict(fwd=13, pool_fwd=0, fused_pool=4, pool_only=4, unstored=[2, 7, 16, 25],
+          bwd=15, pool_bwd=0, pool_bwd_idx=0, routed=4, dual=4, gram_1x1=1, slabs=2)),
+    (torch.float32, 64, 64, DEFAULT_TAPS,        # parity mode: pools fused forward, every map stored, nothing routed
+     dict(fwd=13, pool_fwd=0, fused_pool=4, pool_only=0, unstored=[],
+          bwd=19, pool_bwd=4, pool_bwd_idx=4, routed=0, dual=4, gram_1x1=1, slabs=2)),
+    (torch.bfloat16, 64, 48, ([0, 5, 10, 19, 28], [7]),      # conv2_2 tapped pre-ReLU: its pool stays a pass of its own
+     dict(fwd=14, pool_fwd=1, fused_pool=3, pool_only=3, unstored=[2, 16, 25],
+          bwd=16, pool_bwd=1, pool_bwd_idx=0, routed=3, dual=4, gram_1x1=1, slabs=2)),
+    (torch.bfloat16, 32, 32, ([2, 7], [16, 25]),              # every conv in front of a pool tapped: nothing fused
+     dict(fwd=15, pool_fwd=3, fused_pool=0, pool_only=0, unstored=[],
+          bwd=19, pool_bwd=3, pool_bwd_idx=0, routed=0, dual=0, gram_1x1=2, slabs=2)),
+    (torch.bfloat16, 32, 32, ([28], [0]),
+     dict(fwd=13, pool_fwd=0, fused_pool=4, pool_only=4, unstored=[2, 7, 16, 25],
+          bwd=15, pool_bwd=0, pool_bwd_idx=0, routed=4, dual=0, gram_1x1=1, slabs=2)),
+])
+def test_device_form_schedule(dtype, H, W, taps, want):
+    """The fusions of the schedule the GPU runs, decided on host tensors (``assume_device``; never run): pools in the conv
+    epilogues, pre-pool maps not stored, pooling backward routed in the dgrads, Gram terms riding in dgrads.
+    tests/test_gpu_model.py::test_device_form_matches_the_device ties this form to a schedule built on the GPU."""
+    assert _census(_device_form(dtype, H, W, *taps)) == want
+
+
+@pytest.mark.parametrize("mode", [0, 2])
+def test_device_form_first_layer_gram(mode):
+    s = _device_form(torch.bfloat16, 64, 64, *DEFAULT_TAPS, switches=plan.Switches(fuse_gram_first=mode))
+    first, tap = _fwd(s)[0], s.style_taps[0]
+    assert first.op == _lib.OP_CONV_FIRST_FWD and tap.partials_fused == (mode == 2)
+    assert first.q1 == (tap.partials.data_ptr() if mode == 2 else None)
+    # ... and not where the Gram runs over a sub-range of the buffer (row strips with recomputed halos)
+    s = _device_form(torch.bfloat16, 64, 64, *DEFAULT_TAPS, switches=plan.Switches(fuse_gram_first=2), fuse_first_gram=False)
+    assert not s.style_taps[0].partials_fused and _fwd(s)[0].q1 is None
+
+
+def test_op_lists_do_not_depend_on_build_order():
+    """Everything an op list depends on is fixed when the schedule is constructed: the reverse schedule built before any
+    forward schedule is the one built after it, and a second build of either repeats the first, pointers included."""
+    a, b = (_device_form(torch.bfloat16, 64, 64, *DEFAULT_TAPS) for _ in range(2))
+    bwd_a, fwd_a = _bwd(a), _fwd(a)
+    fwd_b, bwd_b = _fwd(b), _bwd(b)
+    assert _sig(bwd_a) == _sig(bwd_b) and _sig(fwd_a) == _sig(fwd_b)
+    assert any(o.flags & _lib.POOL_ROUTE for o in bwd_a)
+    assert _sig(_bwd(a), pointers=True) == _sig(bwd_a, pointers=True)
+    assert _sig(_fwd(a), pointers=True) == _sig(fwd_a, pointers=True)
+
+
+def test_switches_are_read_when_the_schedule_is_constructed(monkeypatch):
+    monkeypatch.delenv("STV_FUSE_POOL", raising=False)
+    s = _device_form(torch.bfloat16, 64, 64, *DEFAULT_TAPS)
+    before = _sig(_fwd(s), pointers=True), _sig(_bwd(s), pointers=True)
+    monkeypatch.setenv("STV_FUSE_POOL", "0")
+    assert (_sig(_fwd(s), pointers=True), _sig(_bwd(s), pointers=True)) == before
+    assert len(before[0]) == 13
+    fresh = [o.op for o in _fwd(_device_form(torch.bfloat16, 64, 64, *DEFAULT_TAPS))]
+    assert len(fresh) == 17 and fresh.count(_lib.OP_POOL_FWD) == 4

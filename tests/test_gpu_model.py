@@ -608,3 +608,23 @@ def test_4k_image_runs(monkeypatch):
 # (The whole 3840x2160 image in fp32 against the CPU oracle - losses 1e-5, gradient incl. the last rows at the largest
 #  32-bit byte offsets - is part of tests/test_gpu_configs.py::test_configs4_200_adam_steps since round 4: there the
 #  image is the one the four-strip run holds after 100 Adam steps, and the strips are checked against it too.)
+
+
+def test_device_form_matches_the_device(monkeypatch):
+    """tests/test_core_model_host.py inspects the GPU's schedule on host tensors (``assume_device``).  That form is the
+    schedule built on the device: same ops, flags and dimensions, forward and backward, with the first-layer Gram fused."""
+    from style_transfer_visualizer_amd import plan
+    monkeypatch.setenv("STV_FUSE_GRAM_FIRST", "2")
+    layers = list(core_model.build_vgg_features().eval().children())
+    sigs = []
+    for dev, assume in ((DEV, False), (torch.device("cpu"), True)):
+        s = plan.Schedule(layers, [0, 5, 10, 19, 28], [21], 64, 64, torch.bfloat16, dev, with_grad=True, assume_device=assume)
+        for tap in s.style_taps:
+            tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C, device=dev, dtype=torch.bfloat16)
+        for tap in s.content_taps:
+            tap.target = torch.zeros_like(tap.buf.act)
+        x = torch.zeros(1, 3, 64, 64, device=dev)
+        op_list = s.forward_ops(x) + s.backward_ops(torch.zeros_like(x), content_coef=1.0, coef_dev=None)
+        sigs.append([(o.op, o.dtype, o.flags, o.taps, o.H, o.W, o.cin, o.cout, o.n) for o in op_list])
+        assert s.style_taps[0].partials_fused and s._grad_slabs.shape[0] == 2
+    assert sigs[0] == sigs[1] and len(sigs[0]) == 13 + 15
