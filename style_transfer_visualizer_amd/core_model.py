@@ -310,13 +310,15 @@ class _Engine:
     """Buffers + command buffers for one (model, image size, device)."""
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
-                 H: int, W: int, dtype: torch.dtype, device: torch.device, *, split: bool = False) -> None:
+                 H: int, W: int, dtype: torch.dtype, device: torch.device, *, split: bool = False,
+                 assume_device: bool = False) -> None:
+        """``assume_device``: as for ``plan.Schedule`` - the step a GPU engine builds, on host tensors, to be inspected."""
         self.layers, self.style_at, self.content_at = layers, style_at, content_at
         self.H, self.W, self.dtype, self.device = H, W, dtype, device
         self.split = split
-        self.switches = plan.Switches.from_env()      # the A/B switches as they stand now, for every program of this engine
+        # (the A/B switches as they stand now, for every program of this engine)
         self.sched = plan.Schedule(layers, style_at, content_at, H, W, dtype, device, with_grad=True, split=split,
-                                   switches=self.switches)
+                                   switches=plan.Switches.from_env(), assume_device=assume_device)
         s = self.sched
         self.n_style, self.n_content = len(s.style_taps), len(s.content_taps)
         n_terms = self.n_style + self.n_content
@@ -340,121 +342,66 @@ class _Engine:
         self.scores = torch.zeros(4, device=device, dtype=torch.float32)
         self.coef_buf = torch.ones(max(n_terms, 1), device=device, dtype=torch.float32)
         self._programs: dict = {}
-        self.use_graph = self.switches.hip_graph
+        self.use_graph = s.switches.hip_graph
         # Every evaluation overwrites the shared activation buffers; an autograd backward is only
         # valid against the forward that filled them last.  `generation` counts evaluations.
         self.generation = 0
         self._stage: torch.Tensor | None = None      # fp32 contiguous copy of a non-conforming input
 
     # -- op list pieces -------------------------------------------------------
-    def _tap_loss_ops(self, tap, *, style_coef: float, coef_dev: torch.Tensor | None, with_seed: bool,
-                      content_coef: float | None = None) -> list:
-        """Loss-side ops of one tap.  They are spliced in right after the op that produces the tapped
-        activation, while it is still L2 / Infinity-Cache resident."""
-        s = self.sched
-        if tap.kind == "style":
-            cd = coef_dev[tap.order:] if coef_dev is not None else None
-            ops_ = s.gram_ops(tap, gram_out=None, target=tap.target, loss_part=self.parts[tap.parts_off:],
-                              sgrad=tap.sgrad if with_seed else None, coef=style_coef, coef_dev=cd)
-        elif content_coef is not None and self._content_fused(tap):
-            # loss and gradient of the content term in one pass (the coefficient is known: the fused step)
-            ops_ = [s._op(op=plan.OP_CONTENT_LOSS, p0=tap.buf.act, p1=tap.target, q0=self.parts[tap.parts_off:],
-                          q1=tap.buf.grad, n=tap.buf.act.numel(), f0=content_coef)]
-        else:
-            ops_ = [s._op(op=plan.OP_CONTENT_LOSS, p0=tap.buf.act, p1=tap.target,
-                          q0=self.parts[tap.parts_off:], n=tap.buf.act.numel())]
-        return ops_
-
-    def _content_fused(self, tap) -> bool:
-        """One content tap per buffer, nothing else writing that buffer's gradient first (A/B: STV_FUSE_CONTENT=0)."""
-        return (self.switches.fuse_content and tap.buf.grad is not None
-                and sum(1 for t in tap.buf.taps if t.kind == "content") == 1)
-
     def _forward_with_losses(self, x: torch.Tensor, *, style_coef: float, with_seed: bool,
                              content_coef: float | None = None) -> list:
-        # Batched loss side: the Gram chain of a tap is a handful of latency-bound launches (partial
-        # sums, finish), and side by side in one grid (stv_gram_multi) several taps cost the slowest
-        # instead of the sum.  Deferring a tap to the end of the forward pass only pays while its
-        # activation is small enough to still sit in the Infinity Cache by then, so the decision is
-        # per tap: taps up to 48 MiB are batched behind the last conv, larger ones keep their place
-        # right behind their producer.  512^2: all five taps batched; 1024^2: the three deep ones.
-        # Same arithmetic and summation order either way (the batched kernels run the per-tap bodies).
+        """Forward pass with the loss-side ops of every tap where ``Schedule._decide`` placed them: spliced in right
+        behind the op that produces the tapped activation (while it is still L2 / Infinity-Cache resident), or in the
+        tail - one batched Gram launch, then the content terms that follow it.  ``content_coef`` (the fused step: the
+        coefficient is known) lets a content tap form loss and gradient in one pass."""
         s = self.sched
-        mode = self.switches.loss_batch
-        limit = 48 * 2 ** 20
+        if content_coef is not None:
+            s.alloc_grads()          # the content term's gradient is written during the forward half
 
-        def small(tap) -> bool:
-            return tap.buf.act.numel() * tap.buf.act.element_size() <= limit
-        deferred = [tap for tap in s.style_taps if mode == "1" or (mode == "auto" and small(tap))]
-        if len(deferred) < 2 or len(deferred) > 8 or not s.device_form:
-            deferred = []
-        held = {id(tap) for tap in deferred}
-        # Round 4: a LARGE tap keeps only its partial-sum pass behind its producer (that pass reads the activation:
-        # 67-134 MB at 1024^2); its FINISH pass - a reduction of a few MB of fp32 slabs - joins the batched finish
-        # launch at the end of the forward pass instead of being a 6-7 us launch of its own (two launches fewer at
-        # 1024^2; STV_GRAM_FIN_LATE=0: finish right behind the partial sums, as before).  Same kernels' bodies, same
-        # summation order per tap up to the grouping of a many-slab tap's slabs (8 instead of 32 per partial sum).
-        late = []
-        if deferred and self.switches.gram_fin_late and len(s.style_taps) <= 8:
-            late = [tap for tap in s.style_taps if id(tap) not in held]
-        tail = []
-        if deferred:
-            specs = [dict(tap=tap, target=tap.target, loss_part=self.parts[tap.parts_off:],
-                          sgrad=tap.sgrad if with_seed else None, coef=style_coef,
-                          partials_ready=id(tap) not in held) for tap in (s.style_taps if late else deferred)]
-            tail = [s.gram_multi_op(specs)]
-        if deferred and len(deferred) == len(s.style_taps):
-            for tap in s.content_taps:
-                tail += self._tap_loss_ops(tap, style_coef=style_coef, coef_dev=None, with_seed=with_seed,
-                                           content_coef=content_coef)
-            return s.forward_ops(x) + tail
+        def chain(tap) -> list:
+            if tap.kind == "style":
+                return s.gram_ops(tap, gram_out=None, target=tap.target, loss_part=self.parts[tap.parts_off:],
+                                  sgrad=tap.sgrad if with_seed else None, coef=style_coef, coef_dev=None)
+            fused = content_coef is not None and tap.grad_fused
+            return [s.emit(op=plan.OP_CONTENT_LOSS, p0=tap.buf.act, p1=tap.target, q0=self.parts[tap.parts_off:],
+                           q1=tap.buf.grad if fused else None, n=tap.buf.act.numel(), f0=content_coef if fused else 0.0)]
+        batch = [dict(tap=tap, target=tap.target, loss_part=self.parts[tap.parts_off:],
+                      sgrad=tap.sgrad if with_seed else None, coef=style_coef, partials_ready=tap.finish_late)
+                 for tap in s.style_taps if tap.in_tail or tap.finish_late]
+        tail = [s.gram_multi_op(batch)] if batch else []
+        for tap in s.content_taps:
+            if tap.in_tail:
+                tail += chain(tap)
 
-        def after(node):
+        def after(node) -> list:
             out = []
             for tap in node.dst.taps:
-                if id(tap) in held:
-                    continue
-                if late and tap.kind == "style":     # partial sums here (unless the first layer left them itself), finish in the tail
+                if tap.finish_late:      # partial sums here (unless the first layer left them itself), finish in the tail
                     out += s.gram_ops(tap, gram_out=None, target=None, loss_part=None, sgrad=None, coef=0.0,
                                       coef_dev=None, finish=False)
-                    continue
-                out += self._tap_loss_ops(tap, style_coef=style_coef, coef_dev=None, with_seed=with_seed,
-                                          content_coef=content_coef)
+                elif not tap.in_tail:
+                    out += chain(tap)
             return out
-        if self.switches.loss_interleave:
+        if s.interleave:
             return s.forward_ops(x, after_node=after) + tail
-        inline = []
-        for node in s.nodes:
-            inline += after(node)
-        return s.forward_ops(x) + inline + tail
+        return s.forward_ops(x) + [op for node in s.nodes for op in after(node)] + tail
 
     def _combine_op(self, style_w: float, content_w: float, score_log: tuple | None = None):
         """``score_log`` = (ring fp32 [3, capacity], device counter int32 [1][, host-visible record count int32 [1]]):
         the combine kernel also appends the three scores to the caller's history ring (stv_loss_combine_log)."""
         ring, count, seq = (tuple(score_log) + (None,))[:3] if score_log is not None else (None, None, None)
-        return self.sched._op(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=self.table, p2=self.scale, p3=seq,
-                              q0=self.losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
-                              cin=self.n_style + self.n_content, f0=style_w, f1=content_w)
+        return self.sched.emit(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=self.table, p2=self.scale, p3=seq,
+                               q0=self.losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
+                               cin=self.n_style + self.n_content, f0=style_w, f1=content_w)
 
     def _program(self, key: tuple, builder) -> plan.Program:
         prog = self._programs.get(key)
         if prog is None:
             if len(self._programs) >= 16:     # programs are keyed by buffer addresses: bound the cache (oldest out)
                 self._programs.pop(next(iter(self._programs)))
-            prog = self._build(self.sched, builder)
-            self._programs[key] = prog
+            prog = self._programs[key] = plan.Program(builder())
         return prog
-
-    @staticmethod
-    def _build(sched: plan.Schedule, builder, extra: tuple = ()) -> plan.Program:
-        """Program from ``builder()``'s ops, owning exactly the tensors those ops reference by raw
-        pointer (the schedule's keep-alive list is restored: it must not grow with every program,
-        or every image ever evaluated would stay allocated)."""
-        base = len(sched._keep)
-        op_list = builder()
-        keep = sched._keep[base:] + list(extra)
-        del sched._keep[base:]
-        return plan.Program(op_list, keep)
 
     # -- targets ---------------------------------------------------------------
     def stage_input(self, x: torch.Tensor) -> torch.Tensor:
@@ -472,7 +419,7 @@ class _Engine:
     def capture_content(self, content_img: torch.Tensor) -> list[torch.Tensor]:
         self.generation += 1
         x = content_img.detach().contiguous().float()
-        self._build(self.sched, lambda: self.sched.forward_ops(x), (x,)).run()
+        plan.Program(self.sched.forward_ops(x)).run()
         targets = [tap.buf.act.clone() for tap in self.sched.content_taps]
         for tap, t in zip(self.sched.content_taps, targets, strict=True):
             tap.target = t
@@ -484,18 +431,12 @@ class _Engine:
         Hs, Ws = x.shape[-2:]
         sched = (self.sched if (Hs, Ws) == (self.H, self.W) else
                  plan.Schedule(self.layers, self.style_at, self.content_at, Hs, Ws, self.dtype, self.device,
-                               with_grad=False, split=self.split, switches=self.switches))
-        grams = []
-
-        def build():
-            op_list = sched.forward_ops(x)
-            for tap in sched.style_taps:
-                g = torch.empty(tap.buf.C, tap.buf.C, device=self.device, dtype=torch.float32)
-                grams.append(g)
-                op_list += sched.gram_ops(tap, gram_out=g, target=None, loss_part=None, sgrad=None, coef=0.0,
-                                          coef_dev=None)
-            return op_list
-        self._build(sched, build, (x, sched)).run()
+                               with_grad=False, split=self.split, switches=self.sched.switches))
+        grams = [torch.empty(tap.buf.C, tap.buf.C, device=self.device, dtype=torch.float32) for tap in sched.style_taps]
+        op_list = sched.forward_ops(x)
+        for tap, g in zip(sched.style_taps, grams, strict=True):
+            op_list += sched.gram_ops(tap, gram_out=g, target=None, loss_part=None, sgrad=None, coef=0.0, coef_dev=None)
+        plan.Program(op_list, extra=(sched,)).run()      # (a schedule of the style image's own size lives as long as its program)
         for tap, g in zip(self.sched.style_taps, grams, strict=True):
             tap.target = g
         return grams
@@ -562,20 +503,19 @@ class _Engine:
 
         def build():
             s = self.sched
-            s.alloc_grads()          # the content term's gradient is written during the forward half
-            fused_content = tuple(t for t in s.content_taps if self._content_fused(t))
+            fused_content = tuple(t for t in s.content_taps if t.grad_fused)
             tail = []
             if then_step is not None:
                 # m_max = history: the reduction's grid covers a full history from the first step on (blocks past the
                 # live pairs return at once), so ONE captured graph serves every step
-                op = s._op(op=_lib.OP_LBFGS_STEP, p0=grad, q0=x, q1=then_step.state, q2=then_step.work, n=x.numel(),
-                           cin=then_step.history, cout=then_step.history, f0=then_step.lr, f1=then_step.tol_grad,
-                           f2=then_step.tol_change)
+                kw = dict(op=_lib.OP_LBFGS_STEP, p0=grad, q0=x, q1=then_step.state, q2=then_step.work, n=x.numel(),
+                          cin=then_step.history, cout=then_step.history, f0=then_step.lr, f1=then_step.tol_grad,
+                          f2=then_step.tol_change)
                 if then_step.iters_per_step:
                     # several iterations per optimizer step: the same program replays for each of them (position and
                     # stop flag are device state); the step's loss test reads the total the combine op wrote
-                    op.op, op.taps, op.p1 = _lib.OP_LBFGS_ITER, then_step.iters_per_step, self.scores[2:].data_ptr()
-                tail.append(op)
+                    kw.update(op=_lib.OP_LBFGS_ITER, taps=then_step.iters_per_step, p1=self.scores[2:])
+                tail.append(s.emit(**kw))
             return (self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w)
                     + [self._combine_op(style_w, content_w, score_log)]
                     + s.backward_ops(grad, content_coef=content_w, coef_dev=None, prewritten=fused_content)

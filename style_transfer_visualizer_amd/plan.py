@@ -16,10 +16,15 @@ optimization.py:292-313):
 * Gram backward is ``dF = F . S`` with the symmetric seed ``S`` produced by
   ``stv_gram_finish``; it runs as a 1x1 conv on the matrix cores.
 
-Which ops are fused is decided once, in ``Schedule._decide``, from the ``Switches`` the schedule was
-constructed with and from whether it runs on the GPU; the result lives in fields of ``Node``, ``Buf`` and
-``Tap``.  ``forward_ops``, ``alloc_grads``, ``backward_ops`` and the Gram emitters only read those fields,
-so the op lists of one schedule do not depend on the order, or the number of times, they are built.
+Which ops are fused, and where the loss-side ops of every tap go (behind its producer, or in the batched tail of
+the forward pass), is decided once, in ``Schedule._decide``, from the ``Switches`` the schedule was constructed
+with and from whether it runs on the GPU; the result lives in fields of ``Node``, ``Buf``, ``Tap`` and the
+schedule.  ``forward_ops``, ``alloc_grads``, ``backward_ops``, the Gram emitters and the engine's loss head only
+read those fields, so the op lists of one schedule do not depend on the order, or the number of times, they are built.
+
+An op owns its operands: ``Schedule.emit`` records every tensor an op names by raw pointer on the op object
+(``op.refs``), and a ``Program`` keeps alive what its ops reference (:func:`operands`) - nothing accumulates on the
+schedule, and a program pins exactly what it runs on.
 """
 from __future__ import annotations
 
@@ -120,6 +125,10 @@ class Tap:
     sgrad: torch.Tensor | None = None
     parts_off: int = 0
     parts_cnt: int = 0
+    # fixed by Schedule._decide - where the tap's loss-side ops go (row strips build a head of their own: unused there):
+    in_tail: bool = False             # in the batched tail behind the last conv; False: right behind its producer
+    finish_late: bool = False         # style: partial sums behind the producer, only the finish pass in the tail
+    grad_fused: bool = False          # content: the fused step forms loss and gradient in one pass (stv_content_loss_grad)
 
 
 def _check_layer(layer: nn.Module, idx: int) -> str:
@@ -177,7 +186,6 @@ class Schedule:
         self.style_taps: list[Tap] = []
         self.content_taps: list[Tap] = []
         self.with_grad = with_grad
-        self._keep: list = []      # tensors referenced by raw pointer from op arrays
         self._lower_forward(layers, style_at, content_at)
         self._decide(fuse_first_gram)
 
@@ -317,6 +325,10 @@ class Schedule:
                 # fp32 (parity mode) keeps it: the parity tests read ReLU / arg-max decisions off the stored maps.
                 d.stored = not (sw.skip_prepool and not d.taps and self.dtype == torch.bfloat16
                                 and (not self.with_grad or nxt.idx is not None))
+        self._place_losses()
+        # the gradients of the reverse chain rotate through a few slabs (alloc_grads); 2: also on host tensors
+        chain = all(nd.src is self.nodes[i - 1].dst for i, nd in enumerate(self.nodes) if i > 0)
+        self.grad_arena = bool(sw.grad_arena and not self.halo and chain and (sw.grad_arena == 2 or self.device_form))
         if not self.with_grad:
             return
         for k, nd in enumerate(self.nodes):
@@ -336,6 +348,37 @@ class Schedule:
             if self._routable(nd, pool_nd) and not any(t.kind == "content" for t in pool_nd.src.taps):
                 nd.route = pool_nd
 
+    def _place_losses(self) -> None:
+        """Where the loss-side ops of every tap go (part of ``_decide``).  The Gram chain of a tap is a handful of
+        latency-bound launches (partial sums, finish), and side by side in one grid (stv_gram_multi) several taps cost
+        the slowest instead of the sum.  Deferring a tap to the end of the forward pass only pays while its activation
+        is small enough to still sit in the Infinity Cache by then, so the decision is per tap: taps up to 48 MiB are
+        batched behind the last conv, larger ones keep their place right behind their producer (512^2: all five taps
+        batched; 1024^2: the three deep ones).  Same arithmetic and summation order either way (the batched kernels run
+        the per-tap bodies).  A batch holds 2 to 8 taps and exists as a GPU kernel only."""
+        sw = self.switches
+
+        def small(tap: Tap) -> bool:
+            return tap.buf.act.numel() * tap.buf.act.element_size() <= 48 * 2 ** 20
+        tail = [tap for tap in self.style_taps if sw.loss_batch == "1" or (sw.loss_batch == "auto" and small(tap))]
+        if not 2 <= len(tail) <= 8 or not self.device_form:
+            tail = []
+        for tap in tail:
+            tap.in_tail = True
+        # A LARGE tap keeps only its partial-sum pass behind its producer (that pass reads the activation: 67-134 MB at
+        # 1024^2); its FINISH pass - a reduction of a few MB of fp32 slabs - joins the batched launch instead of being
+        # a 6-7 us launch of its own (STV_GRAM_FIN_LATE=0: finish right behind the partial sums).  Same kernels' bodies,
+        # same summation order per tap up to the grouping of a many-slab tap's slabs (8 instead of 32 per partial sum).
+        if tail and sw.gram_fin_late and len(self.style_taps) <= 8:
+            for tap in self.style_taps:
+                tap.finish_late = not tap.in_tail
+        for tap in self.content_taps:
+            tap.in_tail = bool(tail) and len(tail) == len(self.style_taps)      # the content terms follow the batched launch
+            # one content tap on the buffer: nothing else has written that buffer's gradient when the forward half gets there
+            tap.grad_fused = (sw.fuse_content and self.with_grad
+                              and sum(1 for t in tap.buf.taps if t.kind == "content") == 1)
+        self.interleave = sw.loss_interleave      # loss ops right behind their producers; False: all behind the last conv
+
     def _routable(self, nd: Node, pool_nd: Node) -> bool:
         """The backward of `pool_nd`, the producer of conv `nd`'s input, can ride in `nd`'s dgrad: the input is a pooled
         map with an arg-max byte map, no tap on it, no mask, no Gram term on this launch."""
@@ -354,13 +397,16 @@ class Schedule:
         return tap.partials
 
     # ------------------------------------------------------------------ op emission
-    def _op(self, **kw) -> StvOp:
+    def emit(self, **kw) -> StvOp:
+        """One op of this schedule's precision.  A tensor argument becomes its address in the op; the tensor itself
+        is recorded under the field's name in ``op.refs``, so whoever holds the op holds its operands."""
         op = StvOp()
         # bf16x3: the ops that form products take STV_BF16X3, every other op runs on the fp32 storage as STV_F32
         op.dtype = ops.dtype_code(self.dtype, split=self.split and kw.get("op") in _PRODUCT_OPS)
+        op.refs = {}
         for k, v in kw.items():
             if isinstance(v, torch.Tensor):
-                self._keep.append(v)
+                op.refs[k] = v
                 v = v.data_ptr()
             setattr(op, k, v)
         return op
@@ -378,21 +424,21 @@ class Schedule:
             if nd.kind == "conv_first":
                 tap = next((t for t in d.taps if t.kind == "style"), None)
                 slabs = tap.partials if tap is not None and tap.partials_fused else None
-                out.append(self._op(op=OP_CONV_FIRST_FWD, p0=x, p1=nd.wf, p2=nd.bias, p3=nd.wb, q0=d.act, q1=slabs,
-                                    H=d.H, W=d.W, cin=nd.cin, cout=d.C))
+                out.append(self.emit(op=OP_CONV_FIRST_FWD, p0=x, p1=nd.wf, p2=nd.bias, p3=nd.wb, q0=d.act, q1=slabs,
+                                     H=d.H, W=d.W, cin=nd.cin, cout=d.C))
             elif nd.kind == "conv":
                 pool = self.nodes[k + 1] if k + 1 < len(self.nodes) and self.nodes[k + 1].fused else None
                 flags = ((RELU_IN if nd.relu_in else 0) | (RELU_OUT if d.relu_fused else 0)
                          | (W_BLOCKED if nd.wf.dim() == 4 else 0) | (0 if d.stored else POOL_ONLY))
-                out.append(self._op(op=OP_CONV, p0=nd.src.act, p1=nd.wf, p2=nd.bias, q0=d.act,
-                                    q1=pool.dst.act if pool is not None else None,
-                                    q2=pool.idx if pool is not None else None, H=d.H,
-                                    W=d.W, cin=nd.cin, cout=d.C, taps=9, flags=flags))
+                out.append(self.emit(op=OP_CONV, p0=nd.src.act, p1=nd.wf, p2=nd.bias, q0=d.act,
+                                     q1=pool.dst.act if pool is not None else None,
+                                     q2=pool.idx if pool is not None else None, H=d.H,
+                                     W=d.W, cin=nd.cin, cout=d.C, taps=9, flags=flags))
             elif nd.kind == "pool":
                 src_i = self.interior(nd.src.act)
-                out.append(self._op(op=OP_POOL_FWD, p0=src_i, q0=self.interior(d.act), H=src_i.shape[0], W=nd.src.W, cin=d.C))
+                out.append(self.emit(op=OP_POOL_FWD, p0=src_i, q0=self.interior(d.act), H=src_i.shape[0], W=nd.src.W, cin=d.C))
             else:
-                out.append(self._op(op=OP_RELU_FWD, p0=nd.src.act, q0=d.act, n=d.act.numel()))
+                out.append(self.emit(op=OP_RELU_FWD, p0=nd.src.act, q0=d.act, n=d.act.numel()))
             if after_node is not None:
                 out += after_node(nd)
         return out
@@ -404,22 +450,23 @@ class Schedule:
         n = b.H * b.W
         out = []
         if partial and not tap.partials_fused:
-            out.append(self._op(op=OP_GRAM_PARTIAL, p0=b.act, q0=self._partials(tap), n=n, cin=b.C))
+            out.append(self.emit(op=OP_GRAM_PARTIAL, p0=b.act, q0=self._partials(tap), n=n, cin=b.C))
         if not finish:          # (the finish pass runs later, in a batched launch: gram_multi_op with partials_ready)
             return out
-        out.append(self._op(op=OP_GRAM_FINISH, p0=self._partials(tap), p1=target, p2=coef_dev, q0=gram_out, q1=loss_part,
-                            q2=sgrad, n=n, cin=b.C, f0=GRAM_CLAMP_MAX, f1=float(b.C * n), f2=coef))
+        out.append(self.emit(op=OP_GRAM_FINISH, p0=self._partials(tap), p1=target, p2=coef_dev, q0=gram_out, q1=loss_part,
+                             q2=sgrad, n=n, cin=b.C, f0=GRAM_CLAMP_MAX, f1=float(b.C * n), f2=coef))
         return out
 
     def gram_multi_op(self, specs: list[dict]) -> StvOp:
         """One batched Gram chain (stv_gram_multi) for several taps.  ``specs``: per tap the keyword
         arguments of :meth:`gram_ops` plus ``tap``.  The tap table is a host array the program copies."""
         table = (_lib.StvGramTap * len(specs))()
+        refs: dict = {"p0": table}                  # the host array must outlive stv_program_create
 
         def ptr(t: torch.Tensor | None) -> int | None:
             if t is None:
                 return None
-            self._keep.append(t)
+            refs[len(refs)] = t
             return t.data_ptr()
         for e, sp in zip(table, specs, strict=True):
             tap = sp["tap"]
@@ -430,8 +477,9 @@ class Schedule:
             e.sgrad, e.coef_dev = ptr(sp.get("sgrad")), ptr(sp.get("coef_dev"))
             e.n_pixels, e.channels = n, b.C
             e.clamp_max, e.norm, e.coef = GRAM_CLAMP_MAX, float(b.C * n), float(sp.get("coef", 0.0))
-        self._keep.append(table)                    # the host array must outlive stv_program_create
-        return self._op(op=OP_GRAM_MULTI, p0=ctypes.addressof(table), n=len(specs))
+        op = self.emit(op=OP_GRAM_MULTI, p0=ctypes.addressof(table), n=len(specs))
+        op.refs = refs
+        return op
 
     def alloc_grads(self) -> None:
         """Gradient storage of every activation.  The reverse schedule is a chain - the op of node i reads the gradient
@@ -448,11 +496,7 @@ class Schedule:
         todo = [nd for nd in self.nodes if nd.dst.grad is None]
         if not todo:
             return
-        chain = all(nd.src is self.nodes[i - 1].dst for i, nd in enumerate(self.nodes) if i > 0)
-        mode = self.switches.grad_arena          # 2: also for host tensors (the host tests walk the allocator)
-        arena = (mode != 0 and not self.halo and chain and len(todo) == len(self.nodes)
-                 and (mode == 2 or self.device_form))
-        if not arena:
+        if not (self.grad_arena and len(todo) == len(self.nodes)):
             for nd in todo:              # strips: halo rows are read before anything wrote them -> start finite
                 nd.dst.grad = torch.zeros_like(nd.dst.act) if self.halo else torch.empty_like(nd.dst.act)
             return
@@ -499,9 +543,10 @@ class Schedule:
             else:
                 b.grad = torch.empty_like(b.act)
 
-    def backward_ops(self, x_grad: torch.Tensor, *, content_coef: float,
+    def backward_ops(self, x_grad: torch.Tensor, *, content_coef: float | list[float],
                      coef_dev: torch.Tensor | None, prewritten: tuple = ()) -> list[StvOp]:
-        """Reverse schedule.  ``coef_dev`` (optional fp32 device vector, style terms
+        """Reverse schedule.  ``content_coef``: the coefficient of the content gradient, one for all content taps or one
+        per tap (in tap order).  ``coef_dev`` (optional fp32 device vector, style terms
         first) holds upstream d(total)/d(loss_k) for the autograd path.  ``prewritten``: content taps whose
         gradient the forward half already WROTE into their buffer's ``grad`` (stv_content_loss_grad): no
         content-gradient pass for them, and whatever produces that gradient next accumulates onto it."""
@@ -543,23 +588,24 @@ class Schedule:
                 if tap.kind == "style":
                     if tune:
                         ops.conv_tune(d.H, d.W, d.C, d.C, 1, self.dtype, split=self.split)
-                    out.append(self._op(op=OP_CONV, p0=d.act, p1=tap.sgrad, q0=wr(d), H=d.H, W=d.W,
-                                        cin=d.C, cout=d.C, taps=1, flags=acc_flag(d)))
+                    out.append(self.emit(op=OP_CONV, p0=d.act, p1=tap.sgrad, q0=wr(d), H=d.H, W=d.W,
+                                         cin=d.C, cout=d.C, taps=1, flags=acc_flag(d)))
                 else:
                     cd = coef_dev[n_style + tap.order:] if coef_dev is not None else None
-                    out.append(self._op(op=OP_CONTENT_GRAD, p0=d.act, p1=tap.target, p2=cd, q0=wr(d),
-                                        n=d.act.numel(), f0=content_coef, flags=acc_flag(d)))
+                    coef = content_coef[tap.order] if isinstance(content_coef, (list, tuple)) else content_coef
+                    out.append(self.emit(op=OP_CONTENT_GRAD, p0=d.act, p1=tap.target, p2=cd, q0=wr(d),
+                                         n=d.act.numel(), f0=coef, flags=acc_flag(d)))
                 written.add(id(d))
             if id(d) not in written:
                 msg = "internal: activation without any gradient contribution"
                 raise RuntimeError(msg)
             if d.relu_fused and d.taps:
                 # taps see relu(z): mask the summed gradient once, in place
-                out.append(self._op(op=OP_RELU_BWD, p0=d.act, p1=rd(d), q0=d.grad, n=d.act.numel()))
+                out.append(self.emit(op=OP_RELU_BWD, p0=d.act, p1=rd(d), q0=d.grad, n=d.act.numel()))
             s = nd.src
             if nd.kind == "conv_first":
-                out.append(self._op(op=OP_CONV_FIRST_DGRAD, p0=rd(d), p1=nd.wf, p2=nd.wb, q0=x_grad, H=d.H, W=d.W,
-                                    cin=nd.cin, cout=d.C))
+                out.append(self.emit(op=OP_CONV_FIRST_DGRAD, p0=rd(d), p1=nd.wf, p2=nd.wb, q0=x_grad, H=d.H, W=d.W,
+                                     cin=nd.cin, cout=d.C))
                 continue
             mask_src = nd.relu_in or (s.relu_fused and not s.taps)
             if nd.kind == "conv":
@@ -569,39 +615,47 @@ class Schedule:
                     if tune:
                         ops.conv_tune(s.H, s.W, d.C, s.C, ops.TUNE_ROUTE, self.dtype)
                     rflags = (MASK if (ps.relu_fused and not ps.taps) else 0) | W_BLOCKED | POOL_ROUTE
-                    out.append(self._op(op=OP_CONV, p0=rd(d), p1=nd.wb, p2=nd.route.idx, q1=wr(ps), H=s.H, W=s.W,
-                                        cin=d.C, cout=s.C, taps=9, flags=rflags))
+                    out.append(self.emit(op=OP_CONV, p0=rd(d), p1=nd.wb, p2=nd.route.idx, q1=wr(ps), H=s.H, W=s.W,
+                                         cin=d.C, cout=s.C, taps=9, flags=rflags))
                     written.add(id(s))
                     written.add(id(ps))
                     continue
                 if nd.gram is not None:
-                    out.append(self._op(op=OP_CONV, p0=rd(d), p1=nd.wb, p3=s.act if mask_src else None, q0=wr(s),
-                                        q2=s.act, q3=nd.gram.sgrad, n=s.C, H=s.H, W=s.W, cin=d.C, cout=s.C, taps=9,
-                                        flags=flags))
+                    out.append(self.emit(op=OP_CONV, p0=rd(d), p1=nd.wb, p3=s.act if mask_src else None, q0=wr(s),
+                                         q2=s.act, q3=nd.gram.sgrad, n=s.C, H=s.H, W=s.W, cin=d.C, cout=s.C, taps=9,
+                                         flags=flags))
                 else:
-                    out.append(self._op(op=OP_CONV, p0=rd(d), p1=nd.wb, p3=s.act if mask_src else None, q0=wr(s),
-                                        H=s.H, W=s.W, cin=d.C, cout=s.C, taps=9, flags=flags))
+                    out.append(self.emit(op=OP_CONV, p0=rd(d), p1=nd.wb, p3=s.act if mask_src else None, q0=wr(s),
+                                         H=s.H, W=s.W, cin=d.C, cout=s.C, taps=9, flags=flags))
             elif nd.kind == "pool":
                 flags = (MASK if (s.relu_fused and not s.taps) else 0) | acc_flag(s)
                 if nd.idx is not None:      # written by the forward conv that carried this pool
-                    out.append(self._op(op=OP_POOL_BWD, p0=nd.idx, p1=rd(d), q0=wr(s), H=s.H, W=s.W, cin=s.C,
-                                        flags=flags | POOL_IDX))
+                    out.append(self.emit(op=OP_POOL_BWD, p0=nd.idx, p1=rd(d), q0=wr(s), H=s.H, W=s.W, cin=s.C,
+                                         flags=flags | POOL_IDX))
                 else:
                     s_i = self.interior(s.act)
-                    out.append(self._op(op=OP_POOL_BWD, p0=s_i, p1=self.interior(rd(d)), q0=self.interior(wr(s)),
-                                        H=s_i.shape[0], W=s.W, cin=s.C, flags=flags))
+                    out.append(self.emit(op=OP_POOL_BWD, p0=s_i, p1=self.interior(rd(d)), q0=self.interior(wr(s)),
+                                         H=s_i.shape[0], W=s.W, cin=s.C, flags=flags))
             else:  # materialised relu
-                out.append(self._op(op=OP_RELU_BWD, p0=s.act, p1=rd(d), q0=wr(s), n=s.act.numel(),
-                                    flags=acc_flag(s)))
+                out.append(self.emit(op=OP_RELU_BWD, p0=s.act, p1=rd(d), q0=wr(s), n=s.act.numel(),
+                                     flags=acc_flag(s)))
             written.add(id(s))
         return out
 
 
-class Program:
-    """Owns a ``stv_program`` handle (host object inside libstv_hip.so)."""
+def operands(op_list: list[StvOp]) -> list:
+    """Everything the ops name by raw pointer: the tensors ``Schedule.emit`` recorded on them (and the host tap table
+    of a batched Gram op)."""
+    return [ref for o in op_list for ref in getattr(o, "refs", {}).values()]
 
-    def __init__(self, op_list: list[StvOp], keep: list) -> None:
-        self._keep = list(keep)
+
+class Program:
+    """Owns a ``stv_program`` handle (host object inside libstv_hip.so) and keeps its ops' operands alive."""
+
+    def __init__(self, op_list: list[StvOp], extra: tuple | list = ()) -> None:
+        """``extra``: what must outlive the program without being an operand of one of its ops (or the operands of
+        ops that were filled in by hand, without ``Schedule.emit``)."""
+        self._keep = operands(op_list) + list(extra)
         arr = (StvOp * len(op_list))(*op_list)
         handle = ctypes.c_void_p()
         lib = _lib.load()

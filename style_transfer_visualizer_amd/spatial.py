@@ -45,6 +45,95 @@ def strip_rows(H: int, rank: int, world: int) -> tuple[int, int, int, int]:
     return c0, c1, max(0, c0 - HALO_ROWS), min(H, c1 + HALO_ROWS)
 
 
+class _StripLossHead:
+    """The loss head of one row strip, in two phases around one all-reduce (the clamp of the Gram loss is non-linear,
+    so the sums must be global before it):
+
+    * ``phase1``: raw Gram sums ``F^T F`` and the content squared error over this rank's OWN rows;
+    * :meth:`reduce`: pack them, all-reduce (2.4 MB + a scalar per step), unpack the global sums;
+    * ``phase2``: clamp / loss / backward seeds from the GLOBAL sums, then the score combine.
+
+    Both phases are op lists of the strip's schedule; the shard decides which programs they run in.  ``content_coef``
+    is what ``Schedule.backward_ops`` takes as the content-gradient coefficient, one per content tap."""
+
+    def __init__(self, s: plan.Schedule, own, H: int, style_targets: list[torch.Tensor], style_w: float,
+                 content_w: float) -> None:
+        """``own(buf, k, t)``: this rank's rows of ``t``, a tensor laid out like the activation of ``buf``, whose
+        down-sampling factor is ``k``.  ``H``: rows of the whole image.  The content targets are already on the taps."""
+        dev = s.device
+        factor: dict[int, int] = {}      # down-sampling factor of every activation (doubles at each max-pool)
+        for nd in s.nodes:
+            k_src = 1 if nd.src is None else factor[id(nd.src)]
+            factor[id(nd.dst)] = k_src * 2 if nd.kind == "pool" else k_src
+        n_content = len(s.content_taps)
+        self.r_local = [torch.zeros(t.buf.C, t.buf.C, device=dev) for t in s.style_taps]
+        self.r_global = [torch.zeros_like(r) for r in self.r_local]
+        self.flat = torch.zeros(sum(r.numel() for r in self.r_local) + n_content, device=dev)
+        self.parts_c = torch.zeros(ops._lib.CONTENT_LOSS_PARTS * max(1, n_content), device=dev)
+        self.parts2 = torch.zeros(sum(ops.gram_loss_parts(t.buf.C) for t in s.style_taps) + max(1, n_content), device=dev)
+        self.losses = torch.zeros(max(len(self.r_local) + n_content, 1), device=dev)
+        self.scores = torch.zeros(4, device=dev)
+        self.phase1, self.phase2 = [], []
+        rows, scale, off = [], [], 0
+        for tap, r, rg in zip(s.style_taps, self.r_local, self.r_global, strict=True):
+            b, k = tap.buf, factor[id(tap.buf)]
+            mine = own(b, k, b.act)
+            n = mine.shape[0] * b.W
+            tap.partials = torch.empty(ops.gram_ksplit(n, b.C), b.C, b.C, device=dev)
+            tap.target = style_targets[tap.order]
+            tap.sgrad = torch.zeros(1, b.C, b.C, device=dev, dtype=s.dtype)
+            # finish in "raw" mode: no clamp, norm 1 -> the mirrored full matrix R
+            self.phase1 += [s.emit(op=plan.OP_GRAM_PARTIAL, p0=mine, q0=tap.partials, n=n, cin=b.C),
+                            s.emit(op=plan.OP_GRAM_FINISH, p0=tap.partials, q0=r, n=n, cin=b.C, f0=float("inf"), f1=1.0, f2=0.0)]
+            # n = 1 selects a single slab (ksplit = 1): `rg` already is the complete raw Gram
+            self.phase2.append(s.emit(op=plan.OP_GRAM_FINISH, p0=rg, p1=tap.target, q1=self.parts2[off:], q2=tap.sgrad, n=1,
+                                      cin=b.C, f0=plan.GRAM_CLAMP_MAX, f1=float(b.C * (H // k) * b.W), f2=style_w))
+            rows.append([off, ops.gram_loss_parts(b.C), 0])
+            scale.append(1.0 / float(b.C * b.C))
+            off += rows[-1][1]
+        self._content_slot = off
+        local_share = []
+        for i, tap in enumerate(s.content_taps):
+            b, k = tap.buf, factor[id(tap.buf)]
+            f, t = own(b, k, b.act), own(b, k, tap.target)
+            self.phase1.append(s.emit(op=plan.OP_CONTENT_LOSS, p0=f, p1=t, q0=self.parts_c[i * ops._lib.CONTENT_LOSS_PARTS:],
+                                      n=f.numel()))
+            n_global = (H // k) * b.W * b.C
+            rows.append([off, 1, 1])
+            scale.append(1.0 / float(n_global))
+            local_share.append(float(b.act.numel()) / float(n_global))
+            off += 1
+        self.table = torch.tensor(rows, dtype=torch.int32, device=dev).reshape(-1, 3)
+        self.scale = torch.tensor(scale, dtype=torch.float32, device=dev)
+        self.phase2.append(s.emit(op=plan.OP_LOSS_COMBINE, p0=self.parts2, p1=self.table, p2=self.scale, q0=self.losses,
+                                  q1=self.scores, cin=len(rows), f0=style_w, f1=content_w))
+        # The content-gradient op divides by ITS element count, the loss is normalised by the GLOBAL one.  The shares are
+        # handed out in the order the reverse schedule emits its content-gradient ops (the deepest tap first), as they
+        # always were; with one content tap, or content taps at one resolution, that is each tap's own share.
+        emitted = [t for nd in reversed(s.nodes) for t in nd.dst.taps if t.kind == "content"]
+        self.content_coef = [0.0] * n_content
+        for share, tap in zip(local_share, emitted, strict=True):
+            self.content_coef[tap.order] = content_w * share
+
+    def reduce(self, world: int, group=None) -> None:
+        """Between the phases: this rank's sums -> one flat buffer -> all-reduce -> the global sums phase two reads."""
+        n_r = 0
+        for r in self.r_local:
+            self.flat[n_r:n_r + r.numel()].copy_(r.reshape(-1))
+            n_r += r.numel()
+        n_c = len(self.content_coef)
+        if n_c:
+            self.flat[n_r:n_r + n_c].copy_(self.parts_c.reshape(n_c, -1).double().sum(1).float())
+        if world > 1:
+            dist.all_reduce(self.flat, group=group)      # RCCL over xGMI: 2.4 MB + a scalar per step, before the clamp
+        n_r = 0
+        for rg in self.r_global:
+            rg.copy_(self.flat[n_r:n_r + rg.numel()].reshape(rg.shape))
+            n_r += rg.numel()
+        if n_c:
+            self.parts2[self._content_slot:self._content_slot + n_c].copy_(self.flat[n_r:n_r + n_c])
+
+
 class SpatialShard:
     """This rank's share of one image: buffers, the two programs around the all-reduce, Adam state."""
 
@@ -64,88 +153,21 @@ class SpatialShard:
         self.x_ext = torch.zeros(1, 3, He, W, device=dev)
         self.g_ext = torch.zeros(1, 3, He, W, device=dev)
 
-        # down-sampling factor of every activation (doubles at each max-pool)
-        factor: dict[int, int] = {}
-        for nd in s.nodes:
-            k_src = 1 if nd.src is None else factor[id(nd.src)]
-            factor[id(nd.dst)] = k_src * 2 if nd.kind == "pool" else k_src
-        self._factor = factor
-
-        def core_rows(buf: plan.Buf) -> tuple[int, int]:
-            k = factor[id(buf)]
+        def core_rows(buf: plan.Buf, k: int, t: torch.Tensor) -> torch.Tensor:
             r0 = (self.c0 - self.e0) // k
             r1 = buf.H if self.c1 >= H else (self.c1 - self.e0) // k
-            return r0, r1
+            return t[r0:r1]
 
         # --- content targets: features of the content image on this extended strip ---
-        plan.Program(s.forward_ops(content_img[:, :, self.e0:self.e1].contiguous()), s._keep).run()
+        plan.Program(s.forward_ops(content_img[:, :, self.e0:self.e1].contiguous())).run()
         for tap in s.content_taps:
             tap.target = tap.buf.act.clone()
-        n_terms = len(s.style_taps) + len(s.content_taps)
-        self.r_local = [torch.zeros(t.buf.C, t.buf.C, device=dev) for t in s.style_taps]
-        self.flat = torch.zeros(sum(r.numel() for r in self.r_local) + len(s.content_taps), device=dev)
-        self.parts_c = torch.zeros(ops._lib.CONTENT_LOSS_PARTS * max(1, len(s.content_taps)), device=dev)
-        self.losses = torch.zeros(max(n_terms, 1), device=dev)
-        self.scores = torch.zeros(4, device=dev)
-
+        self.head = head = _StripLossHead(s, core_rows, H, style_targets, self.style_w, self.content_w)
+        self.losses, self.scores = head.losses, head.scores
         # --- program 1: forward, raw Gram sums and content squared error over CORE rows ---
-        p1 = s.forward_ops(self.x_ext)
-        self._views = []
-        for tap, r in zip(s.style_taps, self.r_local, strict=True):
-            r0, r1 = core_rows(tap.buf)
-            core = tap.buf.act[r0:r1]
-            n = (r1 - r0) * tap.buf.W
-            tap.partials = torch.empty(ops.gram_ksplit(n, tap.buf.C), tap.buf.C, tap.buf.C, device=dev)
-            p1.append(s._op(op=plan.OP_GRAM_PARTIAL, p0=core, q0=tap.partials, n=n, cin=tap.buf.C))
-            # finish in "raw" mode: no clamp, norm 1 -> the mirrored full matrix R
-            p1.append(s._op(op=plan.OP_GRAM_FINISH, p0=tap.partials, q0=r, n=n, cin=tap.buf.C, f0=float("inf"),
-                            f1=1.0, f2=0.0))
-            tap.target = style_targets[tap.order]
-            tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C, device=dev, dtype=dtype)
-        for i, tap in enumerate(s.content_taps):
-            r0, r1 = core_rows(tap.buf)
-            f, t = tap.buf.act[r0:r1], tap.target[r0:r1]
-            p1.append(s._op(op=plan.OP_CONTENT_LOSS, p0=f, p1=t,
-                            q0=self.parts_c[i * ops._lib.CONTENT_LOSS_PARTS:], n=f.numel()))
-        self.p1 = plan.Program(p1, s._keep)
-
+        self.p1 = plan.Program(s.forward_ops(self.x_ext) + head.phase1)
         # --- program 2: clamp/loss/seed from the GLOBAL R, score combine, backward over the strip ---
-        rows, scale = [], []
-        off = 0
-        self.r_global = [torch.zeros_like(r) for r in self.r_local]
-        self.parts2 = torch.zeros(sum(ops.gram_loss_parts(t.buf.C) for t in s.style_taps)
-                                  + max(1, len(s.content_taps)), device=dev)
-        p2 = []
-        for tap, rg in zip(s.style_taps, self.r_global, strict=True):
-            k = factor[id(tap.buf)]
-            n_global = (H // k) * tap.buf.W
-            cnt = ops.gram_loss_parts(tap.buf.C)
-            # n = 1 selects a single slab (ksplit = 1): `rg` already is the complete raw Gram
-            p2.append(s._op(op=plan.OP_GRAM_FINISH, p0=rg, p1=tap.target, q1=self.parts2[off:], q2=tap.sgrad, n=1,
-                            cin=tap.buf.C, f0=plan.GRAM_CLAMP_MAX, f1=float(tap.buf.C * n_global), f2=self.style_w))
-            rows.append([off, cnt, 0])
-            scale.append(1.0 / float(tap.buf.C * tap.buf.C))
-            off += cnt
-        self._content_slot = off
-        self._content_scale = []
-        for tap in s.content_taps:
-            k = factor[id(tap.buf)]
-            n_global = (H // k) * tap.buf.W * tap.buf.C
-            rows.append([off, 1, 1])
-            scale.append(1.0 / float(n_global))
-            self._content_scale.append(float(tap.buf.act.numel()) / float(n_global))
-            off += 1
-        self.table = torch.tensor(rows, dtype=torch.int32, device=dev).reshape(-1, 3)
-        self.scale = torch.tensor(scale, dtype=torch.float32, device=dev)
-        p2.append(s._op(op=plan.OP_LOSS_COMBINE, p0=self.parts2, p1=self.table, p2=self.scale, q0=self.losses,
-                        q1=self.scores, cin=n_terms, f0=self.style_w, f1=self.content_w))
-        bwd = s.backward_ops(self.g_ext, content_coef=self.content_w, coef_dev=None)
-        ci = 0
-        for o in bwd:     # content gradient is normalised by the GLOBAL element count
-            if o.op == plan.OP_CONTENT_GRAD:
-                o.f0 = self.content_w * self._content_scale[min(ci, len(self._content_scale) - 1)]
-                ci += 1
-        self.p2 = plan.Program(p2 + bwd, s._keep)
+        self.p2 = plan.Program(head.phase2 + s.backward_ops(self.g_ext, content_coef=head.content_coef, coef_dev=None))
 
         # --- this rank's shard of the image and its Adam state ---
         self.x_core = torch.zeros(1, 3, self.c1 - self.c0, W, device=dev, requires_grad=True)
@@ -157,21 +179,7 @@ class SpatialShard:
         """Scores [style, content, total] for the whole image; d(total)/dx of the core rows in g_core."""
         self.x_ext.copy_(x_full[:, :, self.e0:self.e1])
         self.p1.run()
-        n_r = 0
-        for r in self.r_local:
-            self.flat[n_r:n_r + r.numel()].copy_(r.reshape(-1))
-            n_r += r.numel()
-        n_c = len(self.sched.content_taps)
-        if n_c:
-            self.flat[n_r:n_r + n_c].copy_(self.parts_c.reshape(n_c, -1).double().sum(1).float())
-        if self.world > 1:
-            dist.all_reduce(self.flat)                   # RCCL over xGMI: 2.4 MB + a scalar per step
-        n_r = 0
-        for rg in self.r_global:
-            rg.copy_(self.flat[n_r:n_r + rg.numel()].reshape(rg.shape))
-            n_r += rg.numel()
-        if n_c:
-            self.parts2[self._content_slot:self._content_slot + n_c].copy_(self.flat[n_r:n_r + n_c])
+        self.head.reduce(self.world)
         self.p2.run()
         self.g_core.copy_(self.g_ext[:, :, self.c0 - self.e0:self.c1 - self.e0])
         return self.scores[:3].clone()
@@ -271,18 +279,6 @@ class HaloShard:
         self.x_ext = torch.zeros(1, 3, rows + 2, W, device=dev)
         self.g_ext = torch.zeros(1, 3, rows + 2, W, device=dev)
         self._row_stage = torch.zeros(2, 3, W, device=dev)
-        factor: dict[int, int] = {}
-        for nd in s.nodes:
-            k_src = 1 if nd.src is None else factor[id(nd.src)]
-            factor[id(nd.dst)] = k_src * 2 if nd.kind == "pool" else k_src
-        # buffers by address: an op names its operands by raw pointer
-        self._by_ptr = {self.x_ext.data_ptr(): self.x_ext}
-        for nd in s.nodes:
-            self._by_ptr[nd.dst.act.data_ptr()] = nd.dst.act
-        s.alloc_grads()
-        for nd in s.nodes:
-            self._by_ptr[nd.dst.grad.data_ptr()] = nd.dst.grad
-
         # --- content targets: this strip's features of the content image -----------------------
         self.x_ext[:, :, 1:-1].copy_(content_img[:, :, self.c0:self.c1])
         self._fwd = self._segments(s.forward_ops(self.x_ext), forward=True)
@@ -290,66 +286,13 @@ class HaloShard:
         for tap in s.content_taps:
             tap.target = tap.buf.act.clone()
 
-        # --- program 1b: raw Gram sums and content squared error over this rank's own rows --------
-        n_terms = len(s.style_taps) + len(s.content_taps)
-        self.r_local = [torch.zeros(t.buf.C, t.buf.C, device=dev) for t in s.style_taps]
-        self.flat = torch.zeros(sum(r.numel() for r in self.r_local) + len(s.content_taps), device=dev)
-        self.parts_c = torch.zeros(ops._lib.CONTENT_LOSS_PARTS * max(1, len(s.content_taps)), device=dev)
-        self.losses = torch.zeros(max(n_terms, 1), device=dev)
-        self.scores = torch.zeros(4, device=dev)
-        p1 = []
-        for tap, r in zip(s.style_taps, self.r_local, strict=True):
-            own = s.interior(tap.buf.act)
-            n = own.shape[0] * tap.buf.W
-            tap.partials = torch.empty(ops.gram_ksplit(n, tap.buf.C), tap.buf.C, tap.buf.C, device=dev)
-            p1.append(s._op(op=plan.OP_GRAM_PARTIAL, p0=own, q0=tap.partials, n=n, cin=tap.buf.C))
-            p1.append(s._op(op=plan.OP_GRAM_FINISH, p0=tap.partials, q0=r, n=n, cin=tap.buf.C, f0=float("inf"),
-                            f1=1.0, f2=0.0))            # "raw" finish: no clamp, norm 1 -> the mirrored R
-            tap.target = style_targets[tap.order]
-            tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C, device=dev, dtype=dtype)
-        for i, tap in enumerate(s.content_taps):
-            f, t = s.interior(tap.buf.act), s.interior(tap.target)
-            p1.append(s._op(op=plan.OP_CONTENT_LOSS, p0=f, p1=t,
-                            q0=self.parts_c[i * ops._lib.CONTENT_LOSS_PARTS:], n=f.numel()))
-        self.p1 = plan.Program(p1, s._keep)
-
-        # --- program 2: clamp / loss / seeds from the GLOBAL sums, score combine ---------------------
-        rows_tab, scale = [], []
-        off = 0
-        self.r_global = [torch.zeros_like(r) for r in self.r_local]
-        self.parts2 = torch.zeros(sum(ops.gram_loss_parts(t.buf.C) for t in s.style_taps)
-                                  + max(1, len(s.content_taps)), device=dev)
-        p2 = []
-        for tap, rg in zip(s.style_taps, self.r_global, strict=True):
-            k = factor[id(tap.buf)]
-            n_global = (H // k) * tap.buf.W
-            cnt = ops.gram_loss_parts(tap.buf.C)
-            p2.append(s._op(op=plan.OP_GRAM_FINISH, p0=rg, p1=tap.target, q1=self.parts2[off:], q2=tap.sgrad, n=1,
-                            cin=tap.buf.C, f0=plan.GRAM_CLAMP_MAX, f1=float(tap.buf.C * n_global), f2=self.style_w))
-            rows_tab.append([off, cnt, 0])
-            scale.append(1.0 / float(tap.buf.C * tap.buf.C))
-            off += cnt
-        self._content_slot = off
-        content_scale = []
-        for tap in s.content_taps:
-            k = factor[id(tap.buf)]
-            n_global = (H // k) * tap.buf.W * tap.buf.C
-            rows_tab.append([off, 1, 1])
-            scale.append(1.0 / float(n_global))
-            content_scale.append(float(tap.buf.act.numel()) / float(n_global))   # the op divides by ITS element count
-            off += 1
-        self.table = torch.tensor(rows_tab, dtype=torch.int32, device=dev).reshape(-1, 3)
-        self.scale = torch.tensor(scale, dtype=torch.float32, device=dev)
-        p2.append(s._op(op=plan.OP_LOSS_COMBINE, p0=self.parts2, p1=self.table, p2=self.scale, q0=self.losses,
-                        q1=self.scores, cin=n_terms, f0=self.style_w, f1=self.content_w))
-        self.p2 = plan.Program(p2, s._keep)
-        bwd = s.backward_ops(self.g_ext, content_coef=self.content_w, coef_dev=None)
-        ci = 0
-        for o in bwd:
-            if o.op == plan.OP_CONTENT_GRAD:
-                o.f0 = self.content_w * content_scale[min(ci, len(content_scale) - 1)]
-                ci += 1
-        self._bwd = self._segments(bwd, forward=False)
+        # --- program 1b: raw Gram sums and content squared error over this rank's own rows; program 2: clamp / loss /
+        # seeds from the GLOBAL sums, score combine -------------------------------------------------------------------
+        self.head = head = _StripLossHead(s, lambda buf, k, t: s.interior(t), H, style_targets, self.style_w, self.content_w)
+        self.losses, self.scores = head.losses, head.scores
+        self.p1 = plan.Program(head.phase1)
+        self.p2 = plan.Program(head.phase2)
+        self._bwd = self._segments(s.backward_ops(self.g_ext, content_coef=head.content_coef, coef_dev=None), forward=False)
 
         self.x_core = torch.zeros(1, 3, rows, W, device=dev, requires_grad=True)
         self.g_core = torch.zeros(1, 3, rows, W, device=dev)
@@ -366,11 +309,11 @@ class HaloShard:
             needs = (o.op == plan.OP_CONV and o.taps == 9) or o.op in conv_ops
             if needs:
                 if cur:
-                    segs.append((cur_ex, plan.Program(cur, self.sched._keep)))
-                cur, cur_ex = [], self._by_ptr[int(o.p0)]
+                    segs.append((cur_ex, plan.Program(cur)))
+                cur, cur_ex = [], o.refs["p0"]
             cur.append(o)
         if cur:
-            segs.append((cur_ex, plan.Program(cur, self.sched._keep)))
+            segs.append((cur_ex, plan.Program(cur)))
         return segs
 
     def _run(self, segs: list) -> None:
@@ -485,21 +428,7 @@ class HaloShard:
         self.x_ext[:, :, 1:-1].copy_(self.x_core.detach())
         self._run(self._fwd)
         self.p1.run()
-        n_r = 0
-        for r in self.r_local:
-            self.flat[n_r:n_r + r.numel()].copy_(r.reshape(-1))
-            n_r += r.numel()
-        n_c = len(self.sched.content_taps)
-        if n_c:
-            self.flat[n_r:n_r + n_c].copy_(self.parts_c.reshape(n_c, -1).double().sum(1).float())
-        if self.world > 1:
-            dist.all_reduce(self.flat, group=self.group)      # 2.4 MB + a scalar per step, before the clamp
-        n_r = 0
-        for rg in self.r_global:
-            rg.copy_(self.flat[n_r:n_r + rg.numel()].reshape(rg.shape))
-            n_r += rg.numel()
-        if n_c:
-            self.parts2[self._content_slot:self._content_slot + n_c].copy_(self.flat[n_r:n_r + n_c])
+        self.head.reduce(self.world, self.group)
         self.p2.run()
         self._run(self._bwd)
         self.g_core.copy_(self.g_ext[:, :, 1:-1])

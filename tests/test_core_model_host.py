@@ -510,3 +510,172 @@ def test_switches_are_read_when_the_schedule_is_constructed(monkeypatch):
     assert len(before[0]) == 13
     fresh = [o.op for o in _fwd(_device_form(torch.bfloat16, 64, 64, *DEFAULT_TAPS))]
     assert len(fresh) == 17 and fresh.count(_lib.OP_POOL_FWD) == 4
+
+
+# ------------------------------------------------------------------ the whole step, in device form, on host tensors
+class RecordedProgram:
+    """Stands in for ``plan.Program`` under a host engine: keeps the op list it is given and runs nothing."""
+
+    def __init__(self, op_list, extra=()):
+        self.op_list = list(op_list)
+
+    def run(self, use_graph=False):
+        pass
+
+
+def host_engine(monkeypatch, dtype, H, W, style_at, content_at, **env):
+    """An engine in device form on host tensors whose programs only record their ops; ``env``: the step's switches."""
+    for name in ("STV_LOSS_BATCH", "STV_GRAM_FIN_LATE", "STV_LOSS_INTERLEAVE", "STV_FUSE_CONTENT"):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    monkeypatch.setattr(plan, "Program", RecordedProgram)
+    eng = core_model._Engine(_layers(), style_at, content_at, H, W, dtype, CPU, assume_device=True)
+    for tap in eng.sched.style_taps:
+        tap.target = torch.zeros(tap.buf.C, tap.buf.C)
+    for tap in eng.sched.content_taps:
+        tap.target = torch.empty_like(tap.buf.act)
+    return eng
+
+
+def fused_step(eng, x, grad):
+    """The op list of the fused step as the engine caches it."""
+    eng.loss_and_grad(x, grad, 1e5, 1.0)
+    (prog,) = [p for key, p in eng._programs.items() if key[0] == "fused" and key[-1] is None]
+    return prog.op_list
+
+
+_POINTERS = ("p0", "p1", "p2", "p3", "q0", "q1", "q2", "q3")
+_TAP_POINTERS = ("F", "partials", "target", "gram_out", "loss_part", "sgrad", "coef_dev")
+_TAP_VALUES = ("n_pixels", "channels", "clamp_max", "norm", "coef")
+
+
+def step_signature(op_list, canonical=True):
+    """Every field of every op.  ``canonical``: addresses numbered in the order of their first appearance (what two
+    builds on different buffers share); else the raw addresses.  The tap table of a batched Gram op - a host array that
+    every build allocates anew - is expanded entry by entry in place of its address."""
+    seen: dict[int, int] = {}
+
+    def ptr(v):
+        if not v or not canonical:
+            return v
+        return seen.setdefault(int(v), len(seen))
+    out = []
+    for o in op_list:
+        sig = [getattr(o, k) for k in ("op", "dtype", "flags", "taps", "H", "W", "cin", "cout", "n", "f0", "f1", "f2", "f3")]
+        if o.op == _lib.OP_GRAM_MULTI:
+            table = o.refs["p0"]
+            assert len(table) == o.n and not any(getattr(o, k) for k in _POINTERS[1:])
+            sig += [tuple(ptr(getattr(e, k)) for k in _TAP_POINTERS) + tuple(getattr(e, k) for k in _TAP_VALUES) for e in table]
+        else:
+            sig += [ptr(getattr(o, k)) for k in _POINTERS]
+        out.append(tuple(sig))
+    return out
+
+
+def _loss_head_census(eng):
+    names = {_lib.OP_CONV_FIRST_FWD: "CONV_FIRST_FWD", _lib.OP_CONV: "CONV", _lib.OP_POOL_FWD: "POOL_FWD",
+             _lib.OP_GRAM_PARTIAL: "GRAM_PARTIAL", _lib.OP_GRAM_FINISH: "GRAM_FINISH", _lib.OP_GRAM_MULTI: "GRAM_MULTI",
+             _lib.OP_CONTENT_LOSS: "CONTENT_LOSS"}
+    H, W = eng.H, eng.W
+    op_list = fused_step(eng, _image(H, W, "x"), _image(H, W, "x.grad"))
+    out = []
+    for o in op_list:
+        if o.op == _lib.OP_LOSS_COMBINE:
+            break
+        name = names[o.op]
+        if o.op == _lib.OP_GRAM_MULTI:
+            name += "[" + ",".join("F" if e.F else "-" for e in o.refs["p0"]) + "]"
+        if o.op == _lib.OP_CONTENT_LOSS and o.q1:
+            name += "+grad"
+        out.append(name)
+    return out
+
+
+_PAIR = ["GRAM_PARTIAL", "GRAM_FINISH"]
+_GRAD = ["CONTENT_LOSS+grad"]
+
+
+@pytest.mark.parametrize("dtype,size,taps,env,want", [
+    (torch.bfloat16, 64, DEFAULT_TAPS, {},
+     ["CONV_FIRST_FWD"] + ["CONV"] * 12 + ["GRAM_MULTI[F,F,F,F,F]"] + _GRAD),
+    # 448^2 in fp32: the smallest square where conv1_1's map (51.4 MB) exceeds the 48 MiB limit and conv2_1's does not
+    (torch.float32, 448, DEFAULT_TAPS, {},
+     ["CONV_FIRST_FWD", "GRAM_PARTIAL"] + ["CONV"] * 9 + _GRAD + ["CONV"] * 3 + ["GRAM_MULTI[-,F,F,F,F]"]),
+    (torch.float32, 448, DEFAULT_TAPS, {"STV_GRAM_FIN_LATE": "0"},
+     ["CONV_FIRST_FWD"] + _PAIR + ["CONV"] * 9 + _GRAD + ["CONV"] * 3 + ["GRAM_MULTI[F,F,F,F]"]),
+    (torch.float32, 448, DEFAULT_TAPS, {"STV_LOSS_BATCH": "0"},
+     ["CONV_FIRST_FWD"] + _PAIR + ["CONV"] * 2 + _PAIR + ["CONV"] * 2 + _PAIR + ["CONV"] * 4 + _PAIR + ["CONV"] + _GRAD
+     + ["CONV"] * 3 + _PAIR),
+    (torch.float32, 448, DEFAULT_TAPS, {"STV_LOSS_BATCH": "1"},
+     ["CONV_FIRST_FWD"] + ["CONV"] * 12 + ["GRAM_MULTI[F,F,F,F,F]"] + _GRAD),
+    (torch.float32, 448, DEFAULT_TAPS, {"STV_LOSS_INTERLEAVE": "0"},
+     ["CONV_FIRST_FWD"] + ["CONV"] * 12 + ["GRAM_PARTIAL"] + _GRAD + ["GRAM_MULTI[-,F,F,F,F]"]),
+    (torch.bfloat16, 64, ([28], [0, 21]), {},          # a single style tap is not batched
+     ["CONV_FIRST_FWD"] + _GRAD + ["CONV"] * 9 + _GRAD + ["CONV"] * 3 + _PAIR),
+    (torch.bfloat16, 64, ([0, 5], [5, 21]), {"STV_FUSE_CONTENT": "0"},
+     ["CONV_FIRST_FWD"] + ["CONV"] * 9 + ["GRAM_MULTI[F,F]", "CONTENT_LOSS", "CONTENT_LOSS"]),
+])
+def test_loss_head_placement(monkeypatch, dtype, size, taps, env, want):
+    """Where ``Schedule._decide`` puts the loss-side ops of the step: behind their producers, or in the batched tail
+    (``F``: the batched launch reads the activation, ``-``: only the slabs a pass behind the producer left; ``+grad``:
+    the content pass also writes the gradient).  The host tensors of the large case are never touched."""
+    assert _loss_head_census(host_engine(monkeypatch, dtype, size, size, *taps, **env)) == want
+
+
+def test_whole_step_does_not_depend_on_build_order(monkeypatch):
+    """The fused step - forward with losses, combine, backward - built twice, and built before or after the program
+    of ``forward_losses``, is the same op list, pointers included."""
+    a = host_engine(monkeypatch, torch.bfloat16, 64, 64, *DEFAULT_TAPS)
+    b = host_engine(monkeypatch, torch.bfloat16, 64, 64, *DEFAULT_TAPS)
+    x, grad = _image(64, 64, "x"), _image(64, 64, "x.grad")
+    first = step_signature(fused_step(a, x, grad), canonical=False)
+    a.forward_losses(x)
+    a.backward_from(torch.ones(6), grad)
+    fwd_a = step_signature(a._programs[("fwd", x.data_ptr())].op_list, canonical=False)
+    for key in [k for k in a._programs if k[0] == "fused"]:
+        del a._programs[key]
+    assert step_signature(fused_step(a, x, grad), canonical=False) == first
+    ops_ = [sig[0] for sig in first]
+    assert _lib.OP_GRAM_MULTI in ops_ and _lib.OP_LOSS_COMBINE in ops_ and ops_[-1] == _lib.OP_CONV_FIRST_DGRAD
+    b.forward_losses(x)                      # the other engine: forward_losses first
+    assert step_signature(b._programs[("fwd", x.data_ptr())].op_list) == step_signature(a._programs[("fwd", x.data_ptr())].op_list)
+    assert step_signature(fused_step(b, x, grad)) == step_signature(fused_step(a, x, grad))
+    assert step_signature(a._programs[("fwd", x.data_ptr())].op_list, canonical=False) == fwd_a
+
+
+def test_ops_own_their_operands():
+    """An op holds what it names by raw pointer, a program holds what its ops hold, and the schedule holds nothing:
+    an image dies with the op list built on it."""
+    import ctypes
+    import gc
+    import weakref
+    s = _device_form(torch.bfloat16, 64, 64, *DEFAULT_TAPS)
+    x = torch.zeros(1, 3, 64, 64)
+    alive = weakref.ref(x)
+    op_list = s.forward_ops(x)
+    kept = plan.operands(op_list)
+    for t in [x] + [nd.dst.act for nd in s.nodes if nd.dst.stored] + [nd.wf for nd in s.nodes if nd.wf is not None]:
+        assert any(t is k for k in kept)
+    del kept, x
+    gc.collect()
+    assert alive() is not None               # the op list keeps the image ...
+    del op_list
+    gc.collect()
+    assert alive() is None                   # ... and nothing else does
+
+    def batched():
+        return s.gram_multi_op([dict(tap=tap) for tap in s.style_taps])
+    multi = batched()
+    kept = plan.operands([multi])
+    table = [k for k in kept if isinstance(k, ctypes.Array)]
+    assert len(table) == 1 and ctypes.addressof(table[0]) == multi.p0 and len(table[0]) == len(s.style_taps)
+    assert all(any(tap.buf.act is k for k in kept) and any(tap.partials is k for k in kept) for tap in s.style_taps)
+
+    def sizes():
+        return {k: len(v) for k, v in vars(s).items() if isinstance(v, (list, dict, set, tuple))}
+    _fwd(s), _bwd(s), batched()
+    after_one = sizes()
+    for _ in range(10):
+        _fwd(s), _bwd(s), batched()
+    assert sizes() == after_one and not hasattr(s, "_keep")      # nothing on the schedule grows with the builds

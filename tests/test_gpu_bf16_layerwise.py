@@ -154,7 +154,7 @@ def test_bf16_every_stored_tensor_within_one_ulp_of_the_oracle_op(size, monkeypa
         g = None
         # content taps whose gradient the forward half already wrote (stv_content_loss_grad): rounded first, and
         # whatever produces this buffer's gradient accumulates onto the rounded value
-        pre = [t for t in b.taps if t.kind == "content" and eng._content_fused(t)]
+        pre = [t for t in b.taps if t.kind == "content" and t.grad_fused]
         pre_sum = sum((_bf(tap_term(t)) for t in pre), torch.zeros(())) if pre else None
         if consumer is not None:
             dy = _nchw(consumer.dst.grad)

@@ -628,3 +628,42 @@ def test_device_form_matches_the_device(monkeypatch):
         sigs.append([(o.op, o.dtype, o.flags, o.taps, o.H, o.W, o.cin, o.cout, o.n) for o in op_list])
         assert s.style_taps[0].partials_fused and s._grad_slabs.shape[0] == 2
     assert sigs[0] == sigs[1] and len(sigs[0]) == 13 + 15
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_device_form_of_the_whole_step_matches_the_device(monkeypatch, dtype):
+    """The same for the whole fused step (forward with the loss head where ``Schedule._decide`` places it, combine,
+    backward): the program an engine on the device caches under "fused" and runs is, field by field, the one a host
+    engine builds in device form - addresses numbered by first appearance, the tap table of the batched Gram launch
+    compared entry by entry.  The one operand a host schedule cannot have, the first layer's kernel-side weight packing
+    (made by a kernel), gets a stand-in there so that every address the device's ops name has a counterpart."""
+    from style_transfer_visualizer_amd import _lib, plan
+    from tests.test_core_model_host import fused_step, host_engine, step_signature
+
+    class Recording(plan.Program):
+        def __init__(self, op_list, extra=()):
+            self.op_list = list(op_list)
+            super().__init__(op_list, extra)
+    host = host_engine(monkeypatch, dtype, 64, 64, [0, 5, 10, 19, 28], [21])      # (also: the step's switches at their defaults)
+    host.sched.nodes[0].wb = torch.empty(1)
+    xh = torch.zeros(1, 3, 64, 64)
+    on_host = fused_step(host, xh, torch.zeros_like(xh))
+    layers = list(core_model.build_vgg_features().eval().children())
+    monkeypatch.setattr(plan, "Program", Recording)
+    eng = core_model._Engine(layers, [0, 5, 10, 19, 28], [21], 64, 64, dtype, DEV)
+    assert eng.sched.device_form
+    for tap in eng.sched.style_taps:
+        tap.target = torch.zeros(tap.buf.C, tap.buf.C, device=DEV)
+    for tap in eng.sched.content_taps:
+        tap.target = torch.zeros_like(tap.buf.act)
+    x = torch.zeros(1, 3, 64, 64, device=DEV)
+    on_device = fused_step(eng, x, torch.zeros_like(x))
+    torch.cuda.synchronize()
+    prog = next(p for key, p in eng._programs.items() if key[0] == "fused")
+    assert prog.op_meta == [(o.op, o.H, o.W, o.cin, o.cout, o.taps, o.n) for o in on_device]      # what it ran
+    got, want = step_signature(on_device), step_signature(on_host)
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g == w, f"op {k}: device {g} != host form {w}"
+    assert sum(o.op == _lib.OP_GRAM_MULTI for o in on_device) == 1
+    assert torch.isfinite(eng.scores).all()
