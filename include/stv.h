@@ -272,6 +272,18 @@ int stv_content_loss_grad(const void* F, const void* target, float* loss_part, v
 int stv_content_grad(const void* F, const void* target, void* dF, size_t n, float coef,
                      const float* coef_dev, int flags, int dtype, void* stream);
 
+/* ---- Total variation of the image (no counterpart in the reference).  Since version 105.
+ *      TV(x) = ( sum_{c,y<H-1,x} (x[c,y+1,x] - x[c,y,x])^2 + sum_{c,y,x<W-1} (x[c,y,x+1] - x[c,y,x])^2 ) / (C*H*W);
+ *      differences never cross a row end or a channel plane. ---------------------------------------------------- */
+#define STV_TV_LOSS_PARTS 256
+/* x NCHW fp32 [C][H][W].  loss_part (optional): STV_TV_LOSS_PARTS raw partial sums of the squared forward
+ * differences (unscaled; stv_loss_combine applies the scale), one per workgroup, fixed order, every entry written.
+ * dx (optional): dx (=|+=, STV_ACCUM) coef * sum over the existing 4-neighbours n of (x - n), the differences added in
+ * the order up, down, left, right; the product is rounded before it is added to dx (accumulate == write, then an fp32
+ * add).  At least one of the two is non-NULL.  x != dx.  STV_ERR_ARG: null x, both outputs null, a non-positive
+ * dimension, C*H*W*4 >= 2 GiB, a flag other than STV_ACCUM. */
+int stv_tv(const float* x_nchw, float* loss_part, float* dx_nchw, int C, int H, int W, float coef, int flags, void* stream);
+
 /* ---- Frame / PNG export: prepare_image_for_output (image_io.py:129-152: denormalise,
  *      nan_to_num(nan=0, posinf=1, neginf=0), clamp 0..1) fused with the uint8 conversion, on the
  *      device, so only H*W*3 bytes cross to the host.  x NCHW fp32 [3][H][W] -> out HWC uint8.
@@ -284,9 +296,12 @@ int stv_image_to_u8(const float* x_nchw, uint8_t* out_hwc, int H, int W, const f
 
 /* ---- Score combine: torch.stack(losses).sum() and
  *      loss = style_w*style + content_w*content (optimization.py:298-312).
- *  table: int32 [n_terms][3] = {offset into parts, count, kind(0 style,1 content)}
+ *  table: int32 [n_terms][3] = {offset into parts, count, kind(0 style,1 content,2 extra)}
  *  scale: fp32 [n_terms] (1/C^2 for style, 1/n for content)
  *  losses: fp32 [n_terms]; scores: fp32 [4] = {style, content, total, finite_flag}
+ *  kind 2 (since version 105): a term that belongs to neither score - the total-variation term, whose weight the host
+ *  folds into its scale, fp32(tv_w / (C*H*W)).  After total = style_w*style + content_w*content is formed as before,
+ *  the kind-2 terms are added to it in index order, one fp32 add each; losses[k] is the weighted term.
  *  n_terms <= 64 (STV_ERR_ARG beyond). */
 int stv_loss_combine(const float* parts, const int32_t* table, const float* scale,
                      int n_terms, float style_w, float content_w, float* losses,
@@ -367,7 +382,7 @@ enum {
   STV_OP_CONV_FIRST_FWD = 1, STV_OP_CONV_FIRST_DGRAD, STV_OP_CONV, STV_OP_POOL_FWD,
   STV_OP_POOL_BWD, STV_OP_RELU_FWD, STV_OP_RELU_BWD, STV_OP_GRAM_PARTIAL,
   STV_OP_GRAM_FINISH, STV_OP_CONTENT_LOSS, STV_OP_CONTENT_GRAD, STV_OP_LOSS_COMBINE,
-  STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER
+  STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER, STV_OP_TV
 };
 /* Operands follow the direct entry points' argument order (inputs p0.., outputs q0..).
  * CONV_FIRST_FWD takes the optional stv_conv_first_pack buffer in p3 (and, with q1 set, runs
@@ -383,7 +398,8 @@ enum {
  * then one replayed hipGraph - the reference's optimizer.step(closure), optimization.py:186, without a graph boundary
  * between the two.
  * LBFGS_ITER runs stv_lbfgsc_iter in the same place with the same operands, plus p1 = loss (device fp32 scalar: the
- * total score LOSS_COMBINE wrote) and taps = iters_per_step: the one program replays for every iteration of every step. */
+ * total score LOSS_COMBINE wrote) and taps = iters_per_step: the one program replays for every iteration of every step.
+ * TV (since version 105) runs stv_tv: p0 = x, q0 = loss_part, q1 = dx, cin = C, H, W, f0 = coef, flags. */
 typedef struct {
   int32_t op, dtype, flags, taps;
   int32_t H, W, cin, cout;

@@ -18,9 +18,14 @@ RELU_IN, RELU_OUT, MASK, ACCUM, W_BLOCKED, POOL_IDX, POOL_ROUTE, POOL_ONLY = 1, 
 
 (OP_CONV_FIRST_FWD, OP_CONV_FIRST_DGRAD, OP_CONV, OP_POOL_FWD, OP_POOL_BWD, OP_RELU_FWD,
  OP_RELU_BWD, OP_GRAM_PARTIAL, OP_GRAM_FINISH, OP_CONTENT_LOSS, OP_CONTENT_GRAD,
- OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER) = range(1, 17)
+ OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER, OP_TV) = range(1, 18)
 
 CONTENT_LOSS_PARTS = 256
+TV_LOSS_PARTS = 256       # stv.h STV_TV_LOSS_PARTS: one loss partial per workgroup of stv_tv, which is also its grid cap
+# launch constants of stv_tv (csrc/pointwise.hip: kTvThreads, pixels per work item): a work item is TV_VEC consecutive
+# pixels of one row, a pass of the capped grid covers TV_LOSS_PARTS * TV_THREADS items
+TV_THREADS, TV_VEC = 1024, 4
+KIND_STYLE, KIND_CONTENT, KIND_EXTRA = 0, 1, 2      # third column of the combine table
 
 _ERRORS = {1: "STV_ERR_ARG (unsupported shape / null pointer / dtype)",
            2: "STV_ERR_LAUNCH (HIP launch failed)", 3: "STV_ERR_ALLOC", 4: "STV_ERR_GRAPH"}
@@ -88,6 +93,7 @@ SIGNATURES = {
     "stv_content_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "stv_content_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_int, c_void_p]),
     "stv_content_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_int, c_int, c_void_p]),
+    "stv_tv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "stv_image_to_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_void_p]),
     "stv_loss_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "stv_loss_combine_log": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,

@@ -1,7 +1,7 @@
 """``style-visualizer`` command line: same flags and override rules as reference cli.py:26-354.
 
 Options that only have meaning for presentation features outside this build (comparison grids)
-are accepted and reported as unavailable.  One addition: ``--precision {fp32,bf16,bf16x3}``.
+are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,bf16x3}``, ``--tv-w``.
 """
 from __future__ import annotations
 
@@ -39,6 +39,7 @@ def build_arg_parser() -> argparse.ArgumentParser:
     opt.add_argument("--steps", type=int, default=S, help="Number of optimization steps")
     opt.add_argument("--style-w", type=float, default=S, help="Style weight")
     opt.add_argument("--content-w", type=float, default=S, help="Content weight")
+    opt.add_argument("--tv-w", type=float, default=S, help="Total-variation weight (0 = off, the default)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
     opt.add_argument("--init-method", choices=["random", "white", "content"], default=S, help="Initialization method")
     opt.add_argument("--seed", type=int, default=S, help="Random seed")
@@ -102,6 +103,9 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
         ("Loss Plotting", on(cfg.output.plot_losses)), ("Random Seed", o.seed),
         ("Device", cfg.hardware.device), ("Precision", cfg.hardware.precision),
     ]
+    if o.tv_w > 0:
+        rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Content Weight") + 1,
+                    ("Total Variation Weight", f"{o.tv_w:g}"))
     for label, value in rows:
         logger.info("%s: %s", label, value)
 

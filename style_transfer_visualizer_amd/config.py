@@ -1,8 +1,9 @@
 """Configuration schema, TOML loader and CLI override rules.
 
 Field names, bounds and override precedence follow reference config.py:53-309
-so existing ``config.toml`` files and CLI invocations keep working.  The one
-addition is ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf16x3" fp32 storage, split-bf16 products).
+so existing ``config.toml`` files and CLI invocations keep working.  The
+additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf16x3" fp32 storage, split-bf16 products)
+and ``optimization.tv_w`` (weight of the total-variation regulariser, 0 = off).
 """
 from __future__ import annotations
 
@@ -24,6 +25,7 @@ class OptimizationConfig(BaseModel):
     steps: int = Field(d.DEFAULT_STEPS, ge=1)
     style_w: float = Field(d.DEFAULT_STYLE_WEIGHT, ge=0)
     content_w: float = Field(d.DEFAULT_CONTENT_WEIGHT, ge=0)
+    tv_w: float = Field(d.DEFAULT_TV_WEIGHT, ge=0)
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
     seed: int = Field(d.DEFAULT_SEED, ge=0)
@@ -117,7 +119,7 @@ def parse_int_list(value: str | list[int]) -> list[int]:
 _DIRECT = {
     "output": ("output", "output"), "log_every": ("output", "log_every"), "log_loss": ("output", "log_loss"),
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
-    "content_w": ("optimization", "content_w"), "lr": ("optimization", "lr"),
+    "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lr": ("optimization", "lr"),
     "init_method": ("optimization", "init_method"), "seed": ("optimization", "seed"),
     "save_every": ("video", "save_every"), "fps": ("video", "fps"), "quality": ("video", "quality"),
     "metadata_title": ("video", "metadata_title"), "metadata_artist": ("video", "metadata_artist"),

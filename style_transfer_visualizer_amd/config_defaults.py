@@ -5,6 +5,7 @@ from __future__ import annotations
 DEFAULT_STEPS = 1500
 DEFAULT_STYLE_WEIGHT = 1e5
 DEFAULT_CONTENT_WEIGHT = 1.0
+DEFAULT_TV_WEIGHT = 0.0      # build-specific: weight of the total-variation regulariser (0 = off)
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"
 DEFAULT_SEED = 0

@@ -118,6 +118,38 @@ def gram_matrix(tensor: torch.Tensor, clamp_max: float = GRAM_MATRIX_CLAMP_MAX) 
     return _GramFn.apply(tensor, float(clamp_max))
 
 
+# ---------------------------------------------------------------- total variation
+def total_variation(x: torch.Tensor) -> torch.Tensor:
+    """Total variation of an image ``[1, C, H, W]`` (or ``[C, H, W]``), differentiable, on any device:
+
+        TV(x) = ( sum (x[c,y+1,x] - x[c,y,x])^2 + sum (x[c,y,x+1] - x[c,y,x])^2 ) / (C*H*W)
+
+    Differences never cross a row end or a channel plane; ``H = 1`` / ``W = 1`` have none in that direction.  The
+    fused step forms ``tv_w * TV`` and its gradient in the ``stv_tv`` kernel (``StyleContentModel.loss_and_grad(...,
+    tv_w=)``); this is the same definition as torch ops, for models without a fused step and as documentation."""
+    if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
+        msg = f"total_variation expects an image of shape [1, C, H, W] or [C, H, W], got {tuple(x.shape)}"
+        raise ValueError(msg)
+    dy = x[..., 1:, :] - x[..., :-1, :]
+    dx = x[..., :, 1:] - x[..., :, :-1]
+    return (dy.square().sum() + dx.square().sum()) / x.numel()
+
+
+def _fp32(v: float) -> float:
+    """``v`` (a double formed on the host) rounded to fp32 once, as the kernels receive it."""
+    return float(torch.tensor(v, dtype=torch.float64).to(torch.float32))
+
+
+def tv_scale(tv_w: float, C: int, H: int, W: int) -> float:
+    """The combine-table scale of the TV term: ``fp32(tv_w / (C*H*W))`` - the weight rides in the scale."""
+    return _fp32(float(tv_w) / float(C * H * W))
+
+
+def tv_coef(tv_w: float, C: int, H: int, W: int) -> float:
+    """The gradient coefficient of the TV term: ``fp32(tv_w * 2 / (C*H*W))``."""
+    return _fp32(float(tv_w) * 2.0 / float(C * H * W))
+
+
 # ------------------------------------------------------------------- initialisation
 def initialize_input(content_img: torch.Tensor, method: str) -> torch.Tensor:
     """Start image for the optimisation (reference core_model.py:66-100)."""
@@ -335,13 +367,17 @@ class _Engine:
             off += tap.parts_cnt
             rows.append([tap.parts_off, tap.parts_cnt, 1])
             scale.append(1.0 / float(tap.buf.act.numel()))
-        self.parts = torch.zeros(max(off, 1), device=device, dtype=torch.float32)
+        # (the partial sums of the total-variation term sit behind every tap's; only a tv_w > 0 step reads or writes them)
+        self.tv_parts_off = off
+        self.parts = torch.zeros(off + _lib.TV_LOSS_PARTS, device=device, dtype=torch.float32)
         self.table = torch.tensor(rows, dtype=torch.int32, device=device).reshape(-1, 3)
         self.scale = torch.tensor(scale, dtype=torch.float32, device=device)
         self.losses = torch.zeros(max(n_terms, 1), device=device, dtype=torch.float32)
         self.scores = torch.zeros(4, device=device, dtype=torch.float32)
         self.coef_buf = torch.ones(max(n_terms, 1), device=device, dtype=torch.float32)
         self._programs: dict = {}
+        self._tv_heads: dict = {}        # tv_w -> (table, scale, losses) of the combine op with the extra kind-2 row
+        self.image_channels = int(s.nodes[0].cin)
         self.use_graph = s.switches.hip_graph
         # Every evaluation overwrites the shared activation buffers; an autograd backward is only
         # valid against the forward that filled them last.  `generation` counts evaluations.
@@ -387,13 +423,35 @@ class _Engine:
             return s.forward_ops(x, after_node=after) + tail
         return s.forward_ops(x) + [op for node in s.nodes for op in after(node)] + tail
 
-    def _combine_op(self, style_w: float, content_w: float, score_log: tuple | None = None):
+    def tv_head(self, tv_w: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(table, scale, losses) of the combine op of a ``tv_w > 0`` step: the engine's rows plus one kind-2 row whose
+        scale carries the weight, and a losses vector with that term's slot at the end.  One triple per weight."""
+        head = self._tv_heads.get(tv_w)
+        if head is None:
+            if len(self._tv_heads) >= 16:
+                self._tv_heads.pop(next(iter(self._tv_heads)))
+            row = torch.tensor([[self.tv_parts_off, _lib.TV_LOSS_PARTS, _lib.KIND_EXTRA]], dtype=torch.int32, device=self.device)
+            sc = torch.tensor([tv_scale(tv_w, self.image_channels, self.H, self.W)], dtype=torch.float32, device=self.device)
+            head = self._tv_heads[tv_w] = (torch.cat([self.table, row]), torch.cat([self.scale, sc]),
+                                           torch.zeros(self.n_style + self.n_content + 1, device=self.device, dtype=torch.float32))
+        return head
+
+    def _tv_op(self, x: torch.Tensor, *, loss: bool = False, grad: torch.Tensor | None = None, tv_w: float = 0.0):
+        """The total-variation op on the image: its loss partials (``loss``), or ``grad += coef * sum(x - n)``."""
+        return self.sched.emit(op=_lib.OP_TV, p0=x, q0=self.parts[self.tv_parts_off:] if loss else None, q1=grad,
+                               cin=self.image_channels, H=self.H, W=self.W,
+                               f0=tv_coef(tv_w, self.image_channels, self.H, self.W) if grad is not None else 0.0,
+                               flags=_lib.ACCUM if grad is not None else 0)
+
+    def _combine_op(self, style_w: float, content_w: float, score_log: tuple | None = None, tv_w: float = 0.0):
         """``score_log`` = (ring fp32 [3, capacity], device counter int32 [1][, host-visible record count int32 [1]]):
-        the combine kernel also appends the three scores to the caller's history ring (stv_loss_combine_log)."""
+        the combine kernel also appends the three scores to the caller's history ring (stv_loss_combine_log).
+        ``tv_w`` > 0: the table with the total-variation row (:meth:`tv_head`)."""
         ring, count, seq = (tuple(score_log) + (None,))[:3] if score_log is not None else (None, None, None)
-        return self.sched.emit(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=self.table, p2=self.scale, p3=seq,
-                               q0=self.losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
-                               cin=self.n_style + self.n_content, f0=style_w, f1=content_w)
+        table, scale, losses = self.tv_head(tv_w) if tv_w else (self.table, self.scale, self.losses)
+        return self.sched.emit(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=table, p2=scale, p3=seq,
+                               q0=losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
+                               cin=table.shape[0], f0=style_w, f1=content_w)
 
     def _program(self, key: tuple, builder) -> plan.Program:
         prog = self._programs.get(key)
@@ -493,13 +551,17 @@ class _Engine:
 
     # -- execution -------------------------------------------------------------
     def loss_and_grad(self, x: torch.Tensor, grad: torch.Tensor, style_w: float, content_w: float, *,
-                      score_log: tuple | None = None, then_step=None) -> None:
+                      score_log: tuple | None = None, then_step=None, tv_w: float = 0.0) -> None:
         """``then_step`` (an ``optimizers.StepRequest`` for ``x``): the L-BFGS update of ``x`` from ``grad`` is the
-        schedule's last op - closure and update are one launch (one hipGraph)."""
+        schedule's last op - closure and update are one launch (one hipGraph).
+        ``tv_w`` > 0 adds ``tv_w * TV(x)`` to the total and its gradient to ``grad`` in two launches of ``stv_tv``: the
+        loss partials at the head of the forward half (the combine op, and through ``scores[2]`` the multi-iteration
+        L-BFGS op and the logging ring, need the term before the backward half), the gradient accumulated right behind
+        the first-layer dgrad, which WRITES ``grad``.  ``tv_w`` = 0: the step as it always was, under the same key."""
         self.generation += 1
         key = ("fused", x.data_ptr(), grad.data_ptr(), style_w, content_w,
                None if score_log is None else (tuple(t.data_ptr() for t in score_log), tuple(score_log[0].shape)),
-               None if then_step is None else then_step.key())
+               None if then_step is None else then_step.key()) + ((("tv", tv_w),) if tv_w else ())
 
         def build():
             s = self.sched
@@ -516,10 +578,13 @@ class _Engine:
                     # stop flag are device state); the step's loss test reads the total the combine op wrote
                     kw.update(op=_lib.OP_LBFGS_ITER, taps=then_step.iters_per_step, p1=self.scores[2:])
                 tail.append(s.emit(**kw))
-            return (self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w)
-                    + [self._combine_op(style_w, content_w, score_log)]
-                    + s.backward_ops(grad, content_coef=content_w, coef_dev=None, prewritten=fused_content)
-                    + tail)
+            fwd = self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w)
+            bwd = s.backward_ops(grad, content_coef=content_w, coef_dev=None, prewritten=fused_content)
+            if tv_w:
+                fwd.insert(0, self._tv_op(x, loss=True))
+                k = max(i for i, o in enumerate(bwd) if o.op == plan.OP_CONV_FIRST_DGRAD)
+                bwd.insert(k + 1, self._tv_op(x, grad=grad, tv_w=tv_w))
+            return fwd + [self._combine_op(style_w, content_w, score_log, tv_w)] + bwd + tail
         self._program(key, build).run(self.use_graph)
 
     def forward_losses(self, x: torch.Tensor) -> None:
@@ -663,9 +728,9 @@ class StyleContentModel(nn.Module):
         return style, content
 
     def loss_and_grad(self, x: torch.Tensor, style_w: float, content_w: float, *, live_scores: bool = False,
-                      score_log: tuple | None = None,
+                      score_log: tuple | None = None, tv_w: float = 0.0,
                       ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """Fused step: writes d(style_w*S + content_w*C)/dx into ``x.grad``.
+        """Fused step: writes d(style_w*S + content_w*C + tv_w*TV)/dx into ``x.grad``.
 
         Equivalent to reference optimization.py:292-313 (forward, weighted sum,
         ``loss.backward()``) in one command-buffer launch with no host sync.
@@ -674,7 +739,13 @@ class StyleContentModel(nn.Module):
         next evaluation, one copy kernel less per step (the runner consumes them at once).
         ``score_log`` = (ring [3, capacity] fp32, counter [1] int32) on this device: the three scores are also
         appended to that history ring by the combine kernel itself (LossAccumulator.device_log()).
+        ``tv_w`` > 0 adds the total-variation term (:func:`total_variation`) to the total (not to the two scores)
+        and its gradient to ``x.grad``; :meth:`last_tv_term` returns the weighted term.
         """
+        tv_w = float(tv_w)
+        if not 0.0 <= tv_w < float("inf"):
+            msg = f"tv_w must be a finite weight >= 0, got {tv_w}"
+            raise ValueError(msg)
         self._require_targets()
         eng = self._engine_for(x)
         eng.bind_targets(self.style_targets, self.content_targets)
@@ -688,10 +759,16 @@ class StyleContentModel(nn.Module):
         from . import optimizers  # noqa: PLC0415
         # inside HipLBFGS.step(closure) for this very tensor: the update rides at the end of the same launch
         eng.loss_and_grad(x.detach(), grad, float(style_w), float(content_w), score_log=score_log,
-                          then_step=optimizers.claim_step(x))
+                          then_step=optimizers.claim_step(x), tv_w=tv_w)
+        self._tv_term = eng.tv_head(tv_w)[2][eng.n_style + eng.n_content] if tv_w else None
         x.grad = grad
         scores = eng.scores if live_scores else eng.scores.clone()
         return scores[0], scores[1], scores[2]
+
+    def last_tv_term(self) -> torch.Tensor | None:
+        """``tv_w * TV(x)`` of the last ``loss_and_grad`` as a 0-d device view (valid until the next evaluation with
+        that weight), or ``None`` when that evaluation ran with ``tv_w == 0``."""
+        return getattr(self, "_tv_term", None)
 
 
 def prepare_model_and_input(

@@ -1,6 +1,7 @@
 // HBM-bound pointwise / small-reduction kernels around the conv stacks:
 // MaxPool2d(2,2) forward/backward, ReLU forward/backward, content MSE and its
-// gradient, and the final score combine.  All activation traffic is 16-byte
+// gradient, the total variation of the image and its gradient, and the final
+// score combine.  All activation traffic is 16-byte
 // vectors per lane (1 KiB per wave instruction); grids are capped and
 // grid-strided.
 #include <string.h>
@@ -328,6 +329,119 @@ __global__ __launch_bounds__(256) void content_grad_kernel(const T* __restrict__
   }
 }
 
+// ---------------------------------------------------------- total variation
+// TV(x) of the NCHW fp32 image and its gradient.  A work item is four consecutive pixels of one row (one 16-byte
+// vector); items are numbered row by row over all C*H rows, and a pass of the capped grid covers kTvBlocks * kTvThreads
+// consecutive items - whole rows side by side - so the rows above and below an item are read by a neighbouring
+// workgroup in the same pass and come out of the L2.  kVec: W % 4 == 0 and 16-byte aligned bases, every row starts on
+// a vector; otherwise the same items are walked with guarded scalar accesses (same partial sums in the same order).
+// Loss partials: per thread in item order, then wave, then workgroup (block_sum_1024) - fixed order, no atomics;
+// a workgroup without items writes 0.
+constexpr int kTvThreads = 1024;
+constexpr int kTvBlocks = STV_TV_LOSS_PARTS;
+template <bool kVec, bool kLoss, bool kGrad>
+__global__ __launch_bounds__(kTvThreads) void tv_kernel(const float* __restrict__ x, float* __restrict__ part,
+                                                        float* __restrict__ dx, int rows, int H, int W, float coef,
+                                                        int accum) {
+  __shared__ float red[kTvThreads / 64];
+  const int W4 = (W + 3) >> 2;
+  const unsigned items = (unsigned)rows * (unsigned)W4;          // < 2^29: the entry point bounds C*H*W*4 bytes by 2 GiB
+  float loss = 0.0f;
+  for (unsigned i = blockIdx.x * kTvThreads + threadIdx.x; i < items; i += (unsigned)gridDim.x * kTvThreads) {
+    const int r = (int)(i / (unsigned)W4);
+    const int x0 = (int)(i - (unsigned)r * (unsigned)W4) * 4;
+    const int y = r % H;
+    const bool has_up = y > 0, has_down = y < H - 1;
+    const float* row = x + (size_t)r * W;
+    const int nv = kVec ? 4 : (W - x0 < 4 ? W - x0 : 4);          // pixels of this item inside the row
+    float c[4], up[4], dn[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = up[k] = dn[k] = 0.0f;
+    if constexpr (kVec) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(row + x0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) c[k] = v[k];
+      if (kGrad && has_up) {
+        const f32x4 u = *reinterpret_cast<const f32x4*>(row - W + x0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) up[k] = u[k];
+      }
+      if (has_down) {
+        const f32x4 d = *reinterpret_cast<const f32x4*>(row + W + x0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dn[k] = d[k];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k < nv) {
+          c[k] = row[x0 + k];
+          if (kGrad && has_up) up[k] = row[x0 + k - W];
+          if (has_down) dn[k] = row[x0 + k + W];
+        }
+      }
+    }
+    const float left = (kGrad && x0 > 0) ? row[x0 - 1] : 0.0f;
+    const float right = (x0 + 4 < W) ? row[x0 + 4] : 0.0f;
+    float out[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      out[k] = 0.0f;
+      if (k >= nv) continue;
+      const int xx = x0 + k;
+      const bool has_left = xx > 0, has_right = xx < W - 1;
+      const float lv = k > 0 ? c[k - 1] : left;
+      const float rv = k < 3 ? c[k + 1] : right;
+      if constexpr (kLoss) {
+        if (has_down) { const float d = dn[k] - c[k]; loss = fmaf(d, d, loss); }
+        if (has_right) { const float d = rv - c[k]; loss = fmaf(d, d, loss); }
+      }
+      if constexpr (kGrad) {
+        float s = 0.0f;                                            // existing differences, in the order up, down, left, right
+        if (has_up) s = __fadd_rn(s, c[k] - up[k]);
+        if (has_down) s = __fadd_rn(s, c[k] - dn[k]);
+        if (has_left) s = __fadd_rn(s, c[k] - lv);
+        if (has_right) s = __fadd_rn(s, c[k] - rv);
+        out[k] = __fmul_rn(coef, s);                               // no contraction with the accumulate below
+      }
+    }
+    if constexpr (kGrad) {
+      float* o = dx + (size_t)r * W + x0;
+      if constexpr (kVec) {
+        f32x4 v;
+        if (accum) {
+          const f32x4 old = *reinterpret_cast<const f32x4*>(o);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = __fadd_rn(old[k], out[k]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = out[k];
+        }
+        *reinterpret_cast<f32x4*>(o) = v;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (k < nv) o[k] = accum ? __fadd_rn(o[k], out[k]) : out[k];
+      }
+    }
+  }
+  if constexpr (kLoss) {
+    loss = block_sum_1024(loss, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = loss;
+  }
+}
+
+template <bool kVec>
+void tv_launch(const float* x, float* part, float* dx, int rows, int H, int W, float coef, int accum, unsigned grid,
+               hipStream_t st) {
+  if (part && dx)
+    hipLaunchKernelGGL((tv_kernel<kVec, true, true>), dim3(grid), dim3(kTvThreads), 0, st, x, part, dx, rows, H, W, coef, accum);
+  else if (part)
+    hipLaunchKernelGGL((tv_kernel<kVec, true, false>), dim3(grid), dim3(kTvThreads), 0, st, x, part, dx, rows, H, W, coef, accum);
+  else
+    hipLaunchKernelGGL((tv_kernel<kVec, false, true>), dim3(grid), dim3(kTvThreads), 0, st, x, part, dx, rows, H, W, coef, accum);
+}
+
 // ------------------------------------------------------------ score combine
 // One workgroup of 1024 threads.  losses[k] = scale[k] * sum(parts[off..off+cnt)) with a
 // fixed summation tree (deterministic); then the reference's sequential fp32
@@ -394,9 +508,13 @@ __global__ __launch_bounds__(1024) void loss_combine_kernel(const float* __restr
     float style = 0.0f, content = 0.0f;
     for (int k = 0; k < nt; ++k) {
       if (s_kind[k] == 0) style += s_term[k];
-      else content += s_term[k];
+      else if (s_kind[k] == 1) content += s_term[k];
     }
-    const float total_loss = style_w * style + content_w * content;
+    float total_loss = style_w * style + content_w * content;
+    // kind 2: a term on the image itself (total variation), weight already in its scale - joins the total only, in
+    // index order, one fp32 add each
+    for (int k = 0; k < nt; ++k)
+      if (s_kind[k] == 2) total_loss += s_term[k];
     scores[0] = style;
     scores[1] = content;
     scores[2] = total_loss;
@@ -605,6 +723,26 @@ extern "C" int stv_content_grad(const void* F, const void* target, void* dF, siz
                        static_cast<bf16_t*>(dF), n, coef, coef_dev, flags);
   else
     return STV_ERR_ARG;
+  STV_CHECK_LAUNCH();
+  return STV_OK;
+}
+
+extern "C" int stv_tv(const float* x_nchw, float* loss_part, float* dx_nchw, int C, int H, int W, float coef, int flags,
+                      void* stream) {
+  if (!x_nchw || (!loss_part && !dx_nchw) || C <= 0 || H <= 0 || W <= 0 || x_nchw == dx_nchw) return STV_ERR_ARG;
+  if ((unsigned long long)C * (unsigned long long)H * (unsigned long long)W * 4ull >= (1ull << 31)) return STV_ERR_ARG;
+  if (flags & ~STV_ACCUM) return STV_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rows = C * H;
+  const size_t items = (size_t)rows * ((W + 3) / 4);
+  // every loss partial is written on every launch: the loss form always runs the full grid
+  size_t grid = loss_part ? (size_t)kTvBlocks : (items + kTvThreads - 1) / kTvThreads;
+  if (grid > (size_t)kTvBlocks) grid = kTvBlocks;
+  const bool vec = (W % 4 == 0) && ((uintptr_t)x_nchw % 16 == 0) && ((uintptr_t)dx_nchw % 16 == 0);
+  if (vec)
+    tv_launch<true>(x_nchw, loss_part, dx_nchw, rows, H, W, coef, (flags & STV_ACCUM) != 0, (unsigned)grid, st);
+  else
+    tv_launch<false>(x_nchw, loss_part, dx_nchw, rows, H, W, coef, (flags & STV_ACCUM) != 0, (unsigned)grid, st);
   STV_CHECK_LAUNCH();
   return STV_OK;
 }

@@ -412,6 +412,16 @@ def content_grad(F: torch.Tensor, target: torch.Tensor, dF: torch.Tensor, coef: 
                                     dtype_code(F.dtype), _stream()), "stv_content_grad")
 
 
+def tv(x: torch.Tensor | None, *, loss_part: torch.Tensor | None = None, dx: torch.Tensor | None = None,
+       coef: float = 0.0, flags: int = 0, shape: tuple | None = None) -> None:
+    """Total variation of the NCHW fp32 image ``x`` (``stv_tv``): ``loss_part`` receives ``TV_LOSS_PARTS`` raw partial
+    sums of the squared forward differences, ``dx`` (written, or accumulated onto with ``ACCUM``) ``coef`` times the
+    sum over the existing 4-neighbours of ``x - n``.  ``shape`` = (C, H, W), default ``x.shape[-3:]``."""
+    lib = _lib.load()
+    C, H, W = (int(v) for v in (shape if shape is not None else x.shape[-3:]))
+    _lib.check(lib.stv_tv(_ptr(x), _ptr(loss_part), _ptr(dx), C, H, W, coef, flags, _stream()), "stv_tv")
+
+
 class HostMailbox:
     """Pinned host memory the GPU writes while the CPU reads (``stv_host_mailbox_alloc``: mapped under the same
     pointer on the device, fine-grained coherent, zeroed).  ``tensor`` / ``array`` are views; every view keeps this

@@ -32,6 +32,7 @@ from torch.optim import Optimizer
 
 from . import image_io
 from .constants import CSV_LOGGING_RECOMMENDED_STEPS
+from .core_model import total_variation
 from .logging_utils import logger
 from .loss_accumulator import DEFAULT_HISTORY_CAPACITY, LoggedLoss, LossAccumulator
 from .loss_logger import LossCSVLogger
@@ -276,21 +277,25 @@ class OptimizationRunner:
         """One forward + backward; leaves d(total)/d(image) in ``input_img.grad``."""
         oc = self.config.optimization
         self.optimizer.zero_grad()
+        tv_w = float(getattr(oc, "tv_w", 0.0))
         if self._fused:
-            style_score, content_score, loss = self._fused_eval(oc.style_w, oc.content_w)
+            style_score, content_score, loss = self._fused_eval(oc.style_w, oc.content_w, tv_w)
         else:
             style_losses, content_losses = self.model(self.input_img)
             zero = torch.zeros((), device=self.input_img.device, dtype=self.input_img.dtype)
             style_score = torch.stack(style_losses).sum() if style_losses else zero
             content_score = torch.stack(content_losses).sum() if content_losses else zero
             loss = oc.style_w * style_score + oc.content_w * content_score
+            if tv_w > 0:
+                loss = loss + tv_w * total_variation(self.input_img)
             loss.backward()
             self._check_finite(style_score, content_score, loss, step_idx)
         return StepTensors(step=step_idx, style_score=style_score, content_score=content_score, total_loss=loss)
 
-    def _fused_eval(self, style_w: float, content_w: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def _fused_eval(self, style_w: float, content_w: float, tv_w: float = 0.0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """The model's fused step; its scores are recorded before the next evaluation, so views of the
-        live score buffer are enough where the model offers them (models without the keyword: plain call)."""
+        live score buffer are enough where the model offers them (models without the keyword: plain call).
+        ``tv_w`` > 0 is handed to the model, or refused: a fused step that cannot form the term must not drop it."""
         if self._live_scores is None:
             import inspect
             try:
@@ -300,6 +305,12 @@ class OptimizationRunner:
             self._live_scores = "live_scores" in self._model_kwargs
         kwargs = {}
         self._producer_logged = False
+        if tv_w > 0:
+            if "tv_w" not in self._model_kwargs:
+                msg = (f"optimization.tv_w = {tv_w:g}, but the model's loss_and_grad() takes no tv_w keyword: "
+                       "the total-variation term would be dropped")
+                raise ValueError(msg)
+            kwargs["tv_w"] = tv_w
         if self._live_scores:
             kwargs["live_scores"] = True
         if self._single_eval and "score_log" in self._model_kwargs and self._loss_accumulator is not None:

@@ -39,7 +39,7 @@ from torch import nn
 from . import _lib, ops
 from ._lib import (ACCUM, MASK, POOL_IDX, POOL_ONLY, POOL_ROUTE, W_BLOCKED, OP_GRAM_MULTI, OP_CONTENT_GRAD, OP_CONTENT_LOSS, OP_CONV, OP_CONV_FIRST_DGRAD,
                    OP_CONV_FIRST_FWD, OP_GRAM_FINISH, OP_GRAM_PARTIAL, OP_LOSS_COMBINE, OP_POOL_BWD,
-                   OP_POOL_FWD, OP_RELU_BWD, OP_RELU_FWD, RELU_IN, RELU_OUT, StvOp)
+                   OP_POOL_FWD, OP_RELU_BWD, OP_RELU_FWD, OP_TV, RELU_IN, RELU_OUT, StvOp)
 
 GRAM_CLAMP_MAX = 5e5  # reference constants.py:15
 

@@ -139,7 +139,11 @@ class SpatialShard:
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
-                 style_w: float, content_w: float) -> None:
+                 style_w: float, content_w: float, tv_w: float = 0.0) -> None:
+        if tv_w:
+            msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
+                   "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
+            raise ValueError(msg)
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         dev = content_img.device
@@ -246,7 +250,11 @@ class HaloShard:
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
-                 style_w: float, content_w: float, group=None, split: bool = False) -> None:
+                 style_w: float, content_w: float, group=None, split: bool = False, tv_w: float = 0.0) -> None:
+        if tv_w:
+            msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
+                   "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
+            raise ValueError(msg)
         if split:
             msg = ("bf16x3 (split-bf16 products) is not available on the row-strip path: use precision fp32 or "
                    "bf16 with HaloShard, or bf16x3 on a whole image")
