@@ -284,6 +284,25 @@ int stv_content_grad(const void* F, const void* target, void* dF, size_t n, floa
  * dimension, C*H*W*4 >= 2 GiB, a flag other than STV_ACCUM. */
 int stv_tv(const float* x_nchw, float* loss_part, float* dx_nchw, int C, int H, int W, float coef, int flags, void* stream);
 
+/* ---- 2x resize of the image between the levels of a coarse-to-fine run (no counterpart in the reference).  Since
+ *      version 106.  Every product and every sum below is rounded to fp32 on its own (no FMA contraction), in the order
+ *      written, so that an fp32 twin reproduces every output bit.
+ *      DOWN2, the 2x2 box mean:
+ *        y[c,Y,X] = ((x[c,2Y,2X] + x[c,2Y,2X+1]) + (x[c,2Y+1,2X] + x[c,2Y+1,2X+1])) * 0.25f
+ *      UP2, bilinear with half-pixel centres and clamped edges (F.interpolate(scale_factor=2, mode="bilinear",
+ *      align_corners=False)), separable, columns first: for output column X the near column is n = X >> 1 and the far
+ *      column f = clamp(n + (X odd ? +1 : -1), 0, W-1);  h[r,X] = 0.75f*x[r,n] + 0.25f*x[r,f];  the same rule along rows
+ *      on h:  y[Y,X] = 0.75f*h[near row,X] + 0.25f*h[far row,X].  Nothing is read across a channel plane. ------------- */
+enum { STV_RESIZE_DOWN2 = 0, STV_RESIZE_UP2 = 1 };
+/* launch constants: a work item is four consecutive output pixels of one row, a pass of the capped grid covers
+ * STV_RESIZE_MAX_BLOCKS * STV_RESIZE_THREADS items */
+#define STV_RESIZE_THREADS 256
+#define STV_RESIZE_MAX_BLOCKS 1024
+/* x NCHW fp32 [C][H][W] -> y NCHW fp32: DOWN2 [C][H/2][W/2] (H, W even), UP2 [C][2H][2W].  x != y.
+ * STV_ERR_ARG: a null pointer, x == y, a non-positive dimension, odd H or W with DOWN2, an unknown mode, an input or
+ * an output of 2 GiB or more. */
+int stv_resize2x(const float* x, float* y, int C, int H, int W, int mode, void* stream);
+
 /* ---- Frame / PNG export: prepare_image_for_output (image_io.py:129-152: denormalise,
  *      nan_to_num(nan=0, posinf=1, neginf=0), clamp 0..1) fused with the uint8 conversion, on the
  *      device, so only H*W*3 bytes cross to the host.  x NCHW fp32 [3][H][W] -> out HWC uint8.

@@ -26,6 +26,10 @@ TV_LOSS_PARTS = 256       # stv.h STV_TV_LOSS_PARTS: one loss partial per workgr
 # pixels of one row, a pass of the capped grid covers TV_LOSS_PARTS * TV_THREADS items
 TV_THREADS, TV_VEC = 1024, 4
 KIND_STYLE, KIND_CONTENT, KIND_EXTRA = 0, 1, 2      # third column of the combine table
+RESIZE_DOWN2, RESIZE_UP2 = 0, 1                     # stv.h STV_RESIZE_*: the modes of stv_resize2x
+# launch constants of stv_resize2x (stv.h STV_RESIZE_THREADS, STV_RESIZE_MAX_BLOCKS; pixels per work item): a work item is
+# RESIZE_VEC consecutive OUTPUT pixels of one row, a pass of the capped grid covers RESIZE_MAX_BLOCKS * RESIZE_THREADS items
+RESIZE_THREADS, RESIZE_MAX_BLOCKS, RESIZE_VEC = 256, 1024, 4
 
 _ERRORS = {1: "STV_ERR_ARG (unsupported shape / null pointer / dtype)",
            2: "STV_ERR_LAUNCH (HIP launch failed)", 3: "STV_ERR_ALLOC", 4: "STV_ERR_GRAPH"}
@@ -94,6 +98,7 @@ SIGNATURES = {
     "stv_content_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_int, c_void_p]),
     "stv_content_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_int, c_int, c_void_p]),
     "stv_tv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "stv_resize2x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "stv_image_to_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_void_p]),
     "stv_loss_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "stv_loss_combine_log": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,

@@ -1,7 +1,8 @@
 """``style-visualizer`` command line: same flags and override rules as reference cli.py:26-354.
 
 Options that only have meaning for presentation features outside this build (comparison grids)
-are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,bf16x3}``, ``--tv-w``.
+are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,bf16x3}``, ``--tv-w``,
+``--pyramid-levels`` / ``--pyramid-steps``.
 """
 from __future__ import annotations
 
@@ -40,6 +41,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     opt.add_argument("--style-w", type=float, default=S, help="Style weight")
     opt.add_argument("--content-w", type=float, default=S, help="Content weight")
     opt.add_argument("--tv-w", type=float, default=S, help="Total-variation weight (0 = off, the default)")
+    opt.add_argument("--pyramid-levels", type=int, default=S,
+                     help="Coarse-to-fine levels, each twice the size of the one before (1 = off, the default)")
+    opt.add_argument("--pyramid-steps", type=str,
+                     help="Comma-separated steps per pyramid level, coarsest first (default: --steps split evenly)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
     opt.add_argument("--init-method", choices=["random", "white", "content"], default=S, help="Initialization method")
     opt.add_argument("--seed", type=int, default=S, help="Random seed")
@@ -106,6 +111,10 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
     if o.tv_w > 0:
         rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Content Weight") + 1,
                     ("Total Variation Weight", f"{o.tv_w:g}"))
+    if o.pyramid_levels > 1:
+        at = next(i for i, (label, _) in enumerate(rows) if label == "Steps") + 1
+        rows[at:at] = [("Pyramid Levels", o.pyramid_levels),
+                       ("Pyramid Steps", o.pyramid_steps if o.pyramid_steps else "even split of Steps")]
     for label, value in rows:
         logger.info("%s: %s", label, value)
 

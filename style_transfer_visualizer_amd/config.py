@@ -2,8 +2,9 @@
 
 Field names, bounds and override precedence follow reference config.py:53-309
 so existing ``config.toml`` files and CLI invocations keep working.  The
-additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf16x3" fp32 storage, split-bf16 products)
-and ``optimization.tv_w`` (weight of the total-variation regulariser, 0 = off).
+additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf16x3" fp32 storage, split-bf16 products),
+``optimization.tv_w`` (weight of the total-variation regulariser, 0 = off) and ``optimization.pyramid_levels`` /
+``optimization.pyramid_steps`` (coarse-to-fine runs: levels, and optionally the steps of each, coarsest first).
 """
 from __future__ import annotations
 
@@ -26,6 +27,8 @@ class OptimizationConfig(BaseModel):
     style_w: float = Field(d.DEFAULT_STYLE_WEIGHT, ge=0)
     content_w: float = Field(d.DEFAULT_CONTENT_WEIGHT, ge=0)
     tv_w: float = Field(d.DEFAULT_TV_WEIGHT, ge=0)
+    pyramid_levels: int = Field(d.DEFAULT_PYRAMID_LEVELS, ge=1, le=6)
+    pyramid_steps: list[int] | None = d.DEFAULT_PYRAMID_STEPS
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
     seed: int = Field(d.DEFAULT_SEED, ge=0)
@@ -120,6 +123,7 @@ _DIRECT = {
     "output": ("output", "output"), "log_every": ("output", "log_every"), "log_loss": ("output", "log_loss"),
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
     "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lr": ("optimization", "lr"),
+    "pyramid_levels": ("optimization", "pyramid_levels"),
     "init_method": ("optimization", "init_method"), "seed": ("optimization", "seed"),
     "save_every": ("video", "save_every"), "fps": ("video", "fps"), "quality": ("video", "quality"),
     "metadata_title": ("video", "metadata_title"), "metadata_artist": ("video", "metadata_artist"),
@@ -180,6 +184,8 @@ def _apply_optimization_overrides(cfg: StyleTransferConfig, args: Mapping[str, A
         cfg.optimization.style_layers = parse_int_list(args["style_layers"])
     if args.get("content_layers"):
         cfg.optimization.content_layers = parse_int_list(args["content_layers"])
+    if args.get("pyramid_steps"):
+        cfg.optimization.pyramid_steps = parse_int_list(args["pyramid_steps"])
 
 
 def _apply_video_overrides(cfg: StyleTransferConfig, args: Mapping[str, Any]) -> None:

@@ -1,7 +1,7 @@
 // HBM-bound pointwise / small-reduction kernels around the conv stacks:
 // MaxPool2d(2,2) forward/backward, ReLU forward/backward, content MSE and its
-// gradient, the total variation of the image and its gradient, and the final
-// score combine.  All activation traffic is 16-byte
+// gradient, the total variation of the image and its gradient, the 2x resize
+// between the levels of a coarse-to-fine run, and the final score combine.  All activation traffic is 16-byte
 // vectors per lane (1 KiB per wave instruction); grids are capped and
 // grid-strided.
 #include <string.h>
@@ -442,6 +442,98 @@ void tv_launch(const float* x, float* part, float* dx, int rows, int H, int W, f
     hipLaunchKernelGGL((tv_kernel<kVec, false, true>), dim3(grid), dim3(kTvThreads), 0, st, x, part, dx, rows, H, W, coef, accum);
 }
 
+// ------------------------------------------------------------------ 2x resize
+// The change of size between the levels of a coarse-to-fine run, NCHW fp32 -> NCHW fp32.  A work item is four consecutive
+// OUTPUT pixels of one row (one 16-byte store); items are numbered row by row over all output rows of all planes, and a
+// pass of the capped grid covers kResizeBlocks * kResizeThreads consecutive items.  kVec: every output row (and, where the
+// inputs are read as vectors, every input row) starts on a 16-byte boundary and no row end is ragged; otherwise the same
+// items are walked with guarded scalar accesses.  Every product and every sum is rounded on its own, in the order stv.h
+// states, so the outputs are reproducible bit for bit: plain * and + under `fp contract(off)`.  (__fmul_rn / __fadd_rn
+// would not do: the header defines them as x * y and x + y, compiled under the default contraction mode, and the compiler
+// fuses the inlined pair into an FMA whatever the caller's pragma says.)
+//   DOWN2: rows 2r and 2r + 1 of the input hold the window of output row r (H = 2 * Ho: planes stay apart by themselves).
+//   UP2:   separable, columns first; near/far indices are clamped inside the row and inside the plane.
+constexpr int kResizeThreads = STV_RESIZE_THREADS;
+constexpr int kResizeBlocks = STV_RESIZE_MAX_BLOCKS;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+__device__ __forceinline__ float lerp_3_1(float near, float far) {
+#pragma clang fp contract(off)
+  const float a = 0.75f * near, b = 0.25f * far;
+  return a + b;
+}
+template <int kMode, bool kVec>
+__global__ __launch_bounds__(kResizeThreads) void resize2x_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                  int out_rows, int H, int W, int Ho, int Wo) {
+#pragma clang fp contract(off)
+  const int W4 = (Wo + 3) >> 2;
+  const unsigned items = (unsigned)out_rows * (unsigned)W4;      // < 2^29: the entry point bounds both sizes by 2 GiB
+  for (unsigned i = blockIdx.x * kResizeThreads + threadIdx.x; i < items; i += (unsigned)gridDim.x * kResizeThreads) {
+    const int r = (int)(i / (unsigned)W4);
+    const int x0 = (int)(i - (unsigned)r * (unsigned)W4) * 4;
+    const int nv = kVec ? 4 : (Wo - x0 < 4 ? Wo - x0 : 4);        // pixels of this item inside the row
+    float out[4];
+    if constexpr (kMode == STV_RESIZE_DOWN2) {
+      const float* top = x + (size_t)(2 * r) * W + 2 * x0;
+      const float* bot = top + W;
+      float t[8], b[8];
+      if constexpr (kVec) {
+        const f32x4 t0 = *reinterpret_cast<const f32x4*>(top), t1 = *reinterpret_cast<const f32x4*>(top + 4);
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(bot), b1 = *reinterpret_cast<const f32x4*>(bot + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { t[k] = t0[k]; t[4 + k] = t1[k]; b[k] = b0[k]; b[4 + k] = b1[k]; }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const bool in = (k >> 1) < nv;
+          t[k] = in ? top[k] : 0.0f;
+          b[k] = in ? bot[k] : 0.0f;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        out[k] = ((t[2 * k] + t[2 * k + 1]) + (b[2 * k] + b[2 * k + 1])) * 0.25f;
+    } else {
+      const int c = r / Ho, yy = r - c * Ho;
+      const int rn = yy >> 1;
+      int rf = (yy & 1) ? rn + 1 : rn - 1;
+      rf = rf < 0 ? 0 : (rf > H - 1 ? H - 1 : rf);
+      const float* near = x + ((size_t)c * H + rn) * W;
+      const float* far = x + ((size_t)c * H + rf) * W;
+      // output columns x0 .. x0 + 3 read input columns a - 1 .. a + 2 (a = x0 / 2, even), clamped into the row
+      const int a = x0 >> 1;
+      const int cl = a > 0 ? a - 1 : 0;
+      const int cr = a + 2 < W ? a + 2 : W - 1;
+      float n[4], f[4];
+      n[0] = near[cl]; f[0] = far[cl];
+      n[3] = near[cr]; f[3] = far[cr];
+      if constexpr (kVec) {
+        const f32x2 nm = *reinterpret_cast<const f32x2*>(near + a), fm = *reinterpret_cast<const f32x2*>(far + a);
+        n[1] = nm[0]; n[2] = nm[1]; f[1] = fm[0]; f[2] = fm[1];
+      } else {
+        const int a1 = a + 1 < W ? a + 1 : W - 1;
+        n[1] = near[a]; f[1] = far[a];
+        n[2] = near[a1]; f[2] = far[a1];
+      }
+      // (near, far) input column of the four outputs: (a, a-1), (a, a+1), (a+1, a), (a+1, a+2)
+      const float hn[4] = {lerp_3_1(n[1], n[0]), lerp_3_1(n[1], n[2]), lerp_3_1(n[2], n[1]), lerp_3_1(n[2], n[3])};
+      const float hf[4] = {lerp_3_1(f[1], f[0]), lerp_3_1(f[1], f[2]), lerp_3_1(f[2], f[1]), lerp_3_1(f[2], f[3])};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) out[k] = lerp_3_1(hn[k], hf[k]);
+    }
+    float* o = y + (size_t)r * Wo + x0;
+    if constexpr (kVec) {
+      f32x4 v;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = out[k];
+      *reinterpret_cast<f32x4*>(o) = v;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < nv) o[k] = out[k];
+    }
+  }
+}
+
 // ------------------------------------------------------------ score combine
 // One workgroup of 1024 threads.  losses[k] = scale[k] * sum(parts[off..off+cnt)) with a
 // fixed summation tree (deterministic); then the reference's sequential fp32
@@ -743,6 +835,35 @@ extern "C" int stv_tv(const float* x_nchw, float* loss_part, float* dx_nchw, int
     tv_launch<true>(x_nchw, loss_part, dx_nchw, rows, H, W, coef, (flags & STV_ACCUM) != 0, (unsigned)grid, st);
   else
     tv_launch<false>(x_nchw, loss_part, dx_nchw, rows, H, W, coef, (flags & STV_ACCUM) != 0, (unsigned)grid, st);
+  STV_CHECK_LAUNCH();
+  return STV_OK;
+}
+
+extern "C" int stv_resize2x(const float* x, float* y, int C, int H, int W, int mode, void* stream) {
+  if (!x || !y || x == y || C <= 0 || H <= 0 || W <= 0) return STV_ERR_ARG;
+  if (mode != STV_RESIZE_DOWN2 && mode != STV_RESIZE_UP2) return STV_ERR_ARG;
+  const bool down = mode == STV_RESIZE_DOWN2;
+  if (down && ((H | W) & 1)) return STV_ERR_ARG;
+  const unsigned long long in_bytes = (unsigned long long)C * (unsigned long long)H * (unsigned long long)W * 4ull;
+  if (in_bytes >= (1ull << 31) || (!down && in_bytes * 4ull >= (1ull << 31))) return STV_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int Ho = down ? H / 2 : 2 * H, Wo = down ? W / 2 : 2 * W;
+  const int out_rows = C * Ho;
+  const size_t items = (size_t)out_rows * ((Wo + 3) / 4);
+  size_t grid = (items + kResizeThreads - 1) / kResizeThreads;
+  if (grid > (size_t)kResizeBlocks) grid = kResizeBlocks;
+  // all rows start on a vector: output rows of Wo % 4 == 0 floats (then input rows are 8-byte multiples for UP2, 16-byte
+  // multiples for DOWN2) behind 16-byte aligned bases
+  const bool vec = (Wo % 4 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0);
+  const dim3 g((unsigned)grid), b(kResizeThreads);
+  if (down && vec)
+    hipLaunchKernelGGL((resize2x_kernel<STV_RESIZE_DOWN2, true>), g, b, 0, st, x, y, out_rows, H, W, Ho, Wo);
+  else if (down)
+    hipLaunchKernelGGL((resize2x_kernel<STV_RESIZE_DOWN2, false>), g, b, 0, st, x, y, out_rows, H, W, Ho, Wo);
+  else if (vec)
+    hipLaunchKernelGGL((resize2x_kernel<STV_RESIZE_UP2, true>), g, b, 0, st, x, y, out_rows, H, W, Ho, Wo);
+  else
+    hipLaunchKernelGGL((resize2x_kernel<STV_RESIZE_UP2, false>), g, b, 0, st, x, y, out_rows, H, W, Ho, Wo);
   STV_CHECK_LAUNCH();
   return STV_OK;
 }

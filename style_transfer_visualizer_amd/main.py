@@ -12,7 +12,7 @@ from pathlib import Path
 
 import torch
 
-from . import core_model, image_io, optimization, runtime
+from . import core_model, image_io, optimization, pyramid, runtime
 from .logging_utils import logger
 from .type_defs import InputPaths, SaveOptions
 
@@ -44,10 +44,12 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     normalize = config.optimization.normalize
     content_img = image_io.load_image_to_tensor(paths.content_path, device, normalize=normalize)
     style_img = image_io.load_image_to_tensor(paths.style_path, device, normalize=normalize)
-    with _SETUP_LOCK:
-        runtime.setup_random_seed(config.optimization.seed)
-        model, input_img, optimizer = core_model.prepare_model_and_input(
-            content_img, style_img, device, config.optimization, precision=config.hardware.precision)
+    coarse_to_fine = config.optimization.pyramid_levels > 1
+    if not coarse_to_fine:
+        with _SETUP_LOCK:
+            runtime.setup_random_seed(config.optimization.seed)
+            model, input_img, optimizer = core_model.prepare_model_and_input(
+                content_img, style_img, device, config.optimization, precision=config.hardware.precision)
 
     output_path = runtime.setup_output_directory(config.output.output)
     content_name, style_name = Path(paths.content_path).stem, Path(paths.style_path).stem + (output_tag if tag_png else "")
@@ -55,9 +57,14 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
         log_path = Path(config.output.log_loss)
         config.output.log_loss = str(log_path.with_name(log_path.stem + output_tag + log_path.suffix))
 
-    runner = optimization.OptimizationRunner(model, input_img, config, optimizer=optimizer,
-                                             video_writer=video_writer, gif_collector=gif_collector)
-    input_img, loss_metrics, elapsed = runner.run()
+    if coarse_to_fine:                          # (refuses frame sinks: frames would change size between levels)
+        input_img, loss_metrics, elapsed = pyramid.run_pyramid(
+            content_img, style_img, device, config, video_writer=video_writer, gif_collector=gif_collector,
+            seed=config.optimization.seed, setup_lock=_SETUP_LOCK)
+    else:
+        runner = optimization.OptimizationRunner(model, input_img, config, optimizer=optimizer,
+                                                 video_writer=video_writer, gif_collector=gif_collector)
+        input_img, loss_metrics, elapsed = runner.run()
     for sink in (video_writer, gif_collector):
         if sink is not None:
             sink.close()

@@ -422,6 +422,29 @@ def tv(x: torch.Tensor | None, *, loss_part: torch.Tensor | None = None, dx: tor
     _lib.check(lib.stv_tv(_ptr(x), _ptr(loss_part), _ptr(dx), C, H, W, coef, flags, _stream()), "stv_tv")
 
 
+def resize2x(x: torch.Tensor, mode: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """2x resize of a contiguous fp32 image ``[3, H, W]`` or ``[1, 3, H, W]`` on the device (``stv_resize2x``):
+    ``RESIZE_DOWN2`` is the 2x2 box mean (H and W even), ``RESIZE_UP2`` bilinear with half-pixel centres and clamped
+    edges.  Returns a tensor of the same rank (``out`` when given: same rank, the output's shape, not ``x``)."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
+        msg = f"resize2x expects an fp32 image [C, H, W] or [1, C, H, W], got {tuple(x.shape)} {x.dtype}"
+        raise RuntimeError(msg)
+    C, H, W = (int(v) for v in x.shape[-3:])
+    if mode == _lib.RESIZE_DOWN2:
+        Ho, Wo = H // 2, W // 2
+    else:                                   # (an unknown mode is the entry point's to refuse)
+        Ho, Wo = 2 * H, 2 * W
+    shape = (*x.shape[:-2], Ho, Wo)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32:
+        msg = f"resize2x: out is {tuple(out.shape)} {out.dtype}, expected {shape} torch.float32"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_resize2x(_ptr(x), _ptr(out), C, H, W, int(mode), _stream()), "stv_resize2x")
+    return out
+
+
 class HostMailbox:
     """Pinned host memory the GPU writes while the CPU reads (``stv_host_mailbox_alloc``: mapped under the same
     pointer on the device, fine-grained coherent, zeroed).  ``tensor`` / ``array`` are views; every view keeps this
