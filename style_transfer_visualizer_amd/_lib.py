@@ -58,6 +58,16 @@ class StvGramTap(ctypes.Structure):
         ("clamp_max", c_float), ("norm", c_float), ("coef", c_float),
     ]
 
+    def fill(self, *, n_pixels: int, channels: int, clamp_max: float, coef: float, partials: int, F: int | None = None,
+             target: int | None = None, gram_out: int | None = None, loss_part: int | None = None,
+             sgrad: int | None = None, coef_dev: int | None = None) -> None:
+        """One tap of a batched Gram chain from device addresses (None: absent; ``F`` absent: the slabs are already
+        filled).  ``norm`` is the reference's ``b*c*h*w``."""
+        self.F, self.partials, self.target, self.gram_out = F, partials, target, gram_out
+        self.loss_part, self.sgrad, self.coef_dev = loss_part, sgrad, coef_dev
+        self.n_pixels, self.channels = n_pixels, channels
+        self.clamp_max, self.norm, self.coef = clamp_max, float(channels * n_pixels), float(coef)
+
 
 # name -> (restype, argtypes); every symbol include/stv.h declares
 SIGNATURES = {

@@ -15,8 +15,16 @@
 //                    partial sums, and the backward seed
 //                    S = k * [R <= clamp] * (G - T)  (symmetric), so that
 //                    dF^T = F^T * S is a plain 1x1 conv (stv_conv_igemm taps=1).
-#include <type_traits>
-
+// stv_gram_multi   : both passes for several taps (layers) in one grid each.
+//
+// One body and one launch helper per pass; the host fills per-tap entries (PartialMulti / FinishMulti: operands and
+// the first block of each tap) with the helpers add_tap / add_finish_tap, whichever entry point is called.
+// The finish has one wrapper kernel: a single tap is a batch of one.  The partial sums keep two wrappers per body: the
+// batched one, and the same body behind direct arguments for a batch of one, because the batched wrapper measured
+// slower for a single tap (profiles/EXPERIMENTS.md 3.2); launch_partial picks between them in one place.
+//   partial sums: gram_partial_body<T,TS,X3>   fp32 MFMA on widened features; X3: split-bf16 products
+//                 gram_partial_bf16_body<TS>   bf16 MFMA fed by transposing LDS reads (features below 2 GiB)
+//   finish:       gram_finish_body<T,FIN_S>
 #include <stdlib.h>
 
 #include "stv_common.h"
@@ -195,9 +203,9 @@ __device__ __forceinline__ void gram_partial_body(const T* __restrict__ F, float
       }
 }
 
-// One batched launch covers several taps (layers): blocks [block0[i], block0[i+1]) belong to tap i.
-// The Gram chain of a step is five small, latency-bound problems; side by side in one grid they
-// take the time of the slowest instead of the sum.
+// One launch covers a batch of taps (layers): blocks [block0[i], block0[i+1]) belong to tap i, and within a tap block b
+// is tile pair b % pairs of slab b / pairs.  The Gram chain of a step is five small, latency-bound problems; side by
+// side in one grid they take the time of the slowest instead of the sum.  A single tap is a batch of one.
 constexpr int kMaxTaps = 8;
 struct PartialMulti {
   int n;
@@ -217,12 +225,16 @@ __device__ __forceinline__ void decode_block(int b, int pairs, int ksplit, int& 
   ks = b / pairs;
 }
 
+// A batch of one keeps direct arguments: through the batched wrapper every workgroup first walks block0 and then
+// fetches its operands by tap index, which measured +1.2 us on the 18 us bf16 tap of 1024^2 and +0.4 us on the 27 us
+// fp32 tap of 512^2 - more than the run-to-run spread of those launches.
+using PartialSingleFn = void (*)(const void*, float*, int, int, int, int, int);
 template <typename T, int TS, bool X3 = false>
-__global__ __launch_bounds__(256) void gram_partial_kernel(const T* __restrict__ F, float* __restrict__ partials,
+__global__ __launch_bounds__(256) void gram_partial_kernel(const void* __restrict__ F, float* __restrict__ partials,
                                                            int N, int C, int ksplit, int chunk, int pairs) {
   int pair, ks;
   decode_block(blockIdx.x, pairs, ksplit, pair, ks);
-  gram_partial_body<T, TS, X3>(F, partials, N, C, ksplit, chunk, pair, ks);
+  gram_partial_body<T, TS, X3>(static_cast<const T*>(F), partials, N, C, ksplit, chunk, pair, ks);
 }
 template <typename T, int TS, bool X3 = false>
 __global__ __launch_bounds__(256) void gram_partial_multi_kernel(PartialMulti m) {
@@ -420,11 +432,11 @@ __device__ __forceinline__ void gram_partial_bf16_body(const bf16_t* __restrict_
 }
 
 template <int TS>
-__global__ __launch_bounds__(256) void gram_partial_bf16_kernel(const bf16_t* __restrict__ F, float* __restrict__ partials,
+__global__ __launch_bounds__(256) void gram_partial_bf16_kernel(const void* __restrict__ F, float* __restrict__ partials,
                                                                 int N, int C, int ksplit, int chunk, int pairs) {
   int pair, ks;
   decode_block(blockIdx.x, pairs, ksplit, pair, ks);
-  gram_partial_bf16_body<TS>(F, partials, N, C, ksplit, chunk, pair, ks);
+  gram_partial_bf16_body<TS>(static_cast<const bf16_t*>(F), partials, N, C, ksplit, chunk, pair, ks);
 }
 template <int TS>
 __global__ __launch_bounds__(256) void gram_partial_bf16_multi_kernel(PartialMulti m) {
@@ -538,15 +550,6 @@ __device__ __forceinline__ void gram_finish_body(
   }
 }
 
-template <typename T, int FIN_S>
-__global__ __launch_bounds__(FIN_L * FIN_S) void gram_finish_kernel(
-    const float* __restrict__ partials, const float* __restrict__ target, float* __restrict__ gram_out,
-    float* __restrict__ loss_part, T* __restrict__ sgrad, int C, int TS, int ksplit, float clamp_max,
-    float norm, float k_grad, const float* __restrict__ coef_dev) {
-  gram_finish_body<T, FIN_S>(partials, target, gram_out, loss_part, sgrad, C, TS, ksplit, clamp_max, norm, k_grad, coef_dev,
-                             blockIdx.x);
-}
-
 struct FinishMulti {
   int n;
   int block0[kMaxTaps + 1];
@@ -567,43 +570,78 @@ __global__ __launch_bounds__(FIN_L * FIN_S) void gram_finish_multi_kernel(Finish
                          blockIdx.x - m.block0[i]);
 }
 
-template <int TS>
-int launch_bf16(const bf16_t* F, float* partials, int N, int C, int pairs, int ksplit, hipStream_t st) {
-  int chunk = ceil_div(N, ksplit);
-  chunk = ceil_div(chunk, PKB) * PKB;
-  if (stv_set_max_lds(reinterpret_cast<const void*>(&gram_partial_bf16_kernel<TS>), GramBCfg<TS>::LDS_BYTES) != STV_OK)
-    return STV_ERR_LAUNCH;
-  hipLaunchKernelGGL((gram_partial_bf16_kernel<TS>), dim3(pairs * ksplit), dim3(256), GramBCfg<TS>::LDS_BYTES, st,
-                     F, partials, N, C, ksplit, chunk, pairs);
+// ---- host side: one entry per tap, one launch helper per pass ---------------------------------------------------------
+// Appends a tap to a partial-sum batch: its tile pairs, its slabs (stv_gram_ksplit) and the pixels per slab, a whole
+// number of the body's LDS stages (pk: PKB for the transposing-read body, PK otherwise).
+void add_tap(PartialMulti& m, const void* F, float* partials, int N, int C, int pk) {
+  const int nt = ceil_div(C, gram_tile(C)), pairs = nt * (nt + 1) / 2;
+  const int ksplit = stv_gram_ksplit(N, C);
+  const int k = m.n++;
+  m.F[k] = F; m.partials[k] = partials; m.N[k] = N; m.C[k] = C;
+  m.ksplit[k] = ksplit; m.chunk[k] = ceil_div(ceil_div(N, ksplit), pk) * pk; m.pairs[k] = pairs;
+  m.block0[k + 1] = m.block0[k] + pairs * ksplit;
+}
+
+// The partial-sum kernels by body and tile size.  The first three bodies carry the dtype codes of stv.h; the fourth is
+// the fp32-MFMA body reading bf16 features, for maps of 2 GiB and more: their byte count does not fit the 32-bit
+// sizes and offsets of the transposing-read body's buffer loads.
+enum { BODY_F32 = STV_F32, BODY_BF16 = STV_BF16, BODY_X3 = STV_BF16X3, BODY_BF16_WIDE };
+static_assert(BODY_F32 == 0 && BODY_BF16 == 1 && BODY_X3 == 2, "the table below is indexed by dtype code");
+struct PartialKernel {
+  PartialSingleFn single;          // a batch of one
+  void (*multi)(PartialMulti);     // nullptr: stv_gram_multi refuses such taps
+  int lds;
+};
+#define STV_GENERIC(T, X3, TS) {gram_partial_kernel<T, TS, X3>, gram_partial_multi_kernel<T, TS, X3>, GramCfg<TS>::LDS_BYTES}
+const PartialKernel kPartialKernels[4][2] = {      // [body][TS == 128]
+    {STV_GENERIC(float, false, 64), STV_GENERIC(float, false, 128)},
+    {{gram_partial_bf16_kernel<64>, gram_partial_bf16_multi_kernel<64>, GramBCfg<64>::LDS_BYTES},
+     {gram_partial_bf16_kernel<128>, gram_partial_bf16_multi_kernel<128>, GramBCfg<128>::LDS_BYTES}},
+    {STV_GENERIC(float, true, 64), STV_GENERIC(float, true, 128)},
+    {{gram_partial_kernel<bf16_t, 64>, nullptr, GramCfg<64>::LDS_BYTES}, {gram_partial_kernel<bf16_t, 128>, nullptr, GramCfg<128>::LDS_BYTES}},
+};
+#undef STV_GENERIC
+constexpr int kBothLds = GramBCfg<128>::LDS_BYTES > GramBCfg<64>::LDS_BYTES ? GramBCfg<128>::LDS_BYTES : GramBCfg<64>::LDS_BYTES;
+
+inline int pixels_per_stage(int body) { return body == BODY_BF16 ? PKB : PK; }
+
+int launch_partial(int body, int TS, const PartialMulti& m, hipStream_t st) {
+  const PartialKernel& k = kPartialKernels[body][TS == 128];
+  const dim3 grid(m.block0[m.n]), block(256);
+  if (m.n == 1) {
+    if (stv_set_max_lds(reinterpret_cast<const void*>(k.single), k.lds) != STV_OK) return STV_ERR_LAUNCH;
+    hipLaunchKernelGGL(k.single, grid, block, k.lds, st, m.F[0], m.partials[0], m.N[0], m.C[0], m.ksplit[0], m.chunk[0], m.pairs[0]);
+  } else {
+    if (!k.multi) return STV_ERR_ARG;
+    if (stv_set_max_lds(reinterpret_cast<const void*>(k.multi), k.lds) != STV_OK) return STV_ERR_LAUNCH;
+    hipLaunchKernelGGL(k.multi, grid, block, k.lds, st, m);
+  }
   STV_CHECK_LAUNCH();
   return STV_OK;
 }
 
-template <typename T, bool X3 = false>
-int partial_typed(const void* F, float* partials, int N, int C, hipStream_t st) {
-  const int TS = gram_tile(C);
-  const int nt = ceil_div(C, TS);
-  const int pairs = nt * (nt + 1) / 2;
-  const int ksplit = stv_gram_ksplit(N, C);
-  if (std::is_same<T, bf16_t>::value && (size_t)N * C * 2 < ((size_t)1 << 31)) {
-    const bf16_t* Fb = static_cast<const bf16_t*>(F);
-    return TS == 64 ? launch_bf16<64>(Fb, partials, N, C, pairs, ksplit, st)
-                    : launch_bf16<128>(Fb, partials, N, C, pairs, ksplit, st);
-  }
-  int chunk = ceil_div(N, ksplit);
-  chunk = ceil_div(chunk, PK) * PK;
-  dim3 grid(pairs * ksplit);
-  if (TS == 64) {
-    hipLaunchKernelGGL((gram_partial_kernel<T, 64, X3>), grid, dim3(256), GramCfg<64>::LDS_BYTES, st,
-                       static_cast<const T*>(F), partials, N, C, ksplit, chunk, pairs);
-  } else {
-    if (stv_set_max_lds(reinterpret_cast<const void*>(&gram_partial_kernel<T, 128, X3>), GramCfg<128>::LDS_BYTES) != STV_OK)
-      return STV_ERR_LAUNCH;
-    hipLaunchKernelGGL((gram_partial_kernel<T, 128, X3>), grid, dim3(256), GramCfg<128>::LDS_BYTES, st,
-                       static_cast<const T*>(F), partials, N, C, ksplit, chunk, pairs);
-  }
+// Appends a tap to a finish batch.
+void add_finish_tap(FinishMulti& f, const stv_gram_tap_t& t) {
+  const int k = f.n++;
+  f.partials[k] = t.partials; f.target[k] = t.target; f.gram_out[k] = t.gram_out; f.loss_part[k] = t.loss_part;
+  f.sgrad[k] = t.sgrad; f.coef_dev[k] = t.coef_dev; f.C[k] = t.channels; f.TS[k] = gram_tile(t.channels);
+  f.ksplit[k] = stv_gram_ksplit(t.n_pixels, t.channels);
+  f.clamp_max[k] = t.clamp_max; f.norm[k] = t.norm;
+  // d(mean((G-T)^2))/dR = 2/C^2 * (G-T) / norm ; dF = (dR + dR^T) F = 2 dR F
+  f.k_grad[k] = t.coef * 4.0f / ((float)t.channels * (float)t.channels * t.norm);
+  f.block0[k + 1] = f.block0[k] + stv_gram_loss_parts(t.channels);
+}
+
+template <typename T, int S>
+int launch_finish_as(const FinishMulti& f, hipStream_t st) {
+  hipLaunchKernelGGL((gram_finish_multi_kernel<T, S>), dim3(f.block0[f.n]), dim3(FIN_L * S), 0, st, f);
   STV_CHECK_LAUNCH();
   return STV_OK;
+}
+// deep: 32 slices per element instead of 8 (FIN_S above)
+int launch_finish(const FinishMulti& f, bool bf16_seed, bool deep, hipStream_t st) {
+  if (bf16_seed) return deep ? launch_finish_as<bf16_t, 32>(f, st) : launch_finish_as<bf16_t, 8>(f, st);
+  return deep ? launch_finish_as<float, 32>(f, st) : launch_finish_as<float, 8>(f, st);
 }
 
 }  // namespace
@@ -639,51 +677,29 @@ extern "C" int stv_gram_loss_parts(int channels) { return ceil_div(channels * ch
 extern "C" int stv_gram_partial(const void* F, float* partials, int n_pixels, int C, int dtype,
                                 void* stream) {
   if (!F || !partials || n_pixels <= 0 || C <= 0) return STV_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == STV_F32) {
-    if (C % 4) return STV_ERR_ARG;
-    return partial_typed<float>(F, partials, n_pixels, C, st);
-  }
-  if (dtype == STV_BF16) {
-    if (C % 8) return STV_ERR_ARG;
-    return partial_typed<bf16_t>(F, partials, n_pixels, C, st);
-  }
-  if (dtype == STV_BF16X3) {     // the fp32 path's layout and granularity; the byte guard counts bytes
-    if (C % 4 || (size_t)n_pixels * C * 4 >= ((size_t)1 << 31)) return STV_ERR_ARG;
-    return partial_typed<float, true>(F, partials, n_pixels, C, st);
-  }
-  return STV_ERR_ARG;
+  if (dtype != STV_F32 && dtype != STV_BF16 && dtype != STV_BF16X3) return STV_ERR_ARG;
+  const bool bf16 = dtype == STV_BF16;
+  if (C % (bf16 ? 8 : 4)) return STV_ERR_ARG;
+  const bool huge = (size_t)n_pixels * C * (bf16 ? 2 : 4) >= ((size_t)1 << 31);
+  if (dtype == STV_BF16X3 && huge) return STV_ERR_ARG;     // the fp32 path's layout and granularity; the guard counts bytes
+  const int body = (bf16 && huge) ? BODY_BF16_WIDE : dtype;
+  PartialMulti m{};
+  add_tap(m, F, partials, n_pixels, C, pixels_per_stage(body));
+  return launch_partial(body, gram_tile(C), m, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int stv_gram_finish(const float* partials, const float* target, float* gram_out,
                                float* loss_part, void* sgrad, int n_pixels, int C, float clamp_max,
                                float norm, float coef, const float* coef_dev, int dtype, void* stream) {
   if (!partials || n_pixels <= 0 || C <= 0 || norm <= 0.0f) return STV_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int ksplit = stv_gram_ksplit(n_pixels, C);
-  const int TS = gram_tile(C);
-  const int blocks = stv_gram_loss_parts(C);
-  // d(mean((G-T)^2))/dR = 2/C^2 * (G-T) / norm ; dF = (dR + dR^T) F = 2 dR F
-  const float k_grad = coef * 4.0f / ((float)C * (float)C * norm);
-  const bool deep = ksplit >= 128;
-#define STV_FINISH(T, S)                                                                                     \
-  hipLaunchKernelGGL((gram_finish_kernel<T, S>), dim3(blocks), dim3(FIN_L * S), 0, st, partials, target,    \
-                     gram_out, loss_part, static_cast<T*>(sgrad), C, TS, ksplit, clamp_max, norm, k_grad, coef_dev)
-  if (dtype == STV_F32) {
-    if (deep) STV_FINISH(float, 32);
-    else STV_FINISH(float, 8);
-  } else if (dtype == STV_BF16) {
-    if (deep) STV_FINISH(bf16_t, 32);
-    else STV_FINISH(bf16_t, 8);
-  }
-#undef STV_FINISH
-  else
-    return STV_ERR_ARG;
-  STV_CHECK_LAUNCH();
-  return STV_OK;
+  if (dtype != STV_F32 && dtype != STV_BF16) return STV_ERR_ARG;
+  FinishMulti f{};
+  add_finish_tap(f, stv_gram_tap_t{nullptr, const_cast<float*>(partials), target, gram_out, loss_part, sgrad, coef_dev,
+                                   n_pixels, C, clamp_max, norm, coef});
+  return launch_finish(f, dtype == STV_BF16, f.ksplit[0] >= 128, static_cast<hipStream_t>(stream));
 }
 
-// ---- batched Gram chain: all taps of a step in two (partial: one per tile size) + one launches ----
+// ---- batched Gram chain: all taps of a step in one launch per pass (partial sums: one per tile size present) ----
 extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype, void* stream) {
   if (!taps || n_taps <= 0 || n_taps > kMaxTaps) return STV_ERR_ARG;
   if (dtype != STV_F32 && dtype != STV_BF16 && dtype != STV_BF16X3) return STV_ERR_ARG;
@@ -697,86 +713,31 @@ extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype,
     if (x3 && t.F && (size_t)t.n_pixels * t.channels * 4 >= ((size_t)1 << 31)) return STV_ERR_ARG;
   }
   // partial sums: one launch per tile size present (bf16 with both sizes present: one launch for both)
-  PartialMulti held{};                       // the 64-wide taps, waiting for the 128-wide ones
-  for (int TS : {64, 128}) {
-    PartialMulti m{};
-    for (int i = 0; i < n_taps; ++i) {
-      const stv_gram_tap_t& t = taps[i];
-      if (gram_tile(t.channels) != TS || !t.F) continue;      // F == NULL: the producer left the slabs (stv_conv_first_fwd_gram)
-      const int nt = ceil_div(t.channels, TS), pairs = nt * (nt + 1) / 2;
-      const int ksplit = stv_gram_ksplit(t.n_pixels, t.channels);
-      const int pk = dtype == STV_BF16 ? PKB : PK;
-      int chunk = ceil_div(t.n_pixels, ksplit);
-      chunk = ceil_div(chunk, pk) * pk;
-      const int k = m.n++;
-      m.F[k] = t.F; m.partials[k] = t.partials; m.N[k] = t.n_pixels; m.C[k] = t.channels;
-      m.ksplit[k] = ksplit; m.chunk[k] = chunk; m.pairs[k] = pairs;
-      m.block0[k + 1] = m.block0[k] + pairs * ksplit;
-    }
-    if (dtype == STV_BF16 && TS == 64 && m.n) {
-      bool wide = false;
-      for (int i = 0; i < n_taps; ++i) wide |= gram_tile(taps[i].channels) == 128 && taps[i].F != nullptr;
-      if (wide) { held = m; continue; }
-    }
-    if (!m.n) continue;
-    if (dtype == STV_BF16 && TS == 128 && held.n) {
-      constexpr int lds = GramBCfg<128>::LDS_BYTES > GramBCfg<64>::LDS_BYTES ? GramBCfg<128>::LDS_BYTES : GramBCfg<64>::LDS_BYTES;
-      if (stv_set_max_lds(reinterpret_cast<const void*>(&gram_partial_bf16_both_kernel), lds) != STV_OK) return STV_ERR_LAUNCH;
-      hipLaunchKernelGGL(gram_partial_bf16_both_kernel, dim3(m.block0[m.n] + held.block0[held.n]), dim3(256), lds, st, m, held);
-      STV_CHECK_LAUNCH();
-      continue;
-    }
-    const dim3 grid(m.block0[m.n]);
-#define STV_SET_LDS(kern, bytes)                                                                             \
-  do {                                                                                                       \
-    if (stv_set_max_lds(reinterpret_cast<const void*>(&kern), bytes) != STV_OK) return STV_ERR_LAUNCH;      \
-  } while (0)
-    if (dtype == STV_BF16) {
-      if (TS == 64) {
-        STV_SET_LDS(gram_partial_bf16_multi_kernel<64>, GramBCfg<64>::LDS_BYTES);
-        hipLaunchKernelGGL(gram_partial_bf16_multi_kernel<64>, grid, dim3(256), GramBCfg<64>::LDS_BYTES, st, m);
-      } else {
-        STV_SET_LDS(gram_partial_bf16_multi_kernel<128>, GramBCfg<128>::LDS_BYTES);
-        hipLaunchKernelGGL(gram_partial_bf16_multi_kernel<128>, grid, dim3(256), GramBCfg<128>::LDS_BYTES, st, m);
-      }
-    } else if (x3) {
-      if (TS == 64) {
-        STV_SET_LDS((gram_partial_multi_kernel<float, 64, true>), GramCfg<64>::LDS_BYTES);
-        hipLaunchKernelGGL((gram_partial_multi_kernel<float, 64, true>), grid, dim3(256), GramCfg<64>::LDS_BYTES, st, m);
-      } else {
-        STV_SET_LDS((gram_partial_multi_kernel<float, 128, true>), GramCfg<128>::LDS_BYTES);
-        hipLaunchKernelGGL((gram_partial_multi_kernel<float, 128, true>), grid, dim3(256), GramCfg<128>::LDS_BYTES, st, m);
-      }
-    } else {
-      if (TS == 64) {
-        STV_SET_LDS((gram_partial_multi_kernel<float, 64>), GramCfg<64>::LDS_BYTES);
-        hipLaunchKernelGGL((gram_partial_multi_kernel<float, 64>), grid, dim3(256), GramCfg<64>::LDS_BYTES, st, m);
-      } else {
-        STV_SET_LDS((gram_partial_multi_kernel<float, 128>), GramCfg<128>::LDS_BYTES);
-        hipLaunchKernelGGL((gram_partial_multi_kernel<float, 128>), grid, dim3(256), GramCfg<128>::LDS_BYTES, st, m);
-      }
-    }
-#undef STV_SET_LDS
+  PartialMulti by_tile[2] = {};              // [TS == 128]
+  for (int i = 0; i < n_taps; ++i) {
+    const stv_gram_tap_t& t = taps[i];
+    if (!t.F) continue;                      // F == NULL: the producer left the slabs (stv_conv_first_fwd_gram)
+    add_tap(by_tile[gram_tile(t.channels) == 128], t.F, t.partials, t.n_pixels, t.channels, pixels_per_stage(dtype));
+  }
+  const PartialMulti& m64 = by_tile[0];
+  const PartialMulti& m128 = by_tile[1];
+  if (dtype == STV_BF16 && m64.n && m128.n) {
+    if (stv_set_max_lds(reinterpret_cast<const void*>(&gram_partial_bf16_both_kernel), kBothLds) != STV_OK) return STV_ERR_LAUNCH;
+    hipLaunchKernelGGL(gram_partial_bf16_both_kernel, dim3(m128.block0[m128.n] + m64.block0[m64.n]), dim3(256), kBothLds, st,
+                       m128, m64);
     STV_CHECK_LAUNCH();
+  } else {
+    for (int TS : {64, 128}) {
+      const PartialMulti& m = by_tile[TS == 128];
+      if (!m.n) continue;
+      if (const int rc = launch_partial(dtype, TS, m, st)) return rc;
+    }
   }
   // finish: one launch for all taps, 8 slices per element (it measured faster than a second, 1024-thread launch with
   // 32 slices per element for the many-slab tap: 14 + 8 us -> ~15 us at 512^2)
   FinishMulti f{};
-  for (int i = 0; i < n_taps; ++i) {
-    const stv_gram_tap_t& t = taps[i];
-    const int k = f.n++;
-    f.partials[k] = t.partials; f.target[k] = t.target; f.gram_out[k] = t.gram_out; f.loss_part[k] = t.loss_part;
-    f.sgrad[k] = t.sgrad; f.coef_dev[k] = t.coef_dev; f.C[k] = t.channels; f.TS[k] = gram_tile(t.channels);
-    f.ksplit[k] = stv_gram_ksplit(t.n_pixels, t.channels);
-    f.clamp_max[k] = t.clamp_max; f.norm[k] = t.norm;
-    f.k_grad[k] = t.coef * 4.0f / ((float)t.channels * (float)t.channels * t.norm);
-    f.block0[k + 1] = f.block0[k] + stv_gram_loss_parts(t.channels);
-  }
-  const dim3 grid(f.block0[f.n]);
-  if (dtype != STV_BF16) hipLaunchKernelGGL((gram_finish_multi_kernel<float, 8>), grid, dim3(FIN_L * 8), 0, st, f);
-  else hipLaunchKernelGGL((gram_finish_multi_kernel<bf16_t, 8>), grid, dim3(FIN_L * 8), 0, st, f);
-  STV_CHECK_LAUNCH();
-  return STV_OK;
+  for (int i = 0; i < n_taps; ++i) add_finish_tap(f, taps[i]);
+  return launch_finish(f, dtype == STV_BF16, false, st);
 }
 
 #ifdef STV_GRAM_STAMPS

@@ -1,8 +1,11 @@
 // HBM-bound pointwise / small-reduction kernels around the conv stacks:
 // MaxPool2d(2,2) forward/backward, ReLU forward/backward, content MSE and its
-// gradient, the total variation of the image and its gradient, the 2x resize
-// between the levels of a coarse-to-fine run, and the final score combine.  All activation traffic is 16-byte
-// vectors per lane (1 KiB per wave instruction); grids are capped and
+// gradient (content_loss_kernel<T, GRAD>: the loss partials alone or, in the
+// same loop, with the gradient written; content_grad_kernel: the gradient
+// alone, scaled by a device scalar and optionally accumulated), the total
+// variation of the image and its gradient, the 2x resize between the levels of
+// a coarse-to-fine run, and the final score combine.  All activation traffic is
+// 16-byte vectors per lane (1 KiB per wave instruction); grids are capped and
 // grid-strided.
 #include <string.h>
 
@@ -247,60 +250,37 @@ __device__ __forceinline__ float block_sum_1024(float v, float* smem16) {
   for (int i = 0; i < kContentThreads / 64; ++i) s += smem16[i];
   return s;
 }
-template <typename T>
+// GRAD: loss and gradient of the content term in one pass over (F, target) - the same partial sums in the same order
+// (same grid, same stride), and dF = coef * 2/n * (F - target) WRITTEN (the dgrad that produces this layer's gradient
+// later accumulates onto it): one read of the two maps instead of two.
+template <typename T, bool GRAD>
 __global__ __launch_bounds__(kContentThreads) void content_loss_kernel(const T* __restrict__ f, const T* __restrict__ t,
-                                                                       float* __restrict__ part, size_t n) {
+                                                                       float* __restrict__ part, T* __restrict__ df, size_t n,
+                                                                       float coef) {
   constexpr int kVec = elem_traits<T>::kVec;
   constexpr int BT = kContentThreads;
   __shared__ float red[BT / 64];
+  float k = 0.0f;
+  if constexpr (GRAD) k = coef * (2.0f / (float)n);
   float s = 0.0f;
   const size_t nv = n / kVec;
   for (size_t i = (size_t)blockIdx.x * BT + threadIdx.x; i < nv; i += (size_t)gridDim.x * BT) {
     float a[kVec], b[kVec];
+    [[maybe_unused]] float o[kVec];
     unpack16<T>(reinterpret_cast<const u32x4*>(f)[i], a);
     unpack16<T>(reinterpret_cast<const u32x4*>(t)[i], b);
 #pragma unroll
     for (int e = 0; e < kVec; ++e) {
       const float d = a[e] - b[e];
       s = fmaf(d, d, s);
+      if constexpr (GRAD) o[e] = k * d;
     }
+    if constexpr (GRAD) reinterpret_cast<u32x4*>(df)[i] = pack16<T>(o);
   }
   for (size_t i = nv * kVec + (size_t)blockIdx.x * BT + threadIdx.x; i < n; i += (size_t)gridDim.x * BT) {
     const float d = elem_traits<T>::load(f + i) - elem_traits<T>::load(t + i);
     s = fmaf(d, d, s);
-  }
-  s = block_sum_1024(s, red);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-// Loss and gradient of the content term in one pass over (F, target): the same partial sums in the same
-// order as content_loss_kernel (same grid, same stride), and dF = coef * 2/n * (F - target) WRITTEN (the dgrad
-// that produces this layer's gradient later accumulates onto it) - one read of the two maps instead of two.
-template <typename T>
-__global__ __launch_bounds__(kContentThreads) void content_loss_grad_kernel(const T* __restrict__ f, const T* __restrict__ t,
-                                                                            float* __restrict__ part, T* __restrict__ df, size_t n,
-                                                                            float coef) {
-  constexpr int kVec = elem_traits<T>::kVec;
-  constexpr int BT = kContentThreads;
-  __shared__ float red[BT / 64];
-  const float k = coef * (2.0f / (float)n);
-  float s = 0.0f;
-  const size_t nv = n / kVec;
-  for (size_t i = (size_t)blockIdx.x * BT + threadIdx.x; i < nv; i += (size_t)gridDim.x * BT) {
-    float a[kVec], b[kVec], o[kVec];
-    unpack16<T>(reinterpret_cast<const u32x4*>(f)[i], a);
-    unpack16<T>(reinterpret_cast<const u32x4*>(t)[i], b);
-#pragma unroll
-    for (int e = 0; e < kVec; ++e) {
-      const float d = a[e] - b[e];
-      s = fmaf(d, d, s);
-      o[e] = k * d;
-    }
-    reinterpret_cast<u32x4*>(df)[i] = pack16<T>(o);
-  }
-  for (size_t i = nv * kVec + (size_t)blockIdx.x * BT + threadIdx.x; i < n; i += (size_t)gridDim.x * BT) {
-    const float d = elem_traits<T>::load(f + i) - elem_traits<T>::load(t + i);
-    s = fmaf(d, d, s);
-    elem_traits<T>::store(df + i, k * d);
+    if constexpr (GRAD) elem_traits<T>::store(df + i, k * d);
   }
   s = block_sum_1024(s, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
@@ -771,35 +751,33 @@ extern "C" int stv_relu_bwd(const void* x, const void* dy, void* dx, size_t n, i
   return STV_OK;
 }
 
+// dF == nullptr: the loss partials alone
+template <typename T>
+static void launch_content_loss(const void* F, const void* target, float* loss_part, void* dF, size_t n, float coef, hipStream_t st) {
+  const dim3 grid(STV_CONTENT_LOSS_PARTS), block(kContentThreads);
+  const T* f = static_cast<const T*>(F);
+  const T* t = static_cast<const T*>(target);
+  if (dF) hipLaunchKernelGGL((content_loss_kernel<T, true>), grid, block, 0, st, f, t, loss_part, static_cast<T*>(dF), n, coef);
+  else hipLaunchKernelGGL((content_loss_kernel<T, false>), grid, block, 0, st, f, t, loss_part, static_cast<T*>(nullptr), n, 0.0f);
+}
+static int content_loss(const void* F, const void* target, float* loss_part, void* dF, size_t n, float coef, int dtype,
+                        void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == STV_F32) launch_content_loss<float>(F, target, loss_part, dF, n, coef, st);
+  else if (dtype == STV_BF16) launch_content_loss<bf16_t>(F, target, loss_part, dF, n, coef, st);
+  else return STV_ERR_ARG;
+  STV_CHECK_LAUNCH();
+  return STV_OK;
+}
 extern "C" int stv_content_loss(const void* F, const void* target, float* loss_part, size_t n, int dtype,
                                 void* stream) {
   if (!F || !target || !loss_part || n == 0) return STV_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == STV_F32)
-    hipLaunchKernelGGL(content_loss_kernel<float>, dim3(STV_CONTENT_LOSS_PARTS), dim3(kContentThreads), 0, st,
-                       static_cast<const float*>(F), static_cast<const float*>(target), loss_part, n);
-  else if (dtype == STV_BF16)
-    hipLaunchKernelGGL(content_loss_kernel<bf16_t>, dim3(STV_CONTENT_LOSS_PARTS), dim3(kContentThreads), 0, st,
-                       static_cast<const bf16_t*>(F), static_cast<const bf16_t*>(target), loss_part, n);
-  else
-    return STV_ERR_ARG;
-  STV_CHECK_LAUNCH();
-  return STV_OK;
+  return content_loss(F, target, loss_part, nullptr, n, 0.0f, dtype, stream);
 }
 extern "C" int stv_content_loss_grad(const void* F, const void* target, float* loss_part, void* dF, size_t n, float coef,
                                      int dtype, void* stream) {
   if (!F || !target || !loss_part || !dF || n == 0) return STV_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == STV_F32)
-    hipLaunchKernelGGL(content_loss_grad_kernel<float>, dim3(STV_CONTENT_LOSS_PARTS), dim3(kContentThreads), 0, st,
-                       static_cast<const float*>(F), static_cast<const float*>(target), loss_part, static_cast<float*>(dF), n, coef);
-  else if (dtype == STV_BF16)
-    hipLaunchKernelGGL(content_loss_grad_kernel<bf16_t>, dim3(STV_CONTENT_LOSS_PARTS), dim3(kContentThreads), 0, st,
-                       static_cast<const bf16_t*>(F), static_cast<const bf16_t*>(target), loss_part, static_cast<bf16_t*>(dF), n, coef);
-  else
-    return STV_ERR_ARG;
-  STV_CHECK_LAUNCH();
-  return STV_OK;
+  return content_loss(F, target, loss_part, dF, n, coef, dtype, stream);
 }
 extern "C" int stv_content_grad(const void* F, const void* target, void* dF, size_t n, float coef,
                                 const float* coef_dev, int flags, int dtype, void* stream) {

@@ -283,24 +283,19 @@ def gram_multi(feats: list[torch.Tensor], targets: list[torch.Tensor], *, coef: 
     ``coef_dev``: a one-element fp32 device tensor every tap's seed is multiplied by."""
     lib = _lib.load()
     table = (_lib.StvGramTap * len(feats))()
-    keep, grams, parts, seeds = [], [], [], []
+    slabs, grams, parts, seeds = [], [], [], []
     for e, f, t in zip(table, feats, targets, strict=True):
         H, W, C = f.shape
         n = H * W
-        partials = torch.empty(gram_ksplit(n, C), C, C, device=f.device, dtype=torch.float32)
-        g = torch.empty(C, C, device=f.device, dtype=torch.float32)
-        lp = torch.empty(gram_loss_parts(C), device=f.device, dtype=torch.float32)
-        sg = torch.empty(C, C, device=f.device, dtype=f.dtype)
-        keep += [partials]
-        grams.append(g); parts.append(lp); seeds.append(sg)
-        e.F, e.partials, e.target, e.gram_out, e.loss_part, e.sgrad = (_ptr(f), _ptr(partials), _ptr(t), _ptr(g), _ptr(lp),
-                                                                      _ptr(sg))
-        e.coef_dev = _ptr(coef_dev)
-        e.n_pixels, e.channels = n, C
-        e.clamp_max, e.norm, e.coef = clamp_max, float(C * n), coef
+        slabs.append(torch.empty(gram_ksplit(n, C), C, C, device=f.device, dtype=torch.float32))
+        grams.append(torch.empty(C, C, device=f.device, dtype=torch.float32))
+        parts.append(torch.empty(gram_loss_parts(C), device=f.device, dtype=torch.float32))
+        seeds.append(torch.empty(C, C, device=f.device, dtype=f.dtype))
+        e.fill(n_pixels=n, channels=C, clamp_max=clamp_max, coef=coef, F=_ptr(f), partials=_ptr(slabs[-1]), target=_ptr(t),
+               gram_out=_ptr(grams[-1]), loss_part=_ptr(parts[-1]), sgrad=_ptr(seeds[-1]), coef_dev=_ptr(coef_dev))
     _lib.check(lib.stv_gram_multi(ctypes.addressof(table), len(feats), dtype_code(feats[0].dtype), _stream()),
                "stv_gram_multi")
-    torch.cuda.current_stream().synchronize()       # `partials` may go out of scope now
+    torch.cuda.current_stream().synchronize()       # the slabs may go out of scope now
     return grams, parts, seeds
 
 

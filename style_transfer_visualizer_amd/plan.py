@@ -471,12 +471,9 @@ class Schedule:
         for e, sp in zip(table, specs, strict=True):
             tap = sp["tap"]
             b = tap.buf
-            n = b.H * b.W
-            e.F, e.partials = (None if (tap.partials_fused or sp.get("partials_ready")) else ptr(b.act)), ptr(self._partials(tap))
-            e.target, e.gram_out, e.loss_part = ptr(sp.get("target")), ptr(sp.get("gram_out")), ptr(sp.get("loss_part"))
-            e.sgrad, e.coef_dev = ptr(sp.get("sgrad")), ptr(sp.get("coef_dev"))
-            e.n_pixels, e.channels = n, b.C
-            e.clamp_max, e.norm, e.coef = GRAM_CLAMP_MAX, float(b.C * n), float(sp.get("coef", 0.0))
+            e.fill(n_pixels=b.H * b.W, channels=b.C, clamp_max=GRAM_CLAMP_MAX, coef=sp.get("coef", 0.0),
+                   F=None if (tap.partials_fused or sp.get("partials_ready")) else ptr(b.act), partials=ptr(self._partials(tap)),
+                   **{k: ptr(sp.get(k)) for k in ("target", "gram_out", "loss_part", "sgrad", "coef_dev")})
         op = self.emit(op=OP_GRAM_MULTI, p0=ctypes.addressof(table), n=len(specs))
         op.refs = refs
         return op

@@ -38,7 +38,7 @@ LIMIT = ei.LIMIT
 PK = 32                                        # pixels per LDS stage (fp32 partial kernel): slabs hold whole stages
 FIN_V, FIN_L, FIN_U = 4, 32, 4
 FIN_E = FIN_L * FIN_V                          # Gram elements (and one loss partial) per finish block
-FIN_S_SHORT, FIN_S_DEEP = 8, 32                # slices per element: gram_finish_kernel<T, 8> / <T, 32>
+FIN_S_SHORT, FIN_S_DEEP = 8, 32                # slices per element: gram_finish_multi_kernel<T, 8> / <T, 32>
 FIN_DEEP_KSPLIT = 128                          # stv_gram_finish: `deep = ksplit >= 128`
 GRAM_WGS, GRAM_WGS_MIN, GRAM_KDIV = 512, 128, 8
 # ---- csrc/pointwise.hip, csrc/optim.hip --------------------------------------------------------------------------------
