@@ -246,7 +246,9 @@ class Schedule:
                             ops.conv_tune(H, W, cout, cin, 9, self.dtype, split=self.split)
                     node = Node("conv", cur, dst, relu_in=pending_relu, layer=i, wf=wf, wb=wb, bias=bias, cin=cin)
                 pending_relu = False
-                if i + 1 <= last and kinds[i + 1] == "relu" and i not in tapped:
+                # (the first-layer kernels have no ReLU epilogue: an untapped first conv leaves z, and its consumer
+                # applies the ReLU while staging, as behind a tapped conv)
+                if i + 1 <= last and kinds[i + 1] == "relu" and i not in tapped and node.kind == "conv":
                     dst.relu_fused = True      # ReLU runs in this conv's epilogue
                     out_idx = i + 1
                 self.nodes.append(node)
