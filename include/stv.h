@@ -303,6 +303,44 @@ enum { STV_RESIZE_DOWN2 = 0, STV_RESIZE_UP2 = 1 };
  * an output of 2 GiB or more. */
 int stv_resize2x(const float* x, float* y, int C, int H, int W, int mode, void* stream);
 
+/* ---- Colour preservation (--preserve-color; no counterpart in the reference; Gatys et al. 2017, "Controlling
+ *      perceptual factors in neural style transfer", section 5).  Since version 107.  Three streaming passes over the
+ *      image, none of them inside the step.  All three take NCHW fp32 [3][H][W] and return STV_ERR_ARG, before any HIP
+ *      call, for a null pointer, a non-positive dimension or 3*H*W*4 >= 2 GiB. ------------------------------------------ */
+/* launch constants: a work item is STV_COLOR_VEC consecutive pixels of one row, read from all three planes; the three
+ * kernels run STV_COLOR_THREADS threads per workgroup; stv_color_stats always launches STV_COLOR_STATS_PARTS workgroups
+ * (one row of `parts` each: the constant is its grid and its grid cap), the other two at most STV_COLOR_MAX_BLOCKS, so
+ * a pass of the capped grid covers STV_COLOR_STATS_PARTS * STV_COLOR_THREADS, respectively STV_COLOR_MAX_BLOCKS *
+ * STV_COLOR_THREADS items.  Vector path (16-byte loads and stores): W % 4 == 0 behind 16-byte aligned bases; otherwise
+ * the same items with guarded scalar accesses, same results in the same order. */
+#define STV_COLOR_VEC 4
+#define STV_COLOR_THREADS 256
+#define STV_COLOR_STATS_PARTS 256
+#define STV_COLOR_MAX_BLOCKS 1024
+/* Raw colour moments.  parts is double [STV_COLOR_STATS_PARTS][9], one row per workgroup, each row
+ *   sum x0, sum x1, sum x2, sum x0x0, sum x0x1, sum x0x2, sum x1x1, sum x1x2, sum x2x2
+ * over that workgroup's pixels; products and sums are formed in double from the fp32 values (a product of two fp32
+ * numbers is exact in double: cov = sum xx / n - mean^2 cancels, and the pass is memory-bound either way).  Fixed order
+ * - thread in item order, then wave, then workgroup -, no atomics; every entry is written, a workgroup without items
+ * writes zeros.  The caller adds the rows (in float64, on the host). */
+int stv_color_stats(const float* x_nchw, double* parts, int H, int W, void* stream);
+/* Per-pixel affine map of the three channels.  m12: HOST array of 12 floats, the row-major 3x3 matrix m followed by the
+ * offset b, passed by value into the launch (as stv_image_to_u8 takes mean3 / std3).
+ *   y[c] = ((m[c][0]*x[0] + m[c][1]*x[1]) + m[c][2]*x[2]) + b[c]
+ * every product and every sum rounded to fp32 on its own, in that order (no FMA contraction).  y == x (in place) is
+ * allowed; any other overlap of the two ranges is STV_ERR_ARG. */
+int stv_color_affine(const float* x_nchw, float* y_nchw, const float* m12, int H, int W, void* stream);
+/* Luminance of `result`, chrominance of `content`.  mean3 / std3: HOST arrays of 3 floats, or both NULL for an
+ * un-normalised image.  Per pixel and channel c, every operation rounded to fp32 on its own:
+ *   r_c = result[c]*std[c] + mean[c]  (result[c] when un-normalised), then prepare_image_for_output's rule
+ *         (image_io.py:129-152): nan -> 0, +inf -> 1, -inf -> 0, clamp to [0,1];  k_c: the same function of content[c];
+ *   Yr = (0.299f*r_0 + 0.587f*r_1) + 0.114f*r_2  (Rec.601), Yk likewise;  d = Yr - Yk;  o_c = k_c + d;
+ *   out[c] = (o_c - mean[c]) * inv_std[c], inv_std[c] = 1.0f / std[c] formed on the host  (out[c] = o_c un-normalised).
+ * o_c is not clamped: the export path (stv_image_to_u8) clamps.  out == result is allowed.  STV_ERR_ARG also for
+ * out == content or any other overlap of `out` with an input, and for one of mean3 / std3 without the other. */
+int stv_luma_transfer(const float* result, const float* content, float* out, int H, int W, const float* mean3,
+                      const float* std3, void* stream);
+
 /* ---- Frame / PNG export: prepare_image_for_output (image_io.py:129-152: denormalise,
  *      nan_to_num(nan=0, posinf=1, neginf=0), clamp 0..1) fused with the uint8 conversion, on the
  *      device, so only H*W*3 bytes cross to the host.  x NCHW fp32 [3][H][W] -> out HWC uint8.

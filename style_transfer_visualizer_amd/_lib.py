@@ -30,6 +30,10 @@ RESIZE_DOWN2, RESIZE_UP2 = 0, 1                     # stv.h STV_RESIZE_*: the mo
 # launch constants of stv_resize2x (stv.h STV_RESIZE_THREADS, STV_RESIZE_MAX_BLOCKS; pixels per work item): a work item is
 # RESIZE_VEC consecutive OUTPUT pixels of one row, a pass of the capped grid covers RESIZE_MAX_BLOCKS * RESIZE_THREADS items
 RESIZE_THREADS, RESIZE_MAX_BLOCKS, RESIZE_VEC = 256, 1024, 4
+# launch constants of the three colour kernels (stv.h STV_COLOR_*; csrc/color.hip): a work item is COLOR_VEC consecutive
+# pixels of one row read from all three planes; stv_color_stats always runs COLOR_STATS_PARTS workgroups (one row of nine
+# doubles each), stv_color_affine and stv_luma_transfer at most COLOR_MAX_BLOCKS, all of COLOR_THREADS threads
+COLOR_VEC, COLOR_THREADS, COLOR_STATS_PARTS, COLOR_MAX_BLOCKS = 4, 256, 256, 1024
 
 _ERRORS = {1: "STV_ERR_ARG (unsupported shape / null pointer / dtype)",
            2: "STV_ERR_LAUNCH (HIP launch failed)", 3: "STV_ERR_ALLOC", 4: "STV_ERR_GRAPH"}
@@ -109,6 +113,9 @@ SIGNATURES = {
     "stv_content_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_int, c_int, c_void_p]),
     "stv_tv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "stv_resize2x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "stv_color_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "stv_color_affine": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int, c_void_p]),
+    "stv_luma_transfer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),
     "stv_image_to_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_void_p]),
     "stv_loss_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "stv_loss_combine_log": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,

@@ -2,7 +2,7 @@
 
 Options that only have meaning for presentation features outside this build (comparison grids)
 are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,bf16x3}``, ``--tv-w``,
-``--pyramid-levels`` / ``--pyramid-steps``.
+``--pyramid-levels`` / ``--pyramid-steps``, ``--preserve-color {off,match,luma}``.
 """
 from __future__ import annotations
 
@@ -45,6 +45,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
                      help="Coarse-to-fine levels, each twice the size of the one before (1 = off, the default)")
     opt.add_argument("--pyramid-steps", type=str,
                      help="Comma-separated steps per pyramid level, coarsest first (default: --steps split evenly)")
+    opt.add_argument("--preserve-color", choices=["off", "match", "luma"], default=S,
+                     help="Keep the content image's colours: match = give the style image the content's colour mean and "
+                          "covariance before the run, luma = keep only the result's luminance (off = the default)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
     opt.add_argument("--init-method", choices=["random", "white", "content"], default=S, help="Initialization method")
     opt.add_argument("--seed", type=int, default=S, help="Random seed")
@@ -115,6 +118,9 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
         at = next(i for i, (label, _) in enumerate(rows) if label == "Steps") + 1
         rows[at:at] = [("Pyramid Levels", o.pyramid_levels),
                        ("Pyramid Steps", o.pyramid_steps if o.pyramid_steps else "even split of Steps")]
+    if o.preserve_color != "off":
+        rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Initialization Method") + 1,
+                    ("Preserve Color", o.preserve_color))
     for label, value in rows:
         logger.info("%s: %s", label, value)
 

@@ -3,8 +3,9 @@
 Field names, bounds and override precedence follow reference config.py:53-309
 so existing ``config.toml`` files and CLI invocations keep working.  The
 additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf16x3" fp32 storage, split-bf16 products),
-``optimization.tv_w`` (weight of the total-variation regulariser, 0 = off) and ``optimization.pyramid_levels`` /
-``optimization.pyramid_steps`` (coarse-to-fine runs: levels, and optionally the steps of each, coarsest first).
+``optimization.tv_w`` (weight of the total-variation regulariser, 0 = off), ``optimization.pyramid_levels`` /
+``optimization.pyramid_steps`` (coarse-to-fine runs: levels, and optionally the steps of each, coarsest first) and
+``optimization.preserve_color`` ("off" | "match" | "luma": keep the content image's colours, ``color.py``).
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ from pydantic import BaseModel, Field
 from . import config_defaults as d
 from .constants import VIDEO_QUALITY_MAX, VIDEO_QUALITY_MIN
 from .logging_utils import logger
-from .type_defs import InitMethod, Precision, VideoMode
+from .type_defs import InitMethod, Precision, PreserveColor, VideoMode
 
 
 class OptimizationConfig(BaseModel):
@@ -29,6 +30,7 @@ class OptimizationConfig(BaseModel):
     tv_w: float = Field(d.DEFAULT_TV_WEIGHT, ge=0)
     pyramid_levels: int = Field(d.DEFAULT_PYRAMID_LEVELS, ge=1, le=6)
     pyramid_steps: list[int] | None = d.DEFAULT_PYRAMID_STEPS
+    preserve_color: PreserveColor = Field(d.DEFAULT_PRESERVE_COLOR)
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
     seed: int = Field(d.DEFAULT_SEED, ge=0)
@@ -123,7 +125,7 @@ _DIRECT = {
     "output": ("output", "output"), "log_every": ("output", "log_every"), "log_loss": ("output", "log_loss"),
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
     "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lr": ("optimization", "lr"),
-    "pyramid_levels": ("optimization", "pyramid_levels"),
+    "pyramid_levels": ("optimization", "pyramid_levels"), "preserve_color": ("optimization", "preserve_color"),
     "init_method": ("optimization", "init_method"), "seed": ("optimization", "seed"),
     "save_every": ("video", "save_every"), "fps": ("video", "fps"), "quality": ("video", "quality"),
     "metadata_title": ("video", "metadata_title"), "metadata_artist": ("video", "metadata_artist"),

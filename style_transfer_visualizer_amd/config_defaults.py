@@ -8,6 +8,7 @@ DEFAULT_CONTENT_WEIGHT = 1.0
 DEFAULT_TV_WEIGHT = 0.0      # build-specific: weight of the total-variation regulariser (0 = off)
 DEFAULT_PYRAMID_LEVELS = 1   # build-specific: levels of a coarse-to-fine run (1 = the single-size run)
 DEFAULT_PYRAMID_STEPS = None  # build-specific: steps per level, coarsest first (None = optimization.steps split evenly)
+DEFAULT_PRESERVE_COLOR = "off"  # build-specific: keep the content image's colours ("match": style statistics, "luma": chroma swap)
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"
 DEFAULT_SEED = 0

@@ -4,6 +4,10 @@ validate -> seed -> device -> load images -> model/targets/optimizer -> run -> s
 ``input_img.detach().clamp(0, 1)``.  Timelapse video / GIF encoding is presentation and is not
 part of this build: any ``FrameSink`` may be injected, otherwise video requests are downgraded
 with a warning and the run proceeds like ``--no-video``.
+
+``optimization.preserve_color`` (``color.py``, no counterpart in the reference) adds one stage at either end: "match"
+re-colours the style image right behind the loads, "luma" restores the content image's chrominance in the result right
+in front of the save; "off" adds nothing.
 """
 from __future__ import annotations
 
@@ -12,7 +16,7 @@ from pathlib import Path
 
 import torch
 
-from . import core_model, image_io, optimization, pyramid, runtime
+from . import color, core_model, image_io, optimization, pyramid, runtime
 from .logging_utils import logger
 from .type_defs import InputPaths, SaveOptions
 
@@ -44,6 +48,9 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     normalize = config.optimization.normalize
     content_img = image_io.load_image_to_tensor(paths.content_path, device, normalize=normalize)
     style_img = image_io.load_image_to_tensor(paths.style_path, device, normalize=normalize)
+    preserve_color = config.optimization.preserve_color
+    if preserve_color == "match":               # once per run, on the full-size images: a coarse-to-fine run halves the matched style
+        style_img = color.match_style_to_content(style_img, content_img)
     coarse_to_fine = config.optimization.pyramid_levels > 1
     if not coarse_to_fine:
         with _SETUP_LOCK:
@@ -68,6 +75,8 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     for sink in (video_writer, gif_collector):
         if sink is not None:
             sink.close()
+    if preserve_color == "luma":                # the final full-size image only: frames showed the un-swapped one
+        input_img = color.transfer_luma(input_img, content_img, normalize=normalize)
 
     runtime.save_outputs(input_img, loss_metrics, output_path, elapsed, SaveOptions(
         content_name=content_name, style_name=style_name, normalize=normalize,

@@ -440,6 +440,72 @@ def resize2x(x: torch.Tensor, mode: int, out: torch.Tensor | None = None) -> tor
     return out
 
 
+# ---- colour preservation (--preserve-color) ----------------------------------------
+
+def _color_image(x: torch.Tensor, what: str) -> tuple[int, int]:
+    """(H, W) of a contiguous fp32 image ``[3, H, W]`` or ``[1, 3, H, W]``; anything else is refused."""
+    if x.dtype != torch.float32 or x.dim() not in (3, 4) or x.shape[-3] != 3 or (x.dim() == 4 and x.shape[0] != 1):
+        msg = f"{what} expects an fp32 image [3, H, W] or [1, 3, H, W], got {tuple(x.shape)} {x.dtype}"
+        raise RuntimeError(msg)
+    return int(x.shape[-2]), int(x.shape[-1])
+
+
+def _color_out(x: torch.Tensor, out: torch.Tensor | None, what: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty_like(x, memory_format=torch.contiguous_format)
+    if tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32:
+        msg = f"{what}: out is {tuple(out.shape)} {out.dtype}, expected {tuple(x.shape)} torch.float32"
+        raise RuntimeError(msg)
+    return out
+
+
+def color_stats(img: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Raw colour moments of a contiguous fp32 image ``[3, H, W]`` or ``[1, 3, H, W]`` (``stv_color_stats``): a device
+    tensor ``[COLOR_STATS_PARTS, 9]`` of float64, one row per workgroup - the sums of the three channels, then of the
+    products x0x0, x0x1, x0x2, x1x1, x1x2, x2x2 - formed in double, in a fixed order; every entry is written (into ``out`` when given).  The caller adds the rows."""
+    lib = _lib.load()
+    H, W = _color_image(img, "color_stats")
+    parts = out if out is not None else torch.empty(_lib.COLOR_STATS_PARTS, 9, dtype=torch.float64, device=img.device)
+    if tuple(parts.shape) != (_lib.COLOR_STATS_PARTS, 9) or parts.dtype != torch.float64:
+        msg = f"color_stats: out is {tuple(parts.shape)} {parts.dtype}, expected {(_lib.COLOR_STATS_PARTS, 9)} torch.float64"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_color_stats(_ptr(img), _ptr(parts), H, W, _stream()), "stv_color_stats")
+    return parts
+
+
+def color_affine(x: torch.Tensor, m12, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``y[c] = ((m[c][0]*x[0] + m[c][1]*x[1]) + m[c][2]*x[2]) + b[c]`` per pixel of a contiguous fp32 image ``[3, H, W]`` or
+    ``[1, 3, H, W]`` (``stv_color_affine``), every operation rounded to fp32 on its own.  ``m12``: 12 host numbers, the
+    row-major matrix followed by the offset.  ``out`` may be ``x`` (in place); returns ``out`` (a new tensor by default)."""
+    lib = _lib.load()
+    H, W = _color_image(x, "color_affine")
+    values = [float(v) for v in m12]
+    if len(values) != 12:       # noqa: PLR2004
+        msg = f"color_affine: m12 holds {len(values)} numbers, expected 12 (3x3 matrix, then the offset)"
+        raise RuntimeError(msg)
+    out = _color_out(x, out, "color_affine")
+    _lib.check(lib.stv_color_affine(_ptr(x), _ptr(out), (ctypes.c_float * 12)(*values), H, W, _stream()), "stv_color_affine")
+    return out
+
+
+def luma_transfer(result: torch.Tensor, content: torch.Tensor, *, mean: tuple | list | None, std: tuple | list | None,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """Luminance (Rec.601) of ``result`` with the chrominance of ``content`` (``stv_luma_transfer``), both contiguous fp32
+    ``[3, H, W]`` or ``[1, 3, H, W]`` of one size: ``content_rgb + (Y(result_rgb) - Y(content_rgb))`` per channel, in
+    [0, 1] RGB after ``prepare_image_for_output``'s rule, mapped back into the tensors' space.  ``mean``/``std`` given: the
+    images are ImageNet-normalised.  ``out`` may be ``result``, not ``content``; returns ``out`` (a new tensor by default)."""
+    lib = _lib.load()
+    H, W = _color_image(result, "luma_transfer")
+    if _color_image(content, "luma_transfer") != (H, W):
+        msg = f"luma_transfer: result is {tuple(result.shape)}, content {tuple(content.shape)}"
+        raise RuntimeError(msg)
+    out = _color_out(result, out, "luma_transfer")
+    m3 = (ctypes.c_float * 3)(*mean) if mean is not None else None
+    s3 = (ctypes.c_float * 3)(*std) if std is not None else None
+    _lib.check(lib.stv_luma_transfer(_ptr(result), _ptr(content), _ptr(out), H, W, m3, s3, _stream()), "stv_luma_transfer")
+    return out
+
+
 class HostMailbox:
     """Pinned host memory the GPU writes while the CPU reads (``stv_host_mailbox_alloc``: mapped under the same
     pointer on the device, fine-grained coherent, zeroed).  ``tensor`` / ``array`` are views; every view keeps this

@@ -9,6 +9,7 @@ import torch
 InitMethod = Literal["content", "random", "white"]
 VideoMode = Literal["realtime", "postprocess"]
 Precision = Literal["fp32", "bf16", "bf16x3"]
+PreserveColor = Literal["off", "match", "luma"]
 LossHistory = dict[str, list[float]]
 TensorList = list[torch.Tensor]
 
