@@ -68,39 +68,25 @@ int stv_gram_ksplit(int n_pixels, int channels);
  *      `x = block(x)` (core_model.py:316) and their autograd backward
  *      (`loss.backward()`, optimization.py:313). ---------------------------- */
 
-/* (The two unpacked entries below read `wf` as it is, with the shape-generic first-layer
- * kernels; the library holds no scratch of its own.  The 3 -> 64 layer's fast kernels need the
- * kernel-side weight order: stv_conv_first_pack + the *_packed entries further down, which is
- * what the step path and ops.py use.) */
-/* First conv: NCHW fp32 image [cin][H][W] -> NHWC `dtype` [H][W][cout].
- * wf is [9][cout][cin] fp32 (tap = ky*3+kx), bias fp32[cout]. */
-int stv_conv_first_fwd(const float* x_nchw, const float* wf, const float* bias,
-                       void* y, int H, int W, int cin, int cout, int dtype,
-                       void* stream);
-/* Its input-gradient: dy NHWC `dtype` [H][W][cout] -> dx NCHW fp32 [cin][H][W].
- * wf is the same forward-packed fp32 weight. */
-int stv_conv_first_dgrad(const void* dy, const float* wf, float* dx_nchw,
-                         int H, int W, int cin, int cout, int dtype, void* stream);
-
-/* The same two calls for frozen weights: stv_conv_first_pack() writes the
- * kernel-side packing of `wf` (forward order, then flipped taps for dgrad) into
- * a caller-owned buffer of stv_conv_first_packed_bytes(cin, cout) bytes, once;
- * the *_packed entries then skip the per-call repack. */
+/* First conv.  Its weights are frozen, so every caller packs them once: stv_conv_first_pack() writes the
+ * kernel-side form of `wf` ([9][cout][cin] fp32, tap = ky*3+kx) into a caller-owned buffer of
+ * stv_conv_first_packed_bytes(cin, cout) bytes, and both directions read that buffer only.  For 3 -> 64 it
+ * holds the orders and matrix-core fragments the VGG kernels read; for every other shape the packed form is
+ * the weights as given.  The library keeps no scratch of its own. */
 size_t stv_conv_first_packed_bytes(int cin, int cout);
 int stv_conv_first_pack(const float* wf, float* packed, int cin, int cout, void* stream);
-int stv_conv_first_fwd_packed(const float* x_nchw, const float* packed, const float* bias,
-                              void* y, int H, int W, int cin, int cout, int dtype,
-                              void* stream);
-int stv_conv_first_dgrad_packed(const void* dy, const float* packed, float* dx_nchw,
-                                int H, int W, int cin, int cout, int dtype, void* stream);
-/* Forward of a first layer that is a STYLE TAP (conv1_1 in the default layer set, core_model.py:213-226 /
- * 297-314): besides y it leaves the split-K slabs of R = F^T F exactly as stv_gram_partial(y) would
- * (stv_gram_ksplit(H*W, cout) slabs of [cout][cout] fp32 in `gram_partials`, to be reduced by
- * stv_gram_finish / a stv_gram_multi tap with F == NULL), computed from the rounded values it stores, so the
- * map is not read back for the Gram matrix.  bf16, cin = 3, cout = 64 only (stv_conv_first_gram_supported). */
+/* Forward: NCHW fp32 image [cin][H][W] -> NHWC `dtype` [H][W][cout]; bias fp32[cout] or NULL.
+ * gram_partials (NULL, or where stv_conv_first_gram_supported says so: bf16, 3 -> 64) is for a first layer
+ * that is a STYLE TAP (conv1_1 in the default layer set, core_model.py:213-226 / 297-314): besides y the
+ * kernel leaves the split-K slabs of R = F^T F exactly as stv_gram_partial(y) would (stv_gram_ksplit(H*W, cout)
+ * slabs of [cout][cout] fp32, to be reduced by stv_gram_finish / a stv_gram_multi tap with F == NULL),
+ * computed from the rounded values it stores, so the map is not read back for the Gram matrix. */
+int stv_conv_first_fwd(const float* x_nchw, const float* packed, const float* bias, void* y,
+                       float* gram_partials, int H, int W, int cin, int cout, int dtype, void* stream);
+/* Its input-gradient: dy NHWC `dtype` [H][W][cout] -> dx NCHW fp32 [cin][H][W] (written, not accumulated). */
+int stv_conv_first_dgrad(const void* dy, const float* packed, float* dx_nchw,
+                         int H, int W, int cin, int cout, int dtype, void* stream);
 int stv_conv_first_gram_supported(int H, int W, int cin, int cout, int dtype);
-int stv_conv_first_fwd_gram(const float* x_nchw, const float* packed, const float* bias, void* y,
-                            float* gram_partials, int H, int W, int cin, int cout, int dtype, void* stream);
 
 /* Implicit-GEMM 3x3 conv, pad 1, stride 1, NHWC.  `w` is [taps][cout][cin] in
  * `dtype` (K-contiguous rows); bias fp32[cout] or NULL.  taps = 9 (3x3) or 1
@@ -247,7 +233,7 @@ int stv_gram_finish(const float* partials, const float* target, float* gram_out,
  * Same arithmetic, same fixed summation order as the per-tap calls. */
 typedef struct {
   const void* F;          /* features, NHWC [n_pixels][channels] in `dtype`; NULL: `partials` is already filled
-                             (stv_conv_first_fwd_gram) and only the finish pass runs for this tap */
+                             (stv_conv_first_fwd with gram_partials) and only the finish pass runs for this tap */
   float* partials;        /* stv_gram_partials_bytes(n_pixels, channels) */
   const float* target;    /* [C][C] or NULL */
   float* gram_out;        /* [C][C] or NULL */
@@ -442,8 +428,8 @@ enum {
   STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER, STV_OP_TV
 };
 /* Operands follow the direct entry points' argument order (inputs p0.., outputs q0..).
- * CONV_FIRST_FWD takes the optional stv_conv_first_pack buffer in p3 (and, with q1 set, runs
- * stv_conv_first_fwd_gram with q1 = gram_partials), CONV_FIRST_DGRAD in p2;
+ * CONV_FIRST_FWD takes the stv_conv_first_pack buffer in p3 (p1 unused) and gram_partials, or NULL, in q1;
+ * CONV_FIRST_DGRAD takes the buffer in p2 (p1 unused); without the buffer either is STV_ERR_ARG.
  * CONV with q1 set runs stv_conv_igemm_pool (q1 = pooled output, q2 = optional arg-max map); CONV with q2 AND q3 set runs
  * stv_conv_igemm_dual (q2 = x2, q3 = w2, n = cin2: inputs, despite the slot names).
  * GRAM_MULTI: p0 = HOST pointer to an array of stv_gram_tap_t, n = its length; the array is

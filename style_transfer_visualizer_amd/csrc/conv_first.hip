@@ -1,24 +1,35 @@
 // First VGG conv (Cin = 3) at the image boundary: the optimised image and its
 // gradient stay NCHW fp32 (the tensors the reference hands to the optimizer,
 // core_model.py:66-100); activations are NHWC from here on, so the layout
-// change costs nothing extra.  K = 27 is too thin for the matrix cores; these
-// are VALU kernels bound by the HBM write (fwd) / read (dgrad) of the 64-channel
-// activation.  A wave covers 64/LP consecutive pixels with LP lanes per pixel,
-// each lane owning one 16-byte channel vector, so every activation access is a
-// fully coalesced 1 KiB wave transaction.
-#include <stdlib.h>
-
+// change costs nothing extra.  Three families, chosen in fwd_typed / dgrad_typed:
+// 3 -> 64 in bf16 on the matrix cores (two-term bf16 split), 3 -> 64 in fp32 on
+// the VALU with scalar weights (the parity mode), and for any other shape the
+// lanes-per-pixel kernels below (a wave covers 64/LP consecutive pixels with LP
+// lanes per pixel, each lane owning one 16-byte channel vector, so every
+// activation access is a fully coalesced 1 KiB wave transaction) or, where those
+// do not fit, one thread per output element.
 #include <type_traits>
 
 #include "stv_common.h"
 
-#ifndef STV_FIRST_DIAG   // diagnostic builds knock out phases of the matrix-core forward kernel (timing only)
-#define STV_FIRST_DIAG 0
-#endif
-
 namespace {
 
 constexpr int kMaxCin = 4;
+
+// v = hi + lo with both terms bf16: the split that keeps the matrix-core products fp32-faithful
+__device__ __forceinline__ void split_bf16(float v, bf16_t& hi, bf16_t& lo) {
+  hi = f32_to_bf16(v);
+  lo = f32_to_bf16(v - bf16_to_f32(hi));
+}
+
+// the layer's weights [tap][cout][cin] into LDS as [tap][cin][cout], whole workgroup; ends with the barrier
+__device__ __forceinline__ void stage_weights(float* __restrict__ ws, const float* __restrict__ wf, int cin, int cout) {
+  for (int i = threadIdx.x; i < 9 * cin * cout; i += blockDim.x) {
+    const int c = i % cin, n = (i / cin) % cout, tap = i / (cin * cout);
+    ws[(tap * cin + c) * cout + n] = wf[i];
+  }
+  __syncthreads();
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void conv_first_fwd_kernel(
@@ -27,11 +38,7 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(
   constexpr int kVec = elem_traits<T>::kVec;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* ws = reinterpret_cast<float*>(smem);  // [tap][cin][cout]
-  for (int i = threadIdx.x; i < 9 * cin * cout; i += blockDim.x) {
-    const int c = i % cin, n = (i / cin) % cout, tap = i / (cin * cout);
-    ws[(tap * cin + c) * cout + n] = wf[i];
-  }
-  __syncthreads();
+  stage_weights(ws, wf, cin, cout);
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t pix = gid >> lp_shift;
   const int grp = (int)(gid & ((1u << lp_shift) - 1));
@@ -65,11 +72,7 @@ __global__ __launch_bounds__(256) void conv_first_dgrad_kernel(
   constexpr int kVec = elem_traits<T>::kVec;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* ws = reinterpret_cast<float*>(smem);  // [tap][cin][cout]
-  for (int i = threadIdx.x; i < 9 * cin * cout; i += blockDim.x) {
-    const int c = i % cin, n = (i / cin) % cout, tap = i / (cin * cout);
-    ws[(tap * cin + c) * cout + n] = wf[i];
-  }
-  __syncthreads();
+  stage_weights(ws, wf, cin, cout);
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t pix_raw = gid >> lp_shift;
   const int lp = 1 << lp_shift;
@@ -105,7 +108,7 @@ __global__ __launch_bounds__(256) void conv_first_dgrad_kernel(
   }
 }
 
-// ---- fast path for the VGG shape (cin = 3, cout = 64): 16x16 pixel tiles ---------------------------
+// ---- the VGG shape (cin = 3, cout = 64) in fp32: 16x16 pixel tiles ---------------------------------
 // fwd : the 18x18x3 fp32 halo tile sits in LDS; one lane = one pixel x all 64 output channels.
 //       The weight index is wave-uniform, so weights come through the scalar cache as SGPR
 //       operands of v_fmac: exactly 27*64 FMAs per pixel and 27 conflict-free LDS reads.  Output
@@ -249,8 +252,8 @@ __global__ void pack_first_fragments(const float* __restrict__ wf, uint32_t* __r
     const int k = ks * 16 + 8 * h + 2 * q + e2;
     float v = 0.0f;
     if (k < 27) v = wf[((k / 3) * 64 + nt * 32 + r) * 3 + (k % 3)];
-    const bf16_t hi = f32_to_bf16(v);
-    const bf16_t lo = f32_to_bf16(v - bf16_to_f32(hi));
+    bf16_t hi, lo;
+    split_bf16(v, hi, lo);
     out |= (uint32_t)(part ? lo : hi) << (16 * e2);
   }
   frag[i] = out;
@@ -352,14 +355,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
   for (int k = 0; k < NPRE; ++k)
     if (k * 256 + tid < 3 * MF_PLANE) {
-      const bf16_t hi = f32_to_bf16(pre[k]);
-      xs[k * 256 + tid] = ((uint32_t)hi << 16) | (uint32_t)f32_to_bf16(pre[k] - bf16_to_f32(hi));
+      bf16_t hi, lo;
+      split_bf16(pre[k], hi, lo);
+      xs[k * 256 + tid] = ((uint32_t)hi << 16) | (uint32_t)lo;
     }
-  if (t + (int)gridDim.x < ntiles && !(STV_FIRST_DIAG & 4)) request(t + gridDim.x);
+  if (t + (int)gridDim.x < ntiles) request(t + gridDim.x);
   __syncthreads();
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt) {
-    if (STV_FIRST_DIAG & 1) break;          // timing only: no gathers, no MFMAs
     const int base = (wave * 2 + mt) * MF_IW + r;
     f32x16 acc[2];                          // one row block at a time: product, store, Gram (register budget of two waves per SIMD)
 #pragma unroll
@@ -412,8 +415,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const auto sx = __builtin_amdgcn_permlane32_swap(px[jp], px[jp + 1], false, false);
         const auto sy = __builtin_amdgcn_permlane32_swap(py[jp], py[jp + 1], false, false);
         const u32x4 out = {sx[0], sy[0], sx[1], sy[1]};     // lanes 0-31: channels 8jp..8jp+7, lanes 32-63: the next eight
-        if (ok && !(STV_FIRST_DIAG & 2)) *reinterpret_cast<u32x4*>(dst + nt * 32 + 8 * jp + 8 * h) = out;
-        if ((STV_FIRST_DIAG & 2) && out[0] == 0x12345678u) dst[0] = 1;   // keep the work alive
+        if (ok) *reinterpret_cast<u32x4*>(dst + nt * 32 + 8 * jp + 8 * h) = out;
         if (GRAM)      // the stored words, pixel-major, into this wave's patch (zeros for pixels outside the image)
           *reinterpret_cast<u32x4*>(gpatch + r * GT_PITCH + (nt * 32 + 8 * jp + 8 * h) * 2) = ok ? out : (u32x4){0u, 0u, 0u, 0u};
       }
@@ -478,10 +480,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // contribution of input pixel p' to output pixel p' - dxo: a shifted three-term sum finishes the job through
 // a 6-KB per-wave LDS patch.  dy is bf16 as stored; the weights are split in two bf16 terms so the product
 // stays fp32-faithful.  36 lanes of a weight fragment are non-zero (9 columns x 4 k-groups): a 7 KB table.
-#ifndef STV_DG_TH
-#define STV_DG_TH 8
-#endif
-constexpr int DG_TH = STV_DG_TH, DG_TW = 32, DG_IW = DG_TW + 2, DG_PITCH = 128 + 16;
+constexpr int DG_TH = 8, DG_TW = 32, DG_IW = DG_TW + 2, DG_PITCH = 128 + 16;
 constexpr int DG_RW = DG_TH / 4;                            // output rows per wave
 constexpr int DG_CB = 3;                                    // 16-pixel MFMA row blocks across the 34-pixel halo row (48 >= 34)
 static_assert(DG_TH % 4 == 0, "four waves split the rows");
@@ -501,8 +500,8 @@ __global__ void pack_first_dgrad_fragments(const float* __restrict__ wf, uint32_
   for (int e2 = 0; e2 < 2; ++e2) {
     const int n = ks * 32 + 8 * g + 2 * q + e2;
     const float v = wf[((8 - tap) * 64 + n) * 3 + c];         // flipped taps: the read offset becomes +off(tap)
-    const bf16_t hi = f32_to_bf16(v);
-    const bf16_t lo = f32_to_bf16(v - bf16_to_f32(hi));
+    bf16_t hi, lo;
+    split_bf16(v, hi, lo);
     out |= (uint32_t)(part ? lo : hi) << (16 * e2);
   }
   frag[i] = out;
@@ -673,81 +672,100 @@ inline int lanes_shift(int cout, int kvec) {
   return s;
 }
 
-// `packed` (optional): the caller's buffer from stv_conv_first_pack.  The 3 -> 64 kernels read the weights in their
-// kernel-side order only; a caller without that buffer gets the shape-generic kernels below, which read `wf` as it is
-// (the library keeps no scratch of its own: nothing hidden is shared between streams, threads or devices).
+// ---- the packed weights: one caller-owned fp32 buffer that stv_conv_first_pack writes once ------------------
+// 3 -> 64 (the VGG shape): four sections, each in the order its kernel reads.  Every other shape: the weights as given,
+// [9][cout][cin], for the lanes-per-pixel and the generic kernels.  (The library keeps no scratch of its own: nothing
+// hidden is shared between streams, threads or devices.)
+constexpr bool vgg_shape(int cin, int cout) { return cin == 3 && cout == 64; }
+struct Packed {
+  static constexpr int kPlain = 9 * 3 * 64;
+  static constexpr int kFwd = 0;                             // [9][3][64] fp32, taps in forward order: conv_first_fwd_c64
+  static constexpr int kFlipped = kFwd + kPlain;             // [9][3][64] fp32, taps flipped: conv_first_dgrad_c64
+  static constexpr int kFwdFrags = kFlipped + kPlain;        // MF_FRAG_WORDS: conv_first_fwd_mfma
+  static constexpr int kDgradFrags = kFwdFrags + MF_FRAG_WORDS;   // DG_FRAG_WORDS: conv_first_dgrad_mfma
+  static constexpr int kWords = kDgradFrags + DG_FRAG_WORDS;
+  static const uint32_t* frags(const float* packed, int section) { return reinterpret_cast<const uint32_t*>(packed + section); }
+  static uint32_t* frags(float* packed, int section) { return reinterpret_cast<uint32_t*>(packed + section); }
+};
+
+// the split-bf16 kernels on the matrix cores serve the VGG shape in bf16; everything else runs on the VALU
+inline bool on_matrix_cores(int cin, int cout, int dtype) { return vgg_shape(cin, cout) && dtype == STV_BF16; }
+
+// persistent kernels: two resident workgroups per CU walk the tiles (swept 2..8: 2 is fastest at 512^2 and 1024^2)
+inline int resident_grid(int tiles) {
+  constexpr int kResident = 2 * 256;
+  return tiles < kResident ? tiles : kResident;
+}
+
 template <typename T>
-int fwd_typed(const float* x, const float* wf, const float* packed, const float* bias, void* y, int H, int W,
-              int cin, int cout, hipStream_t st, float* gram_slabs = nullptr) {
-  if (cin == 3 && cout == 64 && packed && std::is_same<T, bf16_t>::value && !getenv("STV_FIRST_VALU")) {
-    const int tiles = ceil_div(W, MF_TW) * ceil_div(H, MF_TH);
-    static const int wg_per_cu = getenv("STV_FIRST_WGS") ? atoi(getenv("STV_FIRST_WGS")) : 2;   // swept 2..8: 2 is fastest at 512^2 and 1024^2
-    const int grid = tiles < wg_per_cu * 256 ? tiles : wg_per_cu * 256;   // resident workgroups walk the tiles
-    const uint32_t* fr = reinterpret_cast<const uint32_t*>(packed + 2 * 1728);
-    if (gram_slabs)     // one slab per workgroup: exactly the split the finish kernel will walk (idle workgroups write zeros)
-      hipLaunchKernelGGL(conv_first_fwd_mfma<true>, dim3(stv_gram_ksplit(H * W, 64)), dim3(256), 0, st, x, fr, bias,
-                         static_cast<bf16_t*>(y), gram_slabs, H, W);
-    else
-      hipLaunchKernelGGL(conv_first_fwd_mfma<false>, dim3(grid), dim3(256), 0, st, x, fr, bias, static_cast<bf16_t*>(y),
-                         nullptr, H, W);
-    STV_CHECK_LAUNCH();
-    return STV_OK;
-  }
-  if (gram_slabs) return STV_ERR_ARG;
-  if (cin == 3 && cout == 64 && packed) {
-    const float* wt = packed;
-    const int tiles = ceil_div(W, FT) * ceil_div(H, FT);
-    hipLaunchKernelGGL(conv_first_fwd_c64<T>, dim3(tiles), dim3(256), 0, st, x, wt, bias, static_cast<T*>(y), H, W);
-    STV_CHECK_LAUNCH();
-    return STV_OK;
+int fwd_typed(const float* x, const float* packed, const float* bias, void* y, int H, int W, int cin, int cout,
+              hipStream_t st, float* gram_slabs) {      // gram_slabs: on the matrix cores only (the entry point refuses the rest)
+  if constexpr (std::is_same<T, bf16_t>::value) {
+    if (on_matrix_cores(cin, cout, STV_BF16)) {
+      const uint32_t* fr = Packed::frags(packed, Packed::kFwdFrags);
+      if (gram_slabs)     // one slab per workgroup: exactly the split the finish kernel will walk (idle workgroups write zeros)
+        hipLaunchKernelGGL(conv_first_fwd_mfma<true>, dim3(stv_gram_ksplit(H * W, 64)), dim3(256), 0, st, x, fr, bias,
+                           static_cast<bf16_t*>(y), gram_slabs, H, W);
+      else
+        hipLaunchKernelGGL(conv_first_fwd_mfma<false>, dim3(resident_grid(ceil_div(W, MF_TW) * ceil_div(H, MF_TH))),
+                           dim3(256), 0, st, x, fr, bias, static_cast<bf16_t*>(y), nullptr, H, W);
+      STV_CHECK_LAUNCH();
+      return STV_OK;
+    }
+  } else {
+    if (vgg_shape(cin, cout)) {
+      const int tiles = ceil_div(W, FT) * ceil_div(H, FT);
+      hipLaunchKernelGGL(conv_first_fwd_c64<T>, dim3(tiles), dim3(256), 0, st, x, packed + Packed::kFwd, bias,
+                         static_cast<T*>(y), H, W);
+      STV_CHECK_LAUNCH();
+      return STV_OK;
+    }
   }
   const int sh = lanes_shift(cout, elem_traits<T>::kVec);
   const size_t lds = (size_t)9 * cin * cout * sizeof(float);
   if (sh >= 0 && lds <= 64 * 1024) {
     const size_t threads = ((size_t)H * W) << sh;
     hipLaunchKernelGGL(conv_first_fwd_kernel<T>, dim3((unsigned)((threads + 255) / 256)), dim3(256),
-                       lds, st, x, wf, bias, static_cast<T*>(y), H, W, cin, cout, sh);
+                       lds, st, x, packed, bias, static_cast<T*>(y), H, W, cin, cout, sh);
   } else {
     const size_t total = (size_t)H * W * cout;
     hipLaunchKernelGGL(conv_first_fwd_generic<T>, dim3((unsigned)((total + 255) / 256)), dim3(256),
-                       0, st, x, wf, bias, static_cast<T*>(y), H, W, cin, cout);
+                       0, st, x, packed, bias, static_cast<T*>(y), H, W, cin, cout);
   }
   STV_CHECK_LAUNCH();
   return STV_OK;
 }
 template <typename T>
-int dgrad_typed(const void* dy, const float* wf, const float* packed, float* dx, int H, int W, int cin, int cout,
-                hipStream_t st) {
-  if (cin == 3 && cout == 64 && packed && std::is_same<T, bf16_t>::value && !getenv("STV_FIRST_VALU")) {
-    const int tiles = ceil_div(W, DG_TW) * ceil_div(H, DG_TH);
-    constexpr int lds = DG_TILE_BYTES + (DG_FRAGS + 1) * 16 + DG_D_BYTES;
-    static const int dg_wgs = getenv("STV_FIRST_DG_WGS") ? atoi(getenv("STV_FIRST_DG_WGS")) : 2;
-    const int grid = tiles < dg_wgs * 256 ? tiles : dg_wgs * 256;   // resident workgroups walk the tiles
-    hipLaunchKernelGGL(conv_first_dgrad_mfma, dim3(grid), dim3(256), lds, st, static_cast<const bf16_t*>(dy),
-                       reinterpret_cast<const uint32_t*>(packed + 2 * 1728 + MF_FRAG_WORDS), dx, H, W);
-    STV_CHECK_LAUNCH();
-    return STV_OK;
-  }
-  if (cin == 3 && cout == 64 && packed) {
-    const float* wd = packed + 1728;
-    const int tiles = ceil_div(W, FT) * ceil_div(H, FT);
-    const size_t lds = (size_t)FH * FH * (64 * sizeof(T) + 16);
-    if (stv_set_max_lds(reinterpret_cast<const void*>(&conv_first_dgrad_c64<T>), (int)lds) != STV_OK) return STV_ERR_LAUNCH;
-    hipLaunchKernelGGL(conv_first_dgrad_c64<T>, dim3(tiles), dim3(256), lds, st, static_cast<const T*>(dy), wd, dx,
-                       H, W);
-    STV_CHECK_LAUNCH();
-    return STV_OK;
+int dgrad_typed(const void* dy, const float* packed, float* dx, int H, int W, int cin, int cout, hipStream_t st) {
+  if constexpr (std::is_same<T, bf16_t>::value) {
+    if (on_matrix_cores(cin, cout, STV_BF16)) {
+      constexpr int lds = DG_TILE_BYTES + (DG_FRAGS + 1) * 16 + DG_D_BYTES;
+      hipLaunchKernelGGL(conv_first_dgrad_mfma, dim3(resident_grid(ceil_div(W, DG_TW) * ceil_div(H, DG_TH))), dim3(256),
+                         lds, st, static_cast<const bf16_t*>(dy), Packed::frags(packed, Packed::kDgradFrags), dx, H, W);
+      STV_CHECK_LAUNCH();
+      return STV_OK;
+    }
+  } else {
+    if (vgg_shape(cin, cout)) {
+      const int tiles = ceil_div(W, FT) * ceil_div(H, FT);
+      const size_t lds = (size_t)FH * FH * (64 * sizeof(T) + 16);
+      if (stv_set_max_lds(reinterpret_cast<const void*>(&conv_first_dgrad_c64<T>), (int)lds) != STV_OK) return STV_ERR_LAUNCH;
+      hipLaunchKernelGGL(conv_first_dgrad_c64<T>, dim3(tiles), dim3(256), lds, st, static_cast<const T*>(dy),
+                         packed + Packed::kFlipped, dx, H, W);
+      STV_CHECK_LAUNCH();
+      return STV_OK;
+    }
   }
   const int sh = lanes_shift(cout, elem_traits<T>::kVec);
   const size_t lds = (size_t)9 * cin * cout * sizeof(float);
   if (sh >= 0 && lds <= 64 * 1024 && cin <= kMaxCin) {
     const size_t threads = ((size_t)H * W) << sh;
     hipLaunchKernelGGL(conv_first_dgrad_kernel<T>, dim3((unsigned)((threads + 255) / 256)),
-                       dim3(256), lds, st, static_cast<const T*>(dy), wf, dx, H, W, cin, cout, sh);
+                       dim3(256), lds, st, static_cast<const T*>(dy), packed, dx, H, W, cin, cout, sh);
   } else {
     const size_t total = (size_t)H * W * cin;
     hipLaunchKernelGGL(conv_first_dgrad_generic<T>, dim3((unsigned)((total + 255) / 256)),
-                       dim3(256), 0, st, static_cast<const T*>(dy), wf, dx, H, W, cin, cout);
+                       dim3(256), 0, st, static_cast<const T*>(dy), packed, dx, H, W, cin, cout);
   }
   STV_CHECK_LAUNCH();
   return STV_OK;
@@ -756,20 +774,20 @@ int dgrad_typed(const void* dy, const float* wf, const float* packed, float* dx,
 }  // namespace
 
 extern "C" size_t stv_conv_first_packed_bytes(int cin, int cout) {
-  const size_t plain = (size_t)2 * 9 * (size_t)(cin > 0 ? cin : 0) * (size_t)(cout > 0 ? cout : 0) * sizeof(float);
-  return (cin == 3 && cout == 64) ? plain + (size_t)(MF_FRAG_WORDS + DG_FRAG_WORDS) * 4 : plain;   // + matrix-core fragments
+  if (cin <= 0 || cout <= 0) return 0;
+  return (vgg_shape(cin, cout) ? (size_t)Packed::kWords : (size_t)9 * cin * cout) * sizeof(float);
 }
 
 extern "C" int stv_conv_first_pack(const float* wf, float* packed, int cin, int cout, void* stream) {
   if (!wf || !packed || cin <= 0 || cout <= 0) return STV_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (cin == 3 && cout == 64) {
-    hipLaunchKernelGGL(repack_first_weights, dim3(7), dim3(256), 0, st, wf, packed, 0);
-    hipLaunchKernelGGL(repack_first_weights, dim3(7), dim3(256), 0, st, wf, packed + 1728, 1);
+  if (vgg_shape(cin, cout)) {
+    hipLaunchKernelGGL(repack_first_weights, dim3(7), dim3(256), 0, st, wf, packed + Packed::kFwd, 0);
+    hipLaunchKernelGGL(repack_first_weights, dim3(7), dim3(256), 0, st, wf, packed + Packed::kFlipped, 1);
     hipLaunchKernelGGL(pack_first_fragments, dim3(MF_FRAG_WORDS / 256), dim3(256), 0, st, wf,
-                       reinterpret_cast<uint32_t*>(packed + 2 * 1728));
+                       Packed::frags(packed, Packed::kFwdFrags));
     hipLaunchKernelGGL(pack_first_dgrad_fragments, dim3((DG_FRAG_WORDS + 255) / 256), dim3(256), 0, st, wf,
-                       reinterpret_cast<uint32_t*>(packed + 2 * 1728 + MF_FRAG_WORDS));
+                       Packed::frags(packed, Packed::kDgradFrags));
     STV_CHECK_LAUNCH();
     return STV_OK;
   }
@@ -779,50 +797,25 @@ extern "C" int stv_conv_first_pack(const float* wf, float* packed, int cin, int 
   return STV_OK;
 }
 
-extern "C" int stv_conv_first_fwd_packed(const float* x_nchw, const float* packed, const float* bias, void* y,
-                                         int H, int W, int cin, int cout, int dtype, void* stream) {
+extern "C" int stv_conv_first_gram_supported(int H, int W, int cin, int cout, int dtype) {
+  return (on_matrix_cores(cin, cout, dtype) && H > 0 && W > 0) ? 1 : 0;
+}
+
+extern "C" int stv_conv_first_fwd(const float* x_nchw, const float* packed, const float* bias, void* y,
+                                  float* gram_partials, int H, int W, int cin, int cout, int dtype, void* stream) {
   if (!x_nchw || !packed || !y || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return STV_ERR_ARG;
+  if (gram_partials && !stv_conv_first_gram_supported(H, W, cin, cout, dtype)) return STV_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == STV_F32) return fwd_typed<float>(x_nchw, packed, packed, bias, y, H, W, cin, cout, st);
-  if (dtype == STV_BF16) return fwd_typed<bf16_t>(x_nchw, packed, packed, bias, y, H, W, cin, cout, st);
+  if (dtype == STV_F32) return fwd_typed<float>(x_nchw, packed, bias, y, H, W, cin, cout, st, gram_partials);
+  if (dtype == STV_BF16) return fwd_typed<bf16_t>(x_nchw, packed, bias, y, H, W, cin, cout, st, gram_partials);
   return STV_ERR_ARG;
 }
 
-extern "C" int stv_conv_first_fwd_gram(const float* x_nchw, const float* packed, const float* bias, void* y,
-                                       float* gram_partials, int H, int W, int cin, int cout, int dtype, void* stream) {
-  if (!x_nchw || !packed || !y || !gram_partials || H <= 0 || W <= 0) return STV_ERR_ARG;
-  if (cin != 3 || cout != 64 || dtype != STV_BF16) return STV_ERR_ARG;     // the matrix-core first layer only
-  if (!stv_conv_first_gram_supported(H, W, cin, cout, dtype)) return STV_ERR_ARG;
-  return fwd_typed<bf16_t>(x_nchw, packed, packed, bias, y, H, W, cin, cout, static_cast<hipStream_t>(stream), gram_partials);
-}
-
-extern "C" int stv_conv_first_gram_supported(int H, int W, int cin, int cout, int dtype) {
-  return (cin == 3 && cout == 64 && dtype == STV_BF16 && H > 0 && W > 0 && !getenv("STV_FIRST_VALU")) ? 1 : 0;
-}
-
-extern "C" int stv_conv_first_dgrad_packed(const void* dy, const float* packed, float* dx_nchw, int H, int W,
-                                           int cin, int cout, int dtype, void* stream) {
+extern "C" int stv_conv_first_dgrad(const void* dy, const float* packed, float* dx_nchw, int H, int W,
+                                    int cin, int cout, int dtype, void* stream) {
   if (!dy || !packed || !dx_nchw || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return STV_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == STV_F32) return dgrad_typed<float>(dy, packed, packed, dx_nchw, H, W, cin, cout, st);
-  if (dtype == STV_BF16) return dgrad_typed<bf16_t>(dy, packed, packed, dx_nchw, H, W, cin, cout, st);
-  return STV_ERR_ARG;
-}
-
-extern "C" int stv_conv_first_fwd(const float* x_nchw, const float* wf, const float* bias, void* y,
-                                  int H, int W, int cin, int cout, int dtype, void* stream) {
-  if (!x_nchw || !wf || !y || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return STV_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == STV_F32) return fwd_typed<float>(x_nchw, wf, nullptr, bias, y, H, W, cin, cout, st);
-  if (dtype == STV_BF16) return fwd_typed<bf16_t>(x_nchw, wf, nullptr, bias, y, H, W, cin, cout, st);
-  return STV_ERR_ARG;
-}
-
-extern "C" int stv_conv_first_dgrad(const void* dy, const float* wf, float* dx_nchw, int H, int W,
-                                    int cin, int cout, int dtype, void* stream) {
-  if (!dy || !wf || !dx_nchw || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return STV_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == STV_F32) return dgrad_typed<float>(dy, wf, nullptr, dx_nchw, H, W, cin, cout, st);
-  if (dtype == STV_BF16) return dgrad_typed<bf16_t>(dy, wf, nullptr, dx_nchw, H, W, cin, cout, st);
+  if (dtype == STV_F32) return dgrad_typed<float>(dy, packed, dx_nchw, H, W, cin, cout, st);
+  if (dtype == STV_BF16) return dgrad_typed<bf16_t>(dy, packed, dx_nchw, H, W, cin, cout, st);
   return STV_ERR_ARG;
 }

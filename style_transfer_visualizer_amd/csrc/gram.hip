@@ -716,7 +716,7 @@ extern "C" int stv_gram_multi(const stv_gram_tap_t* taps, int n_taps, int dtype,
   PartialMulti by_tile[2] = {};              // [TS == 128]
   for (int i = 0; i < n_taps; ++i) {
     const stv_gram_tap_t& t = taps[i];
-    if (!t.F) continue;                      // F == NULL: the producer left the slabs (stv_conv_first_fwd_gram)
+    if (!t.F) continue;                      // F == NULL: the producer left the slabs (stv_conv_first_fwd, gram_partials)
     add_tap(by_tile[gram_tile(t.channels) == 128], t.F, t.partials, t.n_pixels, t.channels, pixels_per_stage(dtype));
   }
   const PartialMulti& m64 = by_tile[0];

@@ -21,21 +21,12 @@ namespace {
 
 int run_op(const stv_op_t& o, void* st) {
   switch (o.op) {
-    case STV_OP_CONV_FIRST_FWD:   // p3 (optional): weights packed by stv_conv_first_pack
-      if (o.p3 && o.q1)    // the layer is a style tap: q1 = Gram slabs (stv_gram_partial's output, fused)
-        return stv_conv_first_fwd_gram(static_cast<const float*>(o.p0), static_cast<const float*>(o.p3),
-                                       static_cast<const float*>(o.p2), o.q0, static_cast<float*>(o.q1), o.H, o.W, o.cin,
-                                       o.cout, o.dtype, st);
-      if (o.p3)
-        return stv_conv_first_fwd_packed(static_cast<const float*>(o.p0), static_cast<const float*>(o.p3),
-                                         static_cast<const float*>(o.p2), o.q0, o.H, o.W, o.cin, o.cout, o.dtype, st);
-      return stv_conv_first_fwd(static_cast<const float*>(o.p0), static_cast<const float*>(o.p1),
-                                static_cast<const float*>(o.p2), o.q0, o.H, o.W, o.cin, o.cout, o.dtype, st);
-    case STV_OP_CONV_FIRST_DGRAD:  // p2 (optional): packed weights
-      if (o.p2)
-        return stv_conv_first_dgrad_packed(o.p0, static_cast<const float*>(o.p2), static_cast<float*>(o.q0), o.H,
-                                           o.W, o.cin, o.cout, o.dtype, st);
-      return stv_conv_first_dgrad(o.p0, static_cast<const float*>(o.p1), static_cast<float*>(o.q0), o.H,
+    case STV_OP_CONV_FIRST_FWD:   // p3: weights packed by stv_conv_first_pack; q1: Gram slabs where the layer is a style tap
+      return stv_conv_first_fwd(static_cast<const float*>(o.p0), static_cast<const float*>(o.p3),
+                                static_cast<const float*>(o.p2), o.q0, static_cast<float*>(o.q1), o.H, o.W, o.cin,
+                                o.cout, o.dtype, st);
+    case STV_OP_CONV_FIRST_DGRAD:  // p2: packed weights
+      return stv_conv_first_dgrad(o.p0, static_cast<const float*>(o.p2), static_cast<float*>(o.q0), o.H,
                                   o.W, o.cin, o.cout, o.dtype, st);
     case STV_OP_CONV:
       if (o.flags & STV_POOL_ROUTE)   // dgrad in front of a max-pool: p2 = arg-max byte map, q1 = full-resolution gradient
@@ -128,7 +119,7 @@ int run_all(stv_program* p, void* st) {
 
 }  // namespace
 
-extern "C" int stv_version(void) { return 107; }
+extern "C" int stv_version(void) { return 108; }
 
 extern "C" int stv_program_create(const stv_op_t* ops, int n_ops, stv_program** out) {
   if (!ops || n_ops <= 0 || !out) return STV_ERR_ARG;

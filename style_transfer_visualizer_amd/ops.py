@@ -127,7 +127,7 @@ def from_nhwc(x: torch.Tensor) -> torch.Tensor:
 # ---- conv ---------------------------------------------------------------------
 
 def conv_first_pack(wf: torch.Tensor) -> torch.Tensor:
-    """Kernel-side packing of a frozen first-layer weight [9,Cout,Cin] (fp32), done once (stv_conv_first_pack)."""
+    """Kernel-side form of a frozen first-layer weight [9,Cout,Cin] (fp32), any shape: what both directions read."""
     _, cout, cin = wf.shape
     lib = _lib.load()
     packed = torch.empty(int(lib.stv_conv_first_packed_bytes(cin, cout)) // 4, device=wf.device, dtype=torch.float32)
@@ -136,33 +136,26 @@ def conv_first_pack(wf: torch.Tensor) -> torch.Tensor:
 
 
 def conv_first_gram_supported(H: int, W: int, cin: int, cout: int, dtype: torch.dtype) -> bool:
-    """True when the first layer can leave the Gram slabs of its own output (stv_conv_first_fwd_gram)."""
+    """True when the first layer can leave the Gram slabs of its own output (``gram_partials`` of conv_first_fwd)."""
     return bool(_lib.load().stv_conv_first_gram_supported(H, W, cin, cout, dtype_code(dtype)))
 
 
 def conv_first_fwd(x_nchw: torch.Tensor, wf: torch.Tensor, bias: torch.Tensor | None,
                    dtype: torch.dtype, out: torch.Tensor | None = None, *,
                    packed: torch.Tensor | None = None, gram_partials: torch.Tensor | None = None) -> torch.Tensor:
-    """``packed`` (from :func:`conv_first_pack`) skips the per-call weight repack.  ``gram_partials``
-    ([gram_ksplit(H*W, cout), cout, cout] fp32; needs ``packed``): also filled, as :func:`gram_partial` of the result would."""
+    """``packed``: the weights from :func:`conv_first_pack`; None packs ``wf`` here (a torch-owned buffer, this stream).
+    ``gram_partials`` ([gram_ksplit(H*W, cout), cout, cout] fp32; needs ``packed``): also filled, as :func:`gram_partial`
+    of the result would."""
     _, cin, H, W = x_nchw.shape
     cout = wf.shape[1]
-    if packed is None and gram_partials is None and (cin, cout) == (3, 64):
-        packed = conv_first_pack(wf)      # the 3 -> 64 kernels read the kernel-side order (a torch-owned buffer, this stream)
+    if gram_partials is not None and (packed is None or tuple(gram_partials.shape) != (gram_ksplit(H * W, cout), cout, cout)):
+        raise ValueError("gram_partials needs packed weights and [gram_ksplit(H*W, cout), cout, cout] slabs")
+    if packed is None:
+        packed = conv_first_pack(wf)
     if out is None:
         out = torch.empty(H, W, cout, device=x_nchw.device, dtype=dtype)
-    lib = _lib.load()
-    if gram_partials is not None:
-        if packed is None or tuple(gram_partials.shape) != (gram_ksplit(H * W, cout), cout, cout):
-            raise ValueError("gram_partials needs packed weights and [gram_ksplit(H*W, cout), cout, cout] slabs")
-        _lib.check(lib.stv_conv_first_fwd_gram(_ptr(x_nchw), _ptr(packed), _ptr(bias), _ptr(out), _ptr(gram_partials),
-                                               H, W, cin, cout, dtype_code(dtype), _stream()), "stv_conv_first_fwd_gram")
-    elif packed is not None:
-        _lib.check(lib.stv_conv_first_fwd_packed(_ptr(x_nchw), _ptr(packed), _ptr(bias), _ptr(out), H, W, cin, cout,
-                                                 dtype_code(dtype), _stream()), "stv_conv_first_fwd_packed")
-    else:
-        _lib.check(lib.stv_conv_first_fwd(_ptr(x_nchw), _ptr(wf), _ptr(bias), _ptr(out), H, W, cin, cout,
-                                          dtype_code(dtype), _stream()), "stv_conv_first_fwd")
+    _lib.check(_lib.load().stv_conv_first_fwd(_ptr(x_nchw), _ptr(packed), _ptr(bias), _ptr(out), _ptr(gram_partials),
+                                              H, W, cin, cout, dtype_code(dtype), _stream()), "stv_conv_first_fwd")
     return out
 
 
@@ -171,15 +164,10 @@ def conv_first_dgrad(dy: torch.Tensor, wf: torch.Tensor, cin: int,
     H, W, cout = dy.shape
     if out is None:
         out = torch.empty(1, cin, H, W, device=dy.device, dtype=torch.float32)
-    lib = _lib.load()
-    if packed is None and (cin, cout) == (3, 64):
+    if packed is None:
         packed = conv_first_pack(wf)
-    if packed is not None:
-        _lib.check(lib.stv_conv_first_dgrad_packed(_ptr(dy), _ptr(packed), _ptr(out), H, W, cin, cout,
-                                                   dtype_code(dy.dtype), _stream()), "stv_conv_first_dgrad_packed")
-    else:
-        _lib.check(lib.stv_conv_first_dgrad(_ptr(dy), _ptr(wf), _ptr(out), H, W, cin, cout,
-                                            dtype_code(dy.dtype), _stream()), "stv_conv_first_dgrad")
+    _lib.check(_lib.load().stv_conv_first_dgrad(_ptr(dy), _ptr(packed), _ptr(out), H, W, cin, cout,
+                                                dtype_code(dy.dtype), _stream()), "stv_conv_first_dgrad")
     return out
 
 

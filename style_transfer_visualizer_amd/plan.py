@@ -104,6 +104,7 @@ class Node:
     layer: int = -1
     wf: torch.Tensor | None = None
     wb: torch.Tensor | None = None
+    packed: torch.Tensor | None = None  # conv_first: the kernel-side form of wf (ops.conv_first_pack), read by both directions
     bias: torch.Tensor | None = None
     cin: int = 0
     # fixed by Schedule._decide:
@@ -121,7 +122,7 @@ class Tap:
     target: torch.Tensor | None = None
     # style
     partials: torch.Tensor | None = None
-    partials_fused: bool = False      # the producing conv fills `partials` itself (stv_conv_first_fwd_gram)
+    partials_fused: bool = False      # the producing conv fills `partials` itself (stv_conv_first_fwd's gram_partials)
     sgrad: torch.Tensor | None = None
     parts_off: int = 0
     parts_cnt: int = 0
@@ -225,7 +226,7 @@ class Schedule:
                         raise RuntimeError(msg)
                     node = Node("conv_first", None, dst, layer=i, wf=ops.pack_weights_fwd(w), bias=bias, cin=cin)
                     if self.device.type == "cuda":
-                        node.wb = ops.conv_first_pack(node.wf)   # frozen weights: kernel-side packing, once
+                        node.packed = ops.conv_first_pack(node.wf)   # frozen weights: kernel-side packing, once
                 else:
                     wf = ops.pack_weights_fwd(w).to(self.dtype)
                     wb = ops.pack_weights_bwd(w).to(self.dtype) if self.with_grad else None
@@ -426,7 +427,7 @@ class Schedule:
             if nd.kind == "conv_first":
                 tap = next((t for t in d.taps if t.kind == "style"), None)
                 slabs = tap.partials if tap is not None and tap.partials_fused else None
-                out.append(self.emit(op=OP_CONV_FIRST_FWD, p0=x, p1=nd.wf, p2=nd.bias, p3=nd.wb, q0=d.act, q1=slabs,
+                out.append(self.emit(op=OP_CONV_FIRST_FWD, p0=x, p2=nd.bias, p3=nd.packed, q0=d.act, q1=slabs,
                                      H=d.H, W=d.W, cin=nd.cin, cout=d.C))
             elif nd.kind == "conv":
                 pool = self.nodes[k + 1] if k + 1 < len(self.nodes) and self.nodes[k + 1].fused else None
@@ -603,7 +604,7 @@ class Schedule:
                 out.append(self.emit(op=OP_RELU_BWD, p0=d.act, p1=rd(d), q0=d.grad, n=d.act.numel()))
             s = nd.src
             if nd.kind == "conv_first":
-                out.append(self.emit(op=OP_CONV_FIRST_DGRAD, p0=rd(d), p1=nd.wf, p2=nd.wb, q0=x_grad, H=d.H, W=d.W,
+                out.append(self.emit(op=OP_CONV_FIRST_DGRAD, p0=rd(d), p2=nd.packed, q0=x_grad, H=d.H, W=d.W,
                                      cin=nd.cin, cout=d.C))
                 continue
             mask_src = nd.relu_in or (s.relu_fused and not s.taps)

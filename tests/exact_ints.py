@@ -379,15 +379,15 @@ def _route_case(cd: int, cs: int, H: int, W: int, salt: int) -> dict:
 
 
 @functools.lru_cache(maxsize=None)
-def first_case(H: int, W: int) -> dict:
-    """First layer 3 -> 64: small integers, which every variant (VALU, packed, the split product) multiplies exactly.
-    want_f32 / want_bf16: conv + bias (integer bias: the Gram slabs of the stored map stay integers); dx: the dgrad of
-    an integer dy, exact in fp32."""
-    x = ints((1, 3, H, W), 1040, -3, 3)
-    w = ints((64, 3, 3, 3), 1041, -2, 2)
-    b = ints((64,), 1042, -8, 8)
-    dy = ints((1, 64, H, W), 1043, -3, 3)
-    what = f"first layer {H}x{W}"
+def first_case(H: int, W: int, *, cin: int = 3, cout: int = 64) -> dict:
+    """First layer cin -> cout: small integers, which every kernel (VALU, the split product on the matrix cores)
+    multiplies exactly.  want: conv + bias (integer bias: the Gram slabs of the stored map stay integers), a value
+    bf16 holds too; dx: the dgrad of an integer dy, exact in fp32."""
+    x = ints((1, cin, H, W), 1040, -3, 3)
+    w = ints((cout, cin, 3, 3), 1041, -2, 2)
+    b = ints((cout,), 1042, -8, 8)
+    dy = ints((1, cout, H, W), 1043, -3, 3)
+    what = f"first layer {cin}->{cout} {H}x{W}"
     val, bud = product("bf16", x, w)
     val, bud = val + b.double().view(1, -1, 1, 1), bud + b.double().abs().view(1, -1, 1, 1)
     check_budget(bud, 1.0, what)
@@ -395,7 +395,7 @@ def first_case(H: int, W: int) -> dict:
     wt = w.flip(2, 3).transpose(0, 1).contiguous()
     dx, dbud = product("bf16", dy, wt)
     check_budget(dbud, 1.0, what + " dgrad")
-    y = val[0].permute(1, 2, 0).reshape(H * W, 64)
+    y = val[0].permute(1, 2, 0).reshape(H * W, cout)
     gram = y.t() @ y
     check_budget(y.abs().t() @ y.abs(), 1.0, what + " gram")
     return {"x": x, "w": w, "b": b, "dy": dy, "want": nhwc(store("fp32", val)), "dx": store("fp32", dx), "gram": store("fp32", gram)}
@@ -487,6 +487,9 @@ WS_SHAPES = [(64, 64, 13, 7), (64, 64, 8, 32), (64, 64, 75, 101), (64, 128, 40, 
 
 FIRST_HW = [(40, 72), (5, 7), (64, 64), (33, 100), (1, 1), (1, 37), (37, 1)]
 FIRST_GRAM_HW = [(64, 64), (75, 101), (13, 7), (8, 32)]
+# first layers that are not 3 -> 64 (tests/test_gpu_conv_exact.py::test_first_layer_other_shapes names the kernel each reaches)
+FIRST_OTHER = [(3, 8), (3, 16), (4, 32), (3, 4), (3, 12), (5, 8), (1, 8), (4, 512)]
+FIRST_OTHER_HW = [(1, 1), (5, 7), (17, 40)]
 GRAM_SHAPES = [(n, C) for C in (8, 12, 64, 100, 128, 256, 512) for n in (777, 4099)] + [(64, 64), (1, 8), (63, 128)]
 # (a channel count must fill whole 16-byte groups of the storage type: 12 and 100 in fp32 / bf16x3 only)
 GRAM_PARAMS = [(p, n, C) for p in PRECISIONS for n, C in GRAM_SHAPES if C % store_group(p) == 0]

@@ -80,7 +80,7 @@ def test_storage_only_entry_points_reject_bf16x3():
     assert lib.stv_content_loss(p, p, p, ctypes.c_size_t(64), X3, None) == 1
     assert lib.stv_gram_finish(p, None, p, p, None, 64, 64, ctypes.c_float(5e5), ctypes.c_float(1.0),
                                ctypes.c_float(1.0), None, X3, None) == 1
-    assert lib.stv_conv_first_fwd(p, p, None, p, 8, 8, 3, 64, X3, None) == 1
+    assert lib.stv_conv_first_fwd(p, p, None, p, None, 8, 8, 3, 64, X3, None) == 1
     assert lib.stv_conv_first_dgrad(p, p, p, 8, 8, 3, 64, X3, None) == 1
     assert lib.stv_conv_igemm_route(p, p, p, p, 8, 8, 64, 64, 0, X3, None) == 1
 

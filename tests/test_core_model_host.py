@@ -655,7 +655,11 @@ def test_ops_own_their_operands():
     alive = weakref.ref(x)
     op_list = s.forward_ops(x)
     kept = plan.operands(op_list)
-    for t in [x] + [nd.dst.act for nd in s.nodes if nd.dst.stored] + [nd.wf for nd in s.nodes if nd.wf is not None]:
+    # (the first layer's op names the kernel-side form of its weights, Node.packed - which a host schedule has no kernel
+    # to make - and not wf)
+    first = s.nodes[0]
+    assert first.kind == "conv_first" and first.packed is None and not any(first.wf is k for k in kept)
+    for t in [x] + [nd.dst.act for nd in s.nodes if nd.dst.stored] + [nd.wf for nd in s.nodes if nd.kind == "conv"]:
         assert any(t is k for k in kept)
     del kept, x
     gc.collect()

@@ -50,6 +50,9 @@ def test_other_generators_hold():
             ei.dual_case("bf16", cin, cout, cout, H, W, True)
     for hw in ei.FIRST_HW + ei.FIRST_GRAM_HW:
         ei.first_case(*hw)
+    for cin, cout in ei.FIRST_OTHER:
+        for hw in ei.FIRST_OTHER_HW:
+            ei.first_case(*hw, cin=cin, cout=cout)
     for prec, n, C in ei.GRAM_PARAMS:
         ei.gram_case(prec, n, C)
     for H, W, C in ei.FINISH_SHAPES:

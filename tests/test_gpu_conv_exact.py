@@ -279,17 +279,13 @@ def test_direct_kernel_is_reported(monkeypatch):
 
 
 @pytest.mark.parametrize("hw", ei.FIRST_HW, ids=lambda s: "x".join(map(str, s)))
-@pytest.mark.parametrize("variant", ["fp32", "bf16-matrix", "bf16-valu"])
+@pytest.mark.parametrize("variant", ["fp32", "bf16-matrix"])
 @pytest.mark.parametrize("packed", [False, True])
-def test_first_layer_forward_and_dgrad(hw, variant, packed, monkeypatch):
-    """conv_first_fwd / conv_first_dgrad: the fp32 kernels, the bf16 split-product kernels on the matrix cores and the
-    bf16 VALU kernels (STV_FIRST_VALU), with caller-packed and call-packed weights, down to 1 x 1, 1 x 37 and 37 x 1."""
+def test_first_layer_forward_and_dgrad(hw, variant, packed):
+    """conv_first_fwd / conv_first_dgrad: the fp32 kernels and the bf16 split-product kernels on the matrix cores, with
+    caller-packed and call-packed weights, down to 1 x 1, 1 x 37 and 37 x 1."""
     H, W = hw
     dtype = torch.float32 if variant == "fp32" else torch.bfloat16
-    if variant == "bf16-valu":
-        monkeypatch.setenv("STV_FIRST_VALU", "1")
-    else:
-        monkeypatch.delenv("STV_FIRST_VALU", raising=False)
     c = ei.first_case(H, W)
     wf = ops.pack_weights_fwd(c["w"]).to(DEV)
     pk = ops.conv_first_pack(wf) if packed else None
@@ -298,6 +294,28 @@ def test_first_layer_forward_and_dgrad(hw, variant, packed, monkeypatch):
     same(y, c["want"].to(dtype), "first_layer", what + " forward")
     dx = ops.conv_first_dgrad(ops.to_nhwc(c["dy"], dtype).to(DEV), wf, 3, out=sentinel((1, 3, H, W), torch.float32), packed=pk)
     same(dx, c["dx"], "first_layer", what + " dgrad")
+
+
+@pytest.mark.parametrize("hw", ei.FIRST_OTHER_HW, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("shape", ei.FIRST_OTHER, ids=lambda s: "to".join(map(str, s)))
+def test_first_layer_other_shapes(shape, dtype, hw):
+    """First layers that are not 3 -> 64: the lanes-per-pixel kernels (conv_first_*_kernel; one 16-byte channel vector
+    per lane, 4 channels in fp32 and 8 in bf16) and the one-thread-per-output kernels (conv_first_*_generic).
+    (cin, cout) -> kernel, fp32 / bf16:  (3, 8): 2 / 1 lanes per pixel;  (3, 16): 4 / 2;  (4, 32): 8 / 4, cin at kMaxCin;
+    (3, 4): 1 lane / generic;  (3, 12): generic, 3 lanes is no power of two / generic;  (5, 8): forward lanes-per-pixel,
+    dgrad generic (cin > kMaxCin);  (1, 8): lanes-per-pixel;  (4, 512): generic, more than 64 lanes / 72 KiB of weights.
+    1 x 1 is a single pixel, 5 x 7 and 17 x 40 leave a ragged last workgroup; with the weights packed here and by the caller."""
+    cin, cout = shape
+    H, W = hw
+    c = ei.first_case(H, W, cin=cin, cout=cout)
+    wf = ops.pack_weights_fwd(c["w"]).to(DEV)
+    for pk in (None, ops.conv_first_pack(wf)):
+        what = f"first layer {cin}->{cout} {H}x{W} {dtype} packed={pk is not None}"
+        y = ops.conv_first_fwd(c["x"].to(DEV), wf, c["b"].to(DEV), dtype, out=sentinel((H, W, cout), dtype), packed=pk)
+        same(y, c["want"].to(dtype), "first_layer_other", what + " forward")
+        dx = ops.conv_first_dgrad(ops.to_nhwc(c["dy"], dtype).to(DEV), wf, cin, out=sentinel((1, cin, H, W), torch.float32), packed=pk)
+        same(dx, c["dx"], "first_layer_other", what + " dgrad")
 
 
 @pytest.mark.parametrize("hw", ei.FIRST_GRAM_HW, ids=lambda s: "x".join(map(str, s)))

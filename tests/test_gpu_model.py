@@ -427,7 +427,7 @@ def test_bf16_storage_tracks_fp32(monkeypatch):
 
 
 def test_first_layer_gram_fusion_is_equivalent(monkeypatch):
-    """bf16 mode, conv1_1 tapped: the first layer leaving its own Gram slabs (stv_conv_first_fwd_gram, forced
+    """bf16 mode, conv1_1 tapped: the first layer leaving its own Gram slabs (stv_conv_first_fwd's gram_partials, forced
     on at this small size) against the separate Gram pass - same targets and losses up to the fp32 summation
     order of the slabs, same gradient up to what a last-bit change of the bf16 seed S moves."""
     case = GoldenCase("vgg19_white_lbfgs")
@@ -645,7 +645,7 @@ def test_device_form_of_the_whole_step_matches_the_device(monkeypatch, dtype):
             self.op_list = list(op_list)
             super().__init__(op_list, extra)
     host = host_engine(monkeypatch, dtype, 64, 64, [0, 5, 10, 19, 28], [21])      # (also: the step's switches at their defaults)
-    host.sched.nodes[0].wb = torch.empty(1)
+    host.sched.nodes[0].packed = torch.empty(1)
     xh = torch.zeros(1, 3, 64, 64)
     on_host = fused_step(host, xh, torch.zeros_like(xh))
     layers = list(core_model.build_vgg_features().eval().children())

@@ -64,8 +64,8 @@ def assert_close(got, ref, dtype, k_terms=1, what=""):
 @pytest.mark.parametrize("packed", [False, True])
 @pytest.mark.parametrize("hw", [(40, 72), (5, 7), (64, 64), (33, 100)])
 def test_conv_first_fwd_and_dgrad(dtype, hw, packed):
-    """packed=True: weights prepared once (stv_conv_first_pack); in bf16 the forward then runs on the
-    matrix cores with two-term bf16 splits of image and weights - same tolerance as the VALU kernel."""
+    """packed=True: weights prepared once by the caller (stv_conv_first_pack), otherwise by the call itself - the same
+    kernels either way: in bf16 on the matrix cores with two-term bf16 splits of image and weights, in fp32 on the VALU."""
     H, W = hw
     cout = 64
     x = rnd((1, 3, H, W), 1, -2, 2)
@@ -94,7 +94,7 @@ def test_conv_first_fwd_and_dgrad(dtype, hw, packed):
 
 @pytest.mark.parametrize("hw", [(64, 64), (75, 101), (13, 7), (8, 32), (256, 320), (512, 512)])
 def test_conv_first_fwd_leaves_gram_slabs(hw):
-    """stv_conv_first_fwd_gram: the tapped first layer also writes the split-K slabs of F^T F that
+    """stv_conv_first_fwd with gram_partials: the tapped first layer also writes the split-K slabs of F^T F that
     stv_gram_partial computes from the stored map - same map bit for bit, same Gram matrix up to the
     fp32 summation order (ragged tiles, single-tile images, idle workgroups that must write zero slabs)."""
     H, W = hw

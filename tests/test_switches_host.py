@@ -40,7 +40,7 @@ def test_design_switch_table_matches_the_variables_the_package_reads():
     code, table = _names_read_by_the_package(), _names_in_the_design_table()
     assert code - table == set(), "read by the package, no row in DESIGN.md §9"
     assert table - code == set(), "row in DESIGN.md §9, read nowhere in the package"
-    assert len(code) == len(table) == 39
+    assert len(code) == len(table) == 36
 
 
 def test_removed_switches_are_named_nowhere_in_code_tools_or_tests():

@@ -1,5 +1,4 @@
-"""Times the bf16 first-layer kernels (forward, forward + Gram slabs, dgrad) at 512^2 and 1024^2 - with a diagnostic
-build (STV_LIB_PATH, -DSTV_FIRST_DIAG=n) this is the knock-out table of DESIGN §3.6."""
+"""Times the bf16 first-layer kernels (forward, forward + Gram slabs, dgrad) at 512^2 and 1024^2."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
