@@ -289,6 +289,29 @@ enum { STV_RESIZE_DOWN2 = 0, STV_RESIZE_UP2 = 1 };
  * an output of 2 GiB or more. */
 int stv_resize2x(const float* x, float* y, int C, int H, int W, int mode, void* stream);
 
+/* ---- General resize of an input image (--content-size, --style-size, --style-scale; no counterpart in the reference).
+ *      Since version 109.  One pass of a separable, antialiased resampler: the image is resized along one axis by the
+ *      tables the host builds (resize.py: triangle, Keys cubic or Lanczos-3, stretched by the scale factor on a
+ *      downscale).  Output index i along that axis is
+ *        acc = 0.0f;  for k = 0 .. count[i]-1 ascending:  acc = acc + (weights[i*K + k] * x[.. start[i] + k ..])
+ *      with every product and every sum rounded to fp32 on its own (no FMA contraction), so that an fp32 twin reproduces
+ *      every output bit.  A full resize is the column pass (axis 1) into an intermediate [planes][H][Wo], then the row
+ *      pass (axis 0); the caller owns the intermediate and the tables, and skips a pass whose axis keeps its size.
+ *      Nothing is read across a row end or a channel plane; entries of `weights` behind count[i] are never read. ------ */
+/* launch constants: a work item is STV_RESIZE_AXIS_VEC consecutive output pixels of one row, a pass of the capped grid
+ * covers STV_RESIZE_AXIS_MAX_BLOCKS * STV_RESIZE_AXIS_THREADS items.  Vector path: output rows of a multiple of four
+ * floats behind a 16-byte aligned y (and, for axis 0, x); otherwise the same items with guarded scalar accesses. */
+#define STV_RESIZE_AXIS_VEC 4
+#define STV_RESIZE_AXIS_THREADS 256
+#define STV_RESIZE_AXIS_MAX_BLOCKS 1024
+/* x NCHW fp32 [planes][H][W] -> y NCHW fp32: axis 0 [planes][n_out][W] (rows), axis 1 [planes][H][n_out] (columns).
+ * start, count: int32 [n_out] on the device, start[i] >= 0 and start[i] + count[i] <= the input's size along the axis;
+ * weights: fp32 [n_out][K] on the device, K >= max(count).  x != y.
+ * STV_ERR_ARG, before any device work: a null pointer, x == y, a non-positive size, an axis other than 0 or 1, K < 1,
+ * an input or an output of 2 GiB or more. */
+int stv_resize_axis(const float* x, float* y, int planes, int H, int W, int n_out, int axis, const int32_t* start,
+                    const int32_t* count, const float* weights, int K, void* stream);
+
 /* ---- Colour preservation (--preserve-color; no counterpart in the reference; Gatys et al. 2017, "Controlling
  *      perceptual factors in neural style transfer", section 5).  Since version 107.  Three streaming passes over the
  *      image, none of them inside the step.  All three take NCHW fp32 [3][H][W] and return STV_ERR_ARG, before any HIP

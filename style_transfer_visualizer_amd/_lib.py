@@ -30,6 +30,9 @@ RESIZE_DOWN2, RESIZE_UP2 = 0, 1                     # stv.h STV_RESIZE_*: the mo
 # launch constants of stv_resize2x (stv.h STV_RESIZE_THREADS, STV_RESIZE_MAX_BLOCKS; pixels per work item): a work item is
 # RESIZE_VEC consecutive OUTPUT pixels of one row, a pass of the capped grid covers RESIZE_MAX_BLOCKS * RESIZE_THREADS items
 RESIZE_THREADS, RESIZE_MAX_BLOCKS, RESIZE_VEC = 256, 1024, 4
+# launch constants of stv_resize_axis (stv.h STV_RESIZE_AXIS_*; csrc/resize.hip), with the same meaning: a work item is
+# RESIZE_AXIS_VEC consecutive OUTPUT pixels of one row, a pass covers RESIZE_AXIS_MAX_BLOCKS * RESIZE_AXIS_THREADS items
+RESIZE_AXIS_THREADS, RESIZE_AXIS_MAX_BLOCKS, RESIZE_AXIS_VEC = 256, 1024, 4
 # launch constants of the three colour kernels (stv.h STV_COLOR_*; csrc/color.hip): a work item is COLOR_VEC consecutive
 # pixels of one row read from all three planes; stv_color_stats always runs COLOR_STATS_PARTS workgroups (one row of nine
 # doubles each), stv_color_affine and stv_luma_transfer at most COLOR_MAX_BLOCKS, all of COLOR_THREADS threads
@@ -110,6 +113,7 @@ SIGNATURES = {
     "stv_content_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_int, c_int, c_void_p]),
     "stv_tv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "stv_resize2x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "stv_resize_axis": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "stv_color_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "stv_color_affine": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int, c_void_p]),
     "stv_luma_transfer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),

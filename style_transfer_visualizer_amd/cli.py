@@ -2,7 +2,9 @@
 
 Options that only have meaning for presentation features outside this build (comparison grids)
 are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,bf16x3}``, ``--tv-w``,
-``--pyramid-levels`` / ``--pyramid-steps``, ``--preserve-color {off,match,luma}``.
+``--pyramid-levels`` / ``--pyramid-steps``, ``--preserve-color {off,match,luma}``, ``--content-size`` / ``--style-size`` /
+``--style-scale`` / ``--resize-filter {bilinear,bicubic,lanczos}`` (``--content`` and ``--style`` stay exact options: argparse
+prefers an exact match to a prefix).
 """
 from __future__ import annotations
 
@@ -48,6 +50,15 @@ def build_arg_parser() -> argparse.ArgumentParser:
     opt.add_argument("--preserve-color", choices=["off", "match", "luma"], default=S,
                      help="Keep the content image's colours: match = give the style image the content's colour mean and "
                           "covariance before the run, luma = keep only the result's luminance (off = the default)")
+    opt.add_argument("--content-size", type=int, default=S,
+                     help="Resize the content image so that its longer side has this many pixels (0 = keep, the default)")
+    opt.add_argument("--style-size", type=int, default=S,
+                     help="Resize the style image so that its longer side has this many pixels (0 = keep, the default)")
+    opt.add_argument("--style-scale", type=float, default=S,
+                     help="Resize the style image so that its longer side is this multiple of the content's "
+                          "(0 = keep, the default; not together with --style-size)")
+    opt.add_argument("--resize-filter", choices=["bilinear", "bicubic", "lanczos"], default=S,
+                     help="Filter of the three resize options, antialiased on a downscale (default: lanczos)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
     opt.add_argument("--init-method", choices=["random", "white", "content"], default=S, help="Initialization method")
     opt.add_argument("--seed", type=int, default=S, help="Random seed")
@@ -121,6 +132,12 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
     if o.preserve_color != "off":
         rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Initialization Method") + 1,
                     ("Preserve Color", o.preserve_color))
+    resized = [("Content Size", o.content_size)] if o.content_size > 0 else []
+    resized += [("Style Size", o.style_size)] if o.style_size > 0 else []
+    resized += [("Style Scale", f"{o.style_scale:g}")] if o.style_scale > 0 else []
+    if resized:
+        at = next(i for i, (label, _) in enumerate(rows) if label == "Style image loaded") + 1
+        rows[at:at] = [*resized, ("Resize Filter", o.resize_filter)]
     for label, value in rows:
         logger.info("%s: %s", label, value)
 

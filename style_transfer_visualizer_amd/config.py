@@ -5,7 +5,9 @@ so existing ``config.toml`` files and CLI invocations keep working.  The
 additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf16x3" fp32 storage, split-bf16 products),
 ``optimization.tv_w`` (weight of the total-variation regulariser, 0 = off), ``optimization.pyramid_levels`` /
 ``optimization.pyramid_steps`` (coarse-to-fine runs: levels, and optionally the steps of each, coarsest first) and
-``optimization.preserve_color`` ("off" | "match" | "luma": keep the content image's colours, ``color.py``).
+``optimization.preserve_color`` ("off" | "match" | "luma": keep the content image's colours, ``color.py``) and
+``optimization.content_size`` / ``style_size`` / ``style_scale`` / ``resize_filter`` (resize the inputs on the device before
+the run, ``resize.py``; 0 = keep the file's size).
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ from pydantic import BaseModel, Field
 from . import config_defaults as d
 from .constants import VIDEO_QUALITY_MAX, VIDEO_QUALITY_MIN
 from .logging_utils import logger
-from .type_defs import InitMethod, Precision, PreserveColor, VideoMode
+from .type_defs import InitMethod, Precision, PreserveColor, ResizeFilter, VideoMode
 
 
 class OptimizationConfig(BaseModel):
@@ -31,6 +33,10 @@ class OptimizationConfig(BaseModel):
     pyramid_levels: int = Field(d.DEFAULT_PYRAMID_LEVELS, ge=1, le=6)
     pyramid_steps: list[int] | None = d.DEFAULT_PYRAMID_STEPS
     preserve_color: PreserveColor = Field(d.DEFAULT_PRESERVE_COLOR)
+    content_size: int = Field(d.DEFAULT_CONTENT_SIZE, ge=0)
+    style_size: int = Field(d.DEFAULT_STYLE_SIZE, ge=0)
+    style_scale: float = Field(d.DEFAULT_STYLE_SCALE, ge=0)
+    resize_filter: ResizeFilter = Field(d.DEFAULT_RESIZE_FILTER)
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
     seed: int = Field(d.DEFAULT_SEED, ge=0)
@@ -126,6 +132,8 @@ _DIRECT = {
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
     "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lr": ("optimization", "lr"),
     "pyramid_levels": ("optimization", "pyramid_levels"), "preserve_color": ("optimization", "preserve_color"),
+    "content_size": ("optimization", "content_size"), "style_size": ("optimization", "style_size"),
+    "style_scale": ("optimization", "style_scale"), "resize_filter": ("optimization", "resize_filter"),
     "init_method": ("optimization", "init_method"), "seed": ("optimization", "seed"),
     "save_every": ("video", "save_every"), "fps": ("video", "fps"), "quality": ("video", "quality"),
     "metadata_title": ("video", "metadata_title"), "metadata_artist": ("video", "metadata_artist"),

@@ -9,6 +9,10 @@ DEFAULT_TV_WEIGHT = 0.0      # build-specific: weight of the total-variation reg
 DEFAULT_PYRAMID_LEVELS = 1   # build-specific: levels of a coarse-to-fine run (1 = the single-size run)
 DEFAULT_PYRAMID_STEPS = None  # build-specific: steps per level, coarsest first (None = optimization.steps split evenly)
 DEFAULT_PRESERVE_COLOR = "off"  # build-specific: keep the content image's colours ("match": style statistics, "luma": chroma swap)
+DEFAULT_CONTENT_SIZE = 0     # build-specific: longer side the content image is resized to before the run (0 = keep its size)
+DEFAULT_STYLE_SIZE = 0       # build-specific: longer side the style image is resized to (0 = keep its size)
+DEFAULT_STYLE_SCALE = 0.0    # build-specific: the style's longer side as a multiple of the content's (0 = keep its size)
+DEFAULT_RESIZE_FILTER = "lanczos"  # build-specific: "bilinear" | "bicubic" | "lanczos", antialiased on a downscale
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"
 DEFAULT_SEED = 0

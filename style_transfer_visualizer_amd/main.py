@@ -8,6 +8,11 @@ with a warning and the run proceeds like ``--no-video``.
 ``optimization.preserve_color`` (``color.py``, no counterpart in the reference) adds one stage at either end: "match"
 re-colours the style image right behind the loads, "luma" restores the content image's chrominance in the result right
 in front of the save; "off" adds nothing.
+
+``optimization.content_size`` / ``style_size`` / ``style_scale`` (``resize.py``, no counterpart in the reference) add one stage
+right behind the two loads and in front of the colour match: the loaded tensors are resized on the device by ``ops.resize``,
+in the space they are in (normalised when normalisation is on), so colour statistics, the ``luma`` swap and a coarse-to-fine
+run all see the images the run sees.  With all three at 0 the stage is not entered.
 """
 from __future__ import annotations
 
@@ -16,13 +21,29 @@ from pathlib import Path
 
 import torch
 
-from . import color, core_model, image_io, optimization, pyramid, runtime
+from . import color, core_model, image_io, ops, optimization, pyramid, runtime
+from . import resize as resize_rules
 from .logging_utils import logger
 from .type_defs import InputPaths, SaveOptions
 
 # Several images may be in flight in one process (style_transfer_batch): seeding the global generators and drawing
 # the start image from them is one step per image, as in a sequential run.
 _SETUP_LOCK = threading.Lock()
+
+
+def _resize_inputs(content_img: torch.Tensor, style_img: torch.Tensor, oc) -> tuple[torch.Tensor, torch.Tensor]:
+    """The two images at the sizes ``resize.plan_sizes`` gives (refusals first: nothing is launched for a run that cannot
+    start); an image that keeps its size is handed on as it is."""
+    content_hw, style_hw = resize_rules.plan_sizes(oc, content_img.shape[-2:], style_img.shape[-2:])
+    for name, hw, img in (("Content", content_hw, content_img), ("Style", style_hw, style_img)):
+        if hw is not None:
+            logger.info("%s image resized from %dx%d to %dx%d (%s)", name, img.shape[-1], img.shape[-2], hw[1], hw[0],
+                        oc.resize_filter)
+    if content_hw is not None:
+        content_img = ops.resize(content_img.contiguous(), content_hw, oc.resize_filter)
+    if style_hw is not None:
+        style_img = ops.resize(style_img.contiguous(), style_hw, oc.resize_filter)
+    return content_img, style_img
 
 
 def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collector=None, output_tag: str = "",
@@ -48,6 +69,9 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     normalize = config.optimization.normalize
     content_img = image_io.load_image_to_tensor(paths.content_path, device, normalize=normalize)
     style_img = image_io.load_image_to_tensor(paths.style_path, device, normalize=normalize)
+    oc = config.optimization
+    if oc.content_size > 0 or oc.style_size > 0 or oc.style_scale > 0:
+        content_img, style_img = _resize_inputs(content_img, style_img, oc)
     preserve_color = config.optimization.preserve_color
     if preserve_color == "match":               # once per run, on the full-size images: a coarse-to-fine run halves the matched style
         style_img = color.match_style_to_content(style_img, content_img)

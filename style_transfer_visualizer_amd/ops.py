@@ -10,10 +10,13 @@ float32 or bfloat16; the image / its gradient are ``[1, 3, H, W]`` float32.
 from __future__ import annotations
 
 import ctypes
+import functools
 
+import numpy as np
 import torch
 
 from . import _lib
+from . import resize as _resize
 from ._lib import ACCUM, MASK, POOL_ONLY, RELU_IN, RELU_OUT, STV_BF16, STV_BF16X3, STV_F32, W_BLOCKED  # noqa: F401
 
 
@@ -425,6 +428,67 @@ def resize2x(x: torch.Tensor, mode: int, out: torch.Tensor | None = None) -> tor
         msg = f"resize2x: out is {tuple(out.shape)} {out.dtype}, expected {shape} torch.float32"
         raise RuntimeError(msg)
     _lib.check(lib.stv_resize2x(_ptr(x), _ptr(out), C, H, W, int(mode), _stream()), "stv_resize2x")
+    return out
+
+
+@functools.lru_cache(maxsize=64)
+def _packed_axis_table(n_in: int, n_out: int, filter: str) -> tuple[np.ndarray, int]:  # noqa: A002
+    """One axis's table as a single int32 host array - ``start``, ``count``, then the bits of the fp32 weights row by row -
+    and ``K``: one upload per pass."""
+    start, count, weights = _resize.axis_table(n_in, n_out, filter)
+    return np.concatenate([start, count, weights.reshape(-1).view(np.int32)]), int(weights.shape[1])
+
+
+def _resize_pass(lib, x: torch.Tensor, y: torch.Tensor, planes: int, H: int, W: int, n_out: int, axis: int,  # noqa: PLR0913
+                 filter: str) -> None:  # noqa: A002
+    packed, K = _packed_axis_table(W if axis == 1 else H, n_out, filter)
+    table = torch.from_numpy(packed).to(x.device)
+    start, count, weights = table[:n_out], table[n_out:2 * n_out], table[2 * n_out:]
+    _lib.check(lib.stv_resize_axis(_ptr(x), _ptr(y), planes, H, W, n_out, axis, _ptr(start), _ptr(count), _ptr(weights), K,
+                                   _stream()), "stv_resize_axis")
+
+
+def resize(x: torch.Tensor, size: tuple[int, int], filter: str = "lanczos", out: torch.Tensor | None = None,  # noqa: A002
+           tmp: torch.Tensor | None = None) -> torch.Tensor:
+    """Antialiased resize of a contiguous fp32 image ``[C, H, W]`` or ``[1, C, H, W]`` on the device to ``size = (Ho, Wo)``,
+    up or down, with the ``bilinear``, ``bicubic`` or ``lanczos`` filter (``stv_resize_axis``; tables: ``resize.axis_table``).
+    Columns are filtered first, into the intermediate ``[C, H, Wo]`` (``tmp`` when given), rows second.  A pass whose axis
+    keeps its size is not launched; if both keep it, ``x`` itself is returned and ``out`` is not written.  Returns a tensor
+    of the same rank (``out`` when given: same rank, the output's shape)."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
+        msg = f"resize expects an fp32 image [C, H, W] or [1, C, H, W], got {tuple(x.shape)} {x.dtype}"
+        raise RuntimeError(msg)
+    if filter not in _resize.FILTERS:
+        msg = f"resize: unknown filter {filter!r}, expected one of {sorted(_resize.FILTERS)}"
+        raise RuntimeError(msg)
+    C, H, W = (int(v) for v in x.shape[-3:])
+    Ho, Wo = (int(v) for v in size)
+    if Ho < 1 or Wo < 1:
+        msg = f"resize: size is {(Ho, Wo)}, expected positive numbers"
+        raise RuntimeError(msg)
+    shape = (*x.shape[:-2], Ho, Wo)
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32):
+        msg = f"resize: out is {tuple(out.shape)} {out.dtype}, expected {shape} torch.float32"
+        raise RuntimeError(msg)
+    if (Ho, Wo) == (H, W):
+        return x
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    mid = x
+    if Wo != W:
+        mid = out
+        if Ho != H:
+            mid_shape = (*x.shape[:-2], H, Wo)
+            if tmp is None:
+                tmp = torch.empty(mid_shape, dtype=torch.float32, device=x.device)
+            elif tuple(tmp.shape) != mid_shape or tmp.dtype != torch.float32:
+                msg = f"resize: tmp is {tuple(tmp.shape)} {tmp.dtype}, expected {mid_shape} torch.float32"
+                raise RuntimeError(msg)
+            mid = tmp
+        _resize_pass(lib, x, mid, C, H, W, Wo, 1, filter)
+    if Ho != H:
+        _resize_pass(lib, mid, out, C, H, Wo, Ho, 0, filter)
     return out
 
 

@@ -10,6 +10,7 @@ InitMethod = Literal["content", "random", "white"]
 VideoMode = Literal["realtime", "postprocess"]
 Precision = Literal["fp32", "bf16", "bf16x3"]
 PreserveColor = Literal["off", "match", "luma"]
+ResizeFilter = Literal["bilinear", "bicubic", "lanczos"]
 LossHistory = dict[str, list[float]]
 TensorList = list[torch.Tensor]
 
