@@ -350,6 +350,23 @@ int stv_color_affine(const float* x_nchw, float* y_nchw, const float* m12, int H
 int stv_luma_transfer(const float* result, const float* content, float* out, int H, int W, const float* mean3,
                       const float* std3, void* stream);
 
+/* ---- Blended Gram targets (several style images with blend weights; no counterpart in the reference; jcjohnson's
+ *      -style_blend_weights).  Since version 110.  One launch per style layer when targets are set, none inside the step.
+ *   out[i] = (...((w[0]*G_0[i]) + w[1]*G_1[i]) + ...) + w[K-1]*G_{K-1}[i]      i < n
+ *      every product and every sum rounded to fp32 on its own, tables in ascending order, no FMA contraction: an fp32
+ *      twin reproduces every bit. ----------------------------------------------------------------------------------- */
+/* launch constants: a work item is STV_BLEND_VEC consecutive elements (16-byte loads and a 16-byte store), a pass of the
+ * capped grid covers STV_BLEND_MAX_BLOCKS * STV_BLEND_THREADS items; the n % STV_BLEND_VEC last elements are a scalar tail. */
+#define STV_BLEND_MAX_TABLES 8
+#define STV_BLEND_VEC 4
+#define STV_BLEND_THREADS 256
+#define STV_BLEND_MAX_BLOCKS 128
+/* stack: fp32 [K][n] on the device, contiguous; weights: HOST array of K floats, passed to the kernel by value;
+ * out: fp32 [n] on the device, sharing no byte with the stack.
+ * STV_ERR_ARG, before any HIP call: a null pointer, K < 1 or K > STV_BLEND_MAX_TABLES, n < 1, a weight that is negative
+ * or not finite, a stack of 2 GiB or more, `out` overlapping the stack. */
+int stv_gram_blend(const float* stack, float* out, const float* weights, int K, long long n, void* stream);
+
 /* ---- Frame / PNG export: prepare_image_for_output (image_io.py:129-152: denormalise,
  *      nan_to_num(nan=0, posinf=1, neginf=0), clamp 0..1) fused with the uint8 conversion, on the
  *      device, so only H*W*3 bytes cross to the host.  x NCHW fp32 [3][H][W] -> out HWC uint8.

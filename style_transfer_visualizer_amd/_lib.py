@@ -37,6 +37,9 @@ RESIZE_AXIS_THREADS, RESIZE_AXIS_MAX_BLOCKS, RESIZE_AXIS_VEC = 256, 1024, 4
 # pixels of one row read from all three planes; stv_color_stats always runs COLOR_STATS_PARTS workgroups (one row of nine
 # doubles each), stv_color_affine and stv_luma_transfer at most COLOR_MAX_BLOCKS, all of COLOR_THREADS threads
 COLOR_VEC, COLOR_THREADS, COLOR_STATS_PARTS, COLOR_MAX_BLOCKS = 4, 256, 256, 1024
+# launch constants of stv_gram_blend (stv.h STV_BLEND_*; csrc/blend.hip): at most BLEND_MAX_TABLES tables per launch, a work
+# item is BLEND_VEC consecutive elements, a pass of the capped grid covers BLEND_MAX_BLOCKS * BLEND_THREADS items
+BLEND_MAX_TABLES, BLEND_VEC, BLEND_THREADS, BLEND_MAX_BLOCKS = 8, 4, 256, 128
 
 _ERRORS = {1: "STV_ERR_ARG (unsupported shape / null pointer / dtype)",
            2: "STV_ERR_LAUNCH (HIP launch failed)", 3: "STV_ERR_ALLOC", 4: "STV_ERR_GRAPH"}
@@ -117,6 +120,7 @@ SIGNATURES = {
     "stv_color_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "stv_color_affine": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int, c_void_p]),
     "stv_luma_transfer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),
+    "stv_gram_blend": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int64, c_void_p]),
     "stv_image_to_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_void_p]),
     "stv_loss_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "stv_loss_combine_log": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,

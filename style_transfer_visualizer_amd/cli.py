@@ -3,8 +3,8 @@
 Options that only have meaning for presentation features outside this build (comparison grids)
 are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,bf16x3}``, ``--tv-w``,
 ``--pyramid-levels`` / ``--pyramid-steps``, ``--preserve-color {off,match,luma}``, ``--content-size`` / ``--style-size`` /
-``--style-scale`` / ``--resize-filter {bilinear,bicubic,lanczos}`` (``--content`` and ``--style`` stay exact options: argparse
-prefers an exact match to a prefix).
+``--style-scale`` / ``--resize-filter {bilinear,bicubic,lanczos}``, ``--style-also`` / ``--style-blend`` /
+``--style-layer-weights`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
 """
 from __future__ import annotations
 
@@ -13,6 +13,7 @@ import sys
 
 from . import config as stv_config
 from . import main as stv_main
+from . import style_mix
 from .config_defaults import DEFAULT_LOG_EVERY
 from .constants import VIDEO_QUALITY_MAX, VIDEO_QUALITY_MIN
 from .logging_utils import logger
@@ -29,6 +30,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
     req = p.add_argument_group("required arguments")
     req.add_argument("--content", type=str, help="Path to content image")
     req.add_argument("--style", type=str, help="Path to style image")
+    req.add_argument("--style-also", type=str, nargs="+", default=S, metavar="PATH",
+                     help="Further style images, blended with --style (at most 8 style images in all)")
 
     out = p.add_argument_group("output")
     out.add_argument("--output", type=str, default=S, help="Output directory")
@@ -59,6 +62,12 @@ def build_arg_parser() -> argparse.ArgumentParser:
                           "(0 = keep, the default; not together with --style-size)")
     opt.add_argument("--resize-filter", choices=["bilinear", "bicubic", "lanczos"], default=S,
                      help="Filter of the three resize options, antialiased on a downscale (default: lanczos)")
+    opt.add_argument("--style-blend", type=str,
+                     help="Comma-separated blend weights of the style images, --style's first (normalised to sum 1; "
+                          "default: equal weights)")
+    opt.add_argument("--style-layer-weights", type=str,
+                     help="Comma-separated weights of the style layers, paired by position with --style-layers "
+                          "(default: every layer counts 1)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
     opt.add_argument("--init-method", choices=["random", "white", "content"], default=S, help="Initialization method")
     opt.add_argument("--seed", type=int, default=S, help="Random seed")
@@ -138,6 +147,16 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
     if resized:
         at = next(i for i, (label, _) in enumerate(rows) if label == "Style image loaded") + 1
         rows[at:at] = [*resized, ("Resize Filter", o.resize_filter)]
+    mixed = [("Style images", list(paths.style_paths))] if paths.extra_style_paths else []
+    if paths.extra_style_paths or o.style_blend is not None:
+        blend = style_mix.blend_weights(o.style_blend, len(paths.style_paths))
+        mixed.append(("Style Blend Weights (normalised)", [float(b) for b in blend]))
+    if mixed:
+        at = next(i for i, (label, _) in enumerate(rows) if label == "Style image loaded") + 1
+        rows[at:at] = mixed
+    if o.style_layer_weights is not None:
+        rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Style Layers") + 1,
+                    ("Style Layer Weights", o.style_layer_weights))
     for label, value in rows:
         logger.info("%s: %s", label, value)
 
@@ -155,7 +174,8 @@ def run_from_args(args: argparse.Namespace) -> None:
             logger.info("Config %s validated successfully.", args.config)
             sys.exit(0)
     cfg = stv_config.build_config_from_cli(vars(args), base_config=base_cfg)
-    paths = InputPaths(content_path=args.content, style_path=args.style)
+    paths = InputPaths(content_path=args.content, style_path=args.style,
+                       extra_style_paths=tuple(getattr(args, "style_also", ())))
     log_parameters(paths, cfg, args)
     stv_main.style_transfer(paths, cfg)
     if args.compare_inputs or args.compare_result:

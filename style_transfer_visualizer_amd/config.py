@@ -7,7 +7,8 @@ additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf1
 ``optimization.pyramid_steps`` (coarse-to-fine runs: levels, and optionally the steps of each, coarsest first) and
 ``optimization.preserve_color`` ("off" | "match" | "luma": keep the content image's colours, ``color.py``) and
 ``optimization.content_size`` / ``style_size`` / ``style_scale`` / ``resize_filter`` (resize the inputs on the device before
-the run, ``resize.py``; 0 = keep the file's size).
+the run, ``resize.py``; 0 = keep the file's size) and ``optimization.style_blend`` / ``style_layer_weights`` (blend weights of
+several style images, a weight per style layer, ``style_mix.py``; ``None`` = not set).
 """
 from __future__ import annotations
 
@@ -37,6 +38,8 @@ class OptimizationConfig(BaseModel):
     style_size: int = Field(d.DEFAULT_STYLE_SIZE, ge=0)
     style_scale: float = Field(d.DEFAULT_STYLE_SCALE, ge=0)
     resize_filter: ResizeFilter = Field(d.DEFAULT_RESIZE_FILTER)
+    style_blend: list[float] | None = d.DEFAULT_STYLE_BLEND
+    style_layer_weights: list[float] | None = d.DEFAULT_STYLE_LAYER_WEIGHTS
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
     seed: int = Field(d.DEFAULT_SEED, ge=0)
@@ -126,6 +129,13 @@ def parse_int_list(value: str | list[int]) -> list[int]:
     return [int(v) for v in value.split(",")]
 
 
+def parse_float_list(value: str | list[float]) -> list[float]:
+    """``"0.7,0.3"`` -> ``[0.7, 0.3]`` (lists pass through)."""
+    if isinstance(value, list):
+        return value
+    return [float(v) for v in value.split(",")]
+
+
 # CLI key -> (section, attribute) for plain "present in args => overwrite" options
 _DIRECT = {
     "output": ("output", "output"), "log_every": ("output", "log_every"), "log_loss": ("output", "log_loss"),
@@ -196,6 +206,10 @@ def _apply_optimization_overrides(cfg: StyleTransferConfig, args: Mapping[str, A
         cfg.optimization.content_layers = parse_int_list(args["content_layers"])
     if args.get("pyramid_steps"):
         cfg.optimization.pyramid_steps = parse_int_list(args["pyramid_steps"])
+    if args.get("style_blend"):
+        cfg.optimization.style_blend = parse_float_list(args["style_blend"])
+    if args.get("style_layer_weights"):
+        cfg.optimization.style_layer_weights = parse_float_list(args["style_layer_weights"])
 
 
 def _apply_video_overrides(cfg: StyleTransferConfig, args: Mapping[str, Any]) -> None:

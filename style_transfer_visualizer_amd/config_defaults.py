@@ -13,6 +13,8 @@ DEFAULT_CONTENT_SIZE = 0     # build-specific: longer side the content image is 
 DEFAULT_STYLE_SIZE = 0       # build-specific: longer side the style image is resized to (0 = keep its size)
 DEFAULT_STYLE_SCALE = 0.0    # build-specific: the style's longer side as a multiple of the content's (0 = keep its size)
 DEFAULT_RESIZE_FILTER = "lanczos"  # build-specific: "bilinear" | "bicubic" | "lanczos", antialiased on a downscale
+DEFAULT_STYLE_BLEND = None   # build-specific: one blend weight per style image, --style's first (None = equal weights)
+DEFAULT_STYLE_LAYER_WEIGHTS = None  # build-specific: one weight per entry of style_layers (None = every layer counts 1)
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"
 DEFAULT_SEED = 0

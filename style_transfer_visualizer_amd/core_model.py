@@ -20,7 +20,7 @@ from urllib.parse import urlparse
 import torch
 from torch import nn
 
-from . import _lib, ops, plan, synthetic
+from . import _lib, ops, plan, style_mix, synthetic
 from .constants import GRAM_MATRIX_CLAMP_MAX
 from .logging_utils import logger
 
@@ -377,6 +377,7 @@ class _Engine:
         self.coef_buf = torch.ones(max(n_terms, 1), device=device, dtype=torch.float32)
         self._programs: dict = {}
         self._tv_heads: dict = {}        # tv_w -> (table, scale, losses) of the combine op with the extra kind-2 row
+        self._layer_heads: dict = {}     # style layer weights -> (table, scale, losses) of the combine op of a weighted step
         self.image_channels = int(s.nodes[0].cin)
         self.use_graph = s.switches.hip_graph
         # Every evaluation overwrites the shared activation buffers; an autograd backward is only
@@ -386,24 +387,29 @@ class _Engine:
 
     # -- op list pieces -------------------------------------------------------
     def _forward_with_losses(self, x: torch.Tensor, *, style_coef: float, with_seed: bool,
-                             content_coef: float | None = None) -> list:
+                             content_coef: float | None = None, layer_w: tuple | None = None) -> list:
         """Forward pass with the loss-side ops of every tap where ``Schedule._decide`` placed them: spliced in right
         behind the op that produces the tapped activation (while it is still L2 / Infinity-Cache resident), or in the
         tail - one batched Gram launch, then the content terms that follow it.  ``content_coef`` (the fused step: the
-        coefficient is known) lets a content tap form loss and gradient in one pass."""
+        coefficient is known) lets a content tap form loss and gradient in one pass.  ``layer_w`` (one weight per style tap, in
+        tap order): tap ``l`` is seeded with ``style_coef * layer_w[l]``, the product formed here in double and rounded to
+        fp32 where ``style_coef`` alone is; ``None``: every tap with ``style_coef``."""
         s = self.sched
+
+        def coef_of(tap) -> float:
+            return style_coef if layer_w is None else style_coef * layer_w[tap.order]
         if content_coef is not None:
             s.alloc_grads()          # the content term's gradient is written during the forward half
 
         def chain(tap) -> list:
             if tap.kind == "style":
                 return s.gram_ops(tap, gram_out=None, target=tap.target, loss_part=self.parts[tap.parts_off:],
-                                  sgrad=tap.sgrad if with_seed else None, coef=style_coef, coef_dev=None)
+                                  sgrad=tap.sgrad if with_seed else None, coef=coef_of(tap), coef_dev=None)
             fused = content_coef is not None and tap.grad_fused
             return [s.emit(op=plan.OP_CONTENT_LOSS, p0=tap.buf.act, p1=tap.target, q0=self.parts[tap.parts_off:],
                            q1=tap.buf.grad if fused else None, n=tap.buf.act.numel(), f0=content_coef if fused else 0.0)]
         batch = [dict(tap=tap, target=tap.target, loss_part=self.parts[tap.parts_off:],
-                      sgrad=tap.sgrad if with_seed else None, coef=style_coef, partials_ready=tap.finish_late)
+                      sgrad=tap.sgrad if with_seed else None, coef=coef_of(tap), partials_ready=tap.finish_late)
                  for tap in s.style_taps if tap.in_tail or tap.finish_late]
         tail = [s.gram_multi_op(batch)] if batch else []
         for tap in s.content_taps:
@@ -423,17 +429,35 @@ class _Engine:
             return s.forward_ops(x, after_node=after) + tail
         return s.forward_ops(x) + [op for node in s.nodes for op in after(node)] + tail
 
-    def tv_head(self, tv_w: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(table, scale, losses) of the combine op of a ``tv_w > 0`` step: the engine's rows plus one kind-2 row whose
-        scale carries the weight, and a losses vector with that term's slot at the end.  One triple per weight."""
-        head = self._tv_heads.get(tv_w)
+    def layer_head(self, layer_w: tuple) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(table, scale, losses) of the combine op of a step with style layer weights: the engine's table, a scale vector
+        whose row of style tap ``l`` is ``fp32(layer_w[l] / (C*C))`` (the weight rides in the scale, so the style score is
+        ``sum_l w_l * loss_l``), and a losses vector of its own: the engine's keeps the unweighted terms ``forward()``
+        returns.  One triple per weight tuple."""
+        head = self._layer_heads.get(layer_w)
         if head is None:
-            if len(self._tv_heads) >= 16:
-                self._tv_heads.pop(next(iter(self._tv_heads)))
+            if len(self._layer_heads) >= 16:
+                self._layer_heads.pop(next(iter(self._layer_heads)))
+            sc = [float(w) / float(tap.buf.C * tap.buf.C) for w, tap in zip(layer_w, self.sched.style_taps, strict=True)]
+            sc += [1.0 / float(tap.buf.act.numel()) for tap in self.sched.content_taps]
+            head = self._layer_heads[layer_w] = (self.table, torch.tensor(sc, dtype=torch.float32, device=self.device),
+                                                 torch.zeros_like(self.losses))
+        return head
+
+    def tv_head(self, tv_w: float, layer_w: tuple | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(table, scale, losses) of the combine op of a ``tv_w > 0`` step: the engine's rows (those of :meth:`layer_head`
+        with ``layer_w``) plus one kind-2 row whose scale carries the weight, and a losses vector with that term's slot at
+        the end.  One triple per weight (and weight tuple)."""
+        cache, key = (self._tv_heads, tv_w) if layer_w is None else (self._layer_heads, (tv_w, layer_w))
+        head = cache.get(key)
+        if head is None:
+            table, scale = (self.table, self.scale) if layer_w is None else self.layer_head(layer_w)[:2]
+            if len(cache) >= 16:
+                cache.pop(next(iter(cache)))
             row = torch.tensor([[self.tv_parts_off, _lib.TV_LOSS_PARTS, _lib.KIND_EXTRA]], dtype=torch.int32, device=self.device)
             sc = torch.tensor([tv_scale(tv_w, self.image_channels, self.H, self.W)], dtype=torch.float32, device=self.device)
-            head = self._tv_heads[tv_w] = (torch.cat([self.table, row]), torch.cat([self.scale, sc]),
-                                           torch.zeros(self.n_style + self.n_content + 1, device=self.device, dtype=torch.float32))
+            head = cache[key] = (torch.cat([table, row]), torch.cat([scale, sc]),
+                                 torch.zeros(self.n_style + self.n_content + 1, device=self.device, dtype=torch.float32))
         return head
 
     def _tv_op(self, x: torch.Tensor, *, loss: bool = False, grad: torch.Tensor | None = None, tv_w: float = 0.0):
@@ -443,12 +467,19 @@ class _Engine:
                                f0=tv_coef(tv_w, self.image_channels, self.H, self.W) if grad is not None else 0.0,
                                flags=_lib.ACCUM if grad is not None else 0)
 
-    def _combine_op(self, style_w: float, content_w: float, score_log: tuple | None = None, tv_w: float = 0.0):
+    def _combine_op(self, style_w: float, content_w: float, score_log: tuple | None = None, tv_w: float = 0.0,
+                    layer_w: tuple | None = None):
         """``score_log`` = (ring fp32 [3, capacity], device counter int32 [1][, host-visible record count int32 [1]]):
         the combine kernel also appends the three scores to the caller's history ring (stv_loss_combine_log).
-        ``tv_w`` > 0: the table with the total-variation row (:meth:`tv_head`)."""
+        ``tv_w`` > 0: the table with the total-variation row (:meth:`tv_head`); ``layer_w``: the scale rows that carry the
+        style layer weights (:meth:`layer_head`)."""
         ring, count, seq = (tuple(score_log) + (None,))[:3] if score_log is not None else (None, None, None)
-        table, scale, losses = self.tv_head(tv_w) if tv_w else (self.table, self.scale, self.losses)
+        if tv_w:
+            table, scale, losses = self.tv_head(tv_w, layer_w)
+        elif layer_w is not None:
+            table, scale, losses = self.layer_head(layer_w)
+        else:
+            table, scale, losses = self.table, self.scale, self.losses
         return self.sched.emit(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=table, p2=scale, p3=seq,
                                q0=losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
                                cin=table.shape[0], f0=style_w, f1=content_w)
@@ -551,17 +582,25 @@ class _Engine:
 
     # -- execution -------------------------------------------------------------
     def loss_and_grad(self, x: torch.Tensor, grad: torch.Tensor, style_w: float, content_w: float, *,
-                      score_log: tuple | None = None, then_step=None, tv_w: float = 0.0) -> None:
+                      score_log: tuple | None = None, then_step=None, tv_w: float = 0.0,
+                      layer_w: tuple | None = None) -> None:
         """``then_step`` (an ``optimizers.StepRequest`` for ``x``): the L-BFGS update of ``x`` from ``grad`` is the
         schedule's last op - closure and update are one launch (one hipGraph).
         ``tv_w`` > 0 adds ``tv_w * TV(x)`` to the total and its gradient to ``grad`` in two launches of ``stv_tv``: the
         loss partials at the head of the forward half (the combine op, and through ``scores[2]`` the multi-iteration
         L-BFGS op and the logging ring, need the term before the backward half), the gradient accumulated right behind
-        the first-layer dgrad, which WRITES ``grad``.  ``tv_w`` = 0: the step as it always was, under the same key."""
+        the first-layer dgrad, which WRITES ``grad``.  ``tv_w`` = 0: the step as it always was, under the same key.
+        ``layer_w`` (one weight per style tap, in tap order, not all 1.0): the same op list with ``style_w * layer_w[l]`` as
+        tap ``l``'s seed coefficient and ``layer_w[l] / (C*C)`` as its combine scale; the tuple is part of the key.
+        ``None``: the step as it always was, under the same key."""
+        if layer_w is not None and len(layer_w) != self.n_style:
+            msg = f"{len(layer_w)} style layer weights for {self.n_style} style taps"
+            raise ValueError(msg)
         self.generation += 1
         key = ("fused", x.data_ptr(), grad.data_ptr(), style_w, content_w,
                None if score_log is None else (tuple(t.data_ptr() for t in score_log), tuple(score_log[0].shape)),
-               None if then_step is None else then_step.key()) + ((("tv", tv_w),) if tv_w else ())
+               None if then_step is None else then_step.key()) + ((("tv", tv_w),) if tv_w else ()) + (
+                   (("layer_w", layer_w),) if layer_w is not None else ())
 
         def build():
             s = self.sched
@@ -578,13 +617,13 @@ class _Engine:
                     # stop flag are device state); the step's loss test reads the total the combine op wrote
                     kw.update(op=_lib.OP_LBFGS_ITER, taps=then_step.iters_per_step, p1=self.scores[2:])
                 tail.append(s.emit(**kw))
-            fwd = self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w)
+            fwd = self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w, layer_w=layer_w)
             bwd = s.backward_ops(grad, content_coef=content_w, coef_dev=None, prewritten=fused_content)
             if tv_w:
                 fwd.insert(0, self._tv_op(x, loss=True))
                 k = max(i for i, o in enumerate(bwd) if o.op == plan.OP_CONV_FIRST_DGRAD)
                 bwd.insert(k + 1, self._tv_op(x, grad=grad, tv_w=tv_w))
-            return fwd + [self._combine_op(style_w, content_w, score_log, tv_w)] + bwd + tail
+            return fwd + [self._combine_op(style_w, content_w, score_log, tv_w, layer_w)] + bwd + tail
         self._program(key, build).run(self.use_graph)
 
     def forward_losses(self, x: torch.Tensor) -> None:
@@ -647,8 +686,10 @@ class StyleContentModel(nn.Module):
     """
 
     def __init__(self, style_layers: list[int], content_layers: list[int], *,
-                 precision: str | None = None) -> None:
+                 precision: str | None = None, style_layer_weights: list[float] | None = None) -> None:
         super().__init__()
+        self._style_layers_given = [int(v) for v in style_layers]
+        self.style_layer_weights = style_layer_weights      # (refusals before the stack is built)
         vgg = initialize_vgg()
         self.vgg_blocks, self.content_ids, self.style_ids = create_feature_blocks(
             vgg, style_layers, content_layers)
@@ -659,6 +700,23 @@ class StyleContentModel(nn.Module):
         self._dtype = resolve_precision(precision)
         self._split = resolve_split(precision)       # bf16x3: fp32 storage (self._dtype), split-bf16 products
         self._engines: dict = {}
+
+    # -- style layer weights -----------------------------------------------------
+    @property
+    def style_layer_weights(self) -> tuple[float, ...] | None:
+        """One weight per entry of ``style_layers``, paired by position with the list as it was given (``None``: every
+        layer counts 1).  The style score of :meth:`loss_and_grad` is ``sum_l w_l * loss_l``; :meth:`forward` keeps
+        returning the unweighted per-layer losses.  Settable at any time; ``None`` and all-ones are the unweighted step."""
+        return self._layer_weights
+
+    @style_layer_weights.setter
+    def style_layer_weights(self, weights: list[float] | None) -> None:
+        self._layer_weights = style_mix.check_layer_weights(weights, self._style_layers_given)
+        self._tap_weights = style_mix.tap_weights(self._layer_weights, self._style_layers_given)
+
+    def style_tap_weights(self) -> tuple[float, ...] | None:
+        """The layer weights in the order of ``forward()``'s style losses (the layers sorted), ``None`` when every one is 1."""
+        return self._tap_weights
 
     # -- engine plumbing ---------------------------------------------------------
     def _layers(self) -> list[nn.Module]:
@@ -696,14 +754,32 @@ class StyleContentModel(nn.Module):
             self._engines[key] = eng
         return eng
 
-    def set_targets(self, style_img: torch.Tensor, content_img: torch.Tensor) -> None:
-        """Capture Gram targets from the style image and activations from the content image."""
+    def set_targets(self, style_img: torch.Tensor | list[torch.Tensor] | tuple[torch.Tensor, ...], content_img: torch.Tensor, *,
+                    style_blend: list[float] | None = None) -> None:
+        """Capture Gram targets from the style image and activations from the content image.
+
+        ``style_img`` may be a list or tuple of 1 to ``style_mix.MAX_STYLES`` images of any sizes: each is captured as a
+        single one is, and per style layer the target is the blend ``(...((b_0*G_0) + b_1*G_1) + ...)`` of their Gram
+        matrices, formed by one ``ops.gram_blend`` launch.  ``style_blend``: one weight per image, finite and >= 0,
+        normalised to sum 1 (``style_mix.blend_weights``; ``None``: equal weights).  One image: no blend is launched."""
+        styles = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
+        if not 1 <= len(styles) <= style_mix.MAX_STYLES:
+            msg = f"between 1 and {style_mix.MAX_STYLES} style images can be blended, got {len(styles)}"
+            raise ValueError(msg)
+        blend = style_mix.blend_weights(style_blend, len(styles))       # (refusals before the first launch)
         eng = self._engine_for(content_img)
-        if not style_img.is_cuda:
-            msg = "style image must be a GPU tensor (no CPU fallback on this path)"
-            raise RuntimeError(msg)
-        self._check_image(style_img)
-        self.style_targets = eng.capture_style(style_img)
+        for img in styles:
+            if not isinstance(img, torch.Tensor) or not img.is_cuda:
+                msg = "style image must be a GPU tensor (no CPU fallback on this path)"
+                raise RuntimeError(msg)
+            self._check_image(img)
+        if len(styles) == 1:
+            self.style_targets = eng.capture_style(styles[0])
+        else:
+            per_image = [eng.capture_style(img) for img in styles]
+            self.style_targets = [ops.gram_blend(torch.stack(tables), blend) for tables in zip(*per_image, strict=True)]
+            for tap, t in zip(eng.sched.style_taps, self.style_targets, strict=True):
+                tap.target = t
         # public form as in the reference (core_model.py:230-232): [1, C, H, W].  They are zero-copy
         # NCHW views of the engine's NHWC buffers (channels-last strides, storage dtype).
         self.content_targets = [t.permute(2, 0, 1).unsqueeze(0) for t in eng.capture_content(content_img)]
@@ -741,6 +817,7 @@ class StyleContentModel(nn.Module):
         appended to that history ring by the combine kernel itself (LossAccumulator.device_log()).
         ``tv_w`` > 0 adds the total-variation term (:func:`total_variation`) to the total (not to the two scores)
         and its gradient to ``x.grad``; :meth:`last_tv_term` returns the weighted term.
+        With :attr:`style_layer_weights` the style score is ``sum_l w_l * loss_l`` and the gradient follows.
         """
         tv_w = float(tv_w)
         if not 0.0 <= tv_w < float("inf"):
@@ -759,8 +836,8 @@ class StyleContentModel(nn.Module):
         from . import optimizers  # noqa: PLC0415
         # inside HipLBFGS.step(closure) for this very tensor: the update rides at the end of the same launch
         eng.loss_and_grad(x.detach(), grad, float(style_w), float(content_w), score_log=score_log,
-                          then_step=optimizers.claim_step(x), tv_w=tv_w)
-        self._tv_term = eng.tv_head(tv_w)[2][eng.n_style + eng.n_content] if tv_w else None
+                          then_step=optimizers.claim_step(x), tv_w=tv_w, layer_w=self._tap_weights)
+        self._tv_term = eng.tv_head(tv_w, self._tap_weights)[2][eng.n_style + eng.n_content] if tv_w else None
         x.grad = grad
         scores = eng.scores if live_scores else eng.scores.clone()
         return scores[0], scores[1], scores[2]
@@ -773,7 +850,7 @@ class StyleContentModel(nn.Module):
 
 def prepare_model_and_input(
     content_img: torch.Tensor,
-    style_img: torch.Tensor,
+    style_img: torch.Tensor | list[torch.Tensor],
     device: torch.device,
     optimization,
     *,
@@ -783,7 +860,8 @@ def prepare_model_and_input(
 
     ``precision`` (keyword-only extension): "fp32" | "bf16" activation storage, or "bf16x3"
     (fp32 storage, conv / Gram products from split bf16 operands);
-    default from ``STV_PRECISION`` or fp32.
+    default from ``STV_PRECISION`` or fp32.  ``style_img`` may be a list of style images; ``optimization.style_blend``
+    and ``optimization.style_layer_weights`` (``style_mix.py``) are read where the object has them.
     """
     from .optimizers import make_lbfgs  # noqa: PLC0415
 
@@ -791,8 +869,9 @@ def prepare_model_and_input(
         style_layers=optimization.style_layers,
         content_layers=optimization.content_layers,
         precision=precision,
+        **style_mix.option_kwargs(optimization, "style_layer_weights"),
     ).to(device)
-    model.set_targets(style_img, content_img)
+    model.set_targets(style_img, content_img, **style_mix.option_kwargs(optimization, "style_blend"))
     input_img = initialize_input(content_img, optimization.init_method)
     optimizer = make_lbfgs(
         input_img,

@@ -13,6 +13,10 @@ in front of the save; "off" adds nothing.
 right behind the two loads and in front of the colour match: the loaded tensors are resized on the device by ``ops.resize``,
 in the space they are in (normalised when normalisation is on), so colour statistics, the ``luma`` swap and a coarse-to-fine
 run all see the images the run sees.  With all three at 0 the stage is not entered.
+
+``InputPaths.extra_style_paths`` / ``optimization.style_blend`` / ``optimization.style_layer_weights`` (``style_mix.py``, no
+counterpart in the reference): every style image is loaded, resized and colour-matched on its own by the rules above, and the
+list is handed to the model, which blends the Gram targets.  With no extra style and both options unset nothing here changes.
 """
 from __future__ import annotations
 
@@ -21,7 +25,7 @@ from pathlib import Path
 
 import torch
 
-from . import color, core_model, image_io, ops, optimization, pyramid, runtime
+from . import color, core_model, image_io, ops, optimization, pyramid, runtime, style_mix
 from . import resize as resize_rules
 from .logging_utils import logger
 from .type_defs import InputPaths, SaveOptions
@@ -46,6 +50,22 @@ def _resize_inputs(content_img: torch.Tensor, style_img: torch.Tensor, oc) -> tu
     return content_img, style_img
 
 
+def _resize_extra_style(style_img: torch.Tensor, content_hw: tuple[int, int], oc) -> torch.Tensor:
+    """A further style image of a blend at the size ``resize.plan_sizes`` gives it: ``style_size`` / ``style_scale`` apply to
+    its own longer side, against the content as it was loaded (as for the first style)."""
+    _, style_hw = resize_rules.plan_sizes(oc, content_hw, style_img.shape[-2:])
+    if style_hw is None:
+        return style_img
+    logger.info("Style image resized from %dx%d to %dx%d (%s)", style_img.shape[-1], style_img.shape[-2], style_hw[1],
+                style_hw[0], oc.resize_filter)
+    return ops.resize(style_img.contiguous(), style_hw, oc.resize_filter)
+
+
+def _style_stem(paths: InputPaths) -> str:
+    """The style part of the output names: the stems of the style images joined by ``+``."""
+    return "+".join(Path(p).stem for p in (paths.style_path, *getattr(paths, "extra_style_paths", ())))
+
+
 def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collector=None, output_tag: str = "",
                    tag_png: bool = True) -> torch.Tensor:
     """Run one style transfer; returns the optimised image clamped to [0, 1].
@@ -53,7 +73,16 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     ``output_tag`` (``style_transfer_batch``): appended to the names of this run's loss CSV and loss plot - and, with
     ``tag_png``, of its PNG - so that several runs writing into one directory do not overwrite each other."""
     runtime.validate_input_paths(paths.content_path, paths.style_path)
+    extra_paths = tuple(getattr(paths, "extra_style_paths", ()))
+    for path in extra_paths:
+        runtime.validate_input_paths(paths.content_path, path)
     runtime.validate_parameters(config.video.quality)
+    style_blend = getattr(config.optimization, "style_blend", None)
+    layer_weights = getattr(config.optimization, "style_layer_weights", None)
+    if extra_paths or style_blend is not None:      # refusals before the first launch: the count, the length, the weights
+        style_mix.blend_weights(style_blend, 1 + len(extra_paths))
+    if layer_weights is not None:
+        style_mix.check_layer_weights(layer_weights, config.optimization.style_layers)
 
     if config.video.final_only:                 # reference main.py:30-33
         config.video.create_video = False
@@ -69,12 +98,18 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     normalize = config.optimization.normalize
     content_img = image_io.load_image_to_tensor(paths.content_path, device, normalize=normalize)
     style_img = image_io.load_image_to_tensor(paths.style_path, device, normalize=normalize)
+    extra_styles = [image_io.load_image_to_tensor(path, device, normalize=normalize) for path in extra_paths]
     oc = config.optimization
     if oc.content_size > 0 or oc.style_size > 0 or oc.style_scale > 0:
+        loaded_hw = tuple(int(v) for v in content_img.shape[-2:])
         content_img, style_img = _resize_inputs(content_img, style_img, oc)
+        extra_styles = [_resize_extra_style(img, loaded_hw, oc) for img in extra_styles]
     preserve_color = config.optimization.preserve_color
     if preserve_color == "match":               # once per run, on the full-size images: a coarse-to-fine run halves the matched style
         style_img = color.match_style_to_content(style_img, content_img)
+        extra_styles = [color.match_style_to_content(img, content_img) for img in extra_styles]
+    if extra_styles:                            # (one style: the tensor itself, as always)
+        style_img = [style_img, *extra_styles]
     coarse_to_fine = config.optimization.pyramid_levels > 1
     if not coarse_to_fine:
         with _SETUP_LOCK:
@@ -83,7 +118,7 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
                 content_img, style_img, device, config.optimization, precision=config.hardware.precision)
 
     output_path = runtime.setup_output_directory(config.output.output)
-    content_name, style_name = Path(paths.content_path).stem, Path(paths.style_path).stem + (output_tag if tag_png else "")
+    content_name, style_name = Path(paths.content_path).stem, _style_stem(paths) + (output_tag if tag_png else "")
     if output_tag and config.output.log_loss:
         log_path = Path(config.output.log_loss)
         config.output.log_loss = str(log_path.with_name(log_path.stem + output_tag + log_path.suffix))
@@ -131,7 +166,7 @@ def style_transfer_batch(pairs: list[InputPaths], config, *, images_per_gpu: int
     if torch.cuda.is_available():              # "cuda" in the config then means this rank's GPU
         torch.cuda.set_device(local_rank % torch.cuda.device_count())
 
-    stems = [(Path(p.content_path).stem, Path(p.style_path).stem) for p in pairs]
+    stems = [(Path(p.content_path).stem, _style_stem(p)) for p in pairs]
 
     def one(index: int, paths: InputPaths) -> torch.Tensor:
         tag = f"_{index:03d}" if len(pairs) > 1 else ""

@@ -558,6 +558,33 @@ def luma_transfer(result: torch.Tensor, content: torch.Tensor, *, mean: tuple | 
     return out
 
 
+# ---- blended Gram targets (several style images) ------------------------------------
+
+def gram_blend(stack: torch.Tensor, weights, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``out = (...((w[0]*G_0) + w[1]*G_1) + ...) + w[K-1]*G_{K-1}`` element by element (``stv_gram_blend``) for a
+    contiguous fp32 stack ``[K, ...]`` of ``K`` <= ``BLEND_MAX_TABLES`` tables, every product and every sum rounded to fp32
+    on its own.  ``weights``: ``K`` host numbers, finite and >= 0, handed over as fp32.  ``out`` has the shape of one table
+    and is not part of the stack; returns ``out`` (a new tensor by default)."""
+    lib = _lib.load()
+    if stack.dtype != torch.float32 or stack.dim() < 2:
+        msg = f"gram_blend expects an fp32 stack [K, ...], got {tuple(stack.shape)} {stack.dtype}"
+        raise RuntimeError(msg)
+    K = int(stack.shape[0])
+    values = [float(v) for v in weights]
+    if len(values) != K:
+        msg = f"gram_blend: {len(values)} weights for a stack of {K} tables"
+        raise RuntimeError(msg)
+    shape = tuple(stack.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=stack.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32:
+        msg = f"gram_blend: out is {tuple(out.shape)} {out.dtype}, expected {shape} torch.float32"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_gram_blend(_ptr(stack), _ptr(out), (ctypes.c_float * K)(*values), K, out.numel(), _stream()),
+               "stv_gram_blend")
+    return out
+
+
 class HostMailbox:
     """Pinned host memory the GPU writes while the CPU reads (``stv_host_mailbox_alloc``: mapped under the same
     pointer on the device, fine-grained coherent, zeroed).  ``tensor`` / ``array`` are views; every view keeps this

@@ -283,6 +283,11 @@ class OptimizationRunner:
         else:
             style_losses, content_losses = self.model(self.input_img)
             zero = torch.zeros((), device=self.input_img.device, dtype=self.input_img.dtype)
+            # (style layer weights, style_mix.py: forward() returns the unweighted per-layer losses, the score is weighted)
+            tap_w = getattr(self.model, "style_tap_weights", None)
+            tap_w = tap_w() if callable(tap_w) else None
+            if tap_w is not None and style_losses:
+                style_losses = [w * term for w, term in zip(tap_w, style_losses, strict=True)]
             style_score = torch.stack(style_losses).sum() if style_losses else zero
             content_score = torch.stack(content_losses).sum() if content_losses else zero
             loss = oc.style_w * style_score + oc.content_w * content_score

@@ -7,6 +7,9 @@ coarsest level starts from ``initialize_input`` and every later one from the pre
 ``OptimizationRunner`` on a copy of the config whose ``steps`` is that level's count: each step is the fused step the
 single-level run takes, and the image never visits the host between levels.
 
+Several style images (``style_mix.py``): ``style_img`` may be a list; each image is cropped and halved on its own, and each
+level's targets are blended from that level's images.
+
 Not built: frames (video / GIF) during such a run - their size would change between levels -, ratios other than two
 between levels, and row strips (``spatial.py``).
 """
@@ -22,7 +25,7 @@ from pathlib import Path
 import torch
 from torch.optim import Optimizer
 
-from . import _lib, core_model, ops, optimization, runtime
+from . import _lib, core_model, ops, optimization, runtime, style_mix
 from .constants import MIN_DIMENSION
 from .logging_utils import logger
 from .loss_logger import HEADER
@@ -129,16 +132,21 @@ def run_pyramid(  # noqa: PLR0913
     level is built; ``setup_lock``: held while that happens and while any level's model is constructed (constructing one
     draws from the process-wide CPU generator) - ``main.style_transfer`` passes both, as it seeds under its lock in a
     single-level run."""
-    levels, Hs, Ws = _validate(content_img, style_img, config, video_writer, gif_collector)
+    style_list = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
+    crops = [_validate(content_img, img, config, video_writer, gif_collector) for img in style_list]
+    levels = crops[0][0]
     oc = config.optimization
     counts = level_steps(oc.steps, levels, oc.pyramid_steps)
     H, W = (int(v) for v in content_img.shape[-2:])
     shapes = level_shapes(H, W, levels)
-    if (Hs, Ws) != tuple(style_img.shape[-2:]):
-        logger.info("Style image cropped from %dx%d to %dx%d (a multiple of %d on both sides)",
-                    style_img.shape[-1], style_img.shape[-2], Ws, Hs, 1 << (levels - 1))
-        style_img = style_img[..., :Hs, :Ws]
-    contents, styles = _halvings(content_img, levels), _halvings(style_img, levels)
+    for i, (img, (_, Hs, Ws)) in enumerate(zip(style_list, crops, strict=True)):
+        if (Hs, Ws) != tuple(img.shape[-2:]):
+            logger.info("Style image cropped from %dx%d to %dx%d (a multiple of %d on both sides)",
+                        img.shape[-1], img.shape[-2], Ws, Hs, 1 << (levels - 1))
+            style_list[i] = img[..., :Hs, :Ws]
+    contents, per_style = _halvings(content_img, levels), [_halvings(img, levels) for img in style_list]
+    # level k's style: the tensor itself for one image (as always), the list of that level's images for a blend
+    styles = per_style[0] if len(per_style) == 1 else [[chain[k] for chain in per_style] for k in range(levels)]
 
     log_path = Path(config.output.log_loss) if config.output.log_loss else None
     lock = setup_lock if setup_lock is not None else contextlib.nullcontext()
@@ -162,8 +170,9 @@ def run_pyramid(  # noqa: PLR0913
                 if k == 0 and seed is not None:
                     runtime.setup_random_seed(seed)
                 model = core_model.StyleContentModel(style_layers=oc.style_layers, content_layers=oc.content_layers,
-                                                     precision=config.hardware.precision).to(device)
-                model.set_targets(styles[k], contents[k])
+                                                     precision=config.hardware.precision,
+                                                     **style_mix.option_kwargs(oc, "style_layer_weights")).to(device)
+                model.set_targets(styles[k], contents[k], **style_mix.option_kwargs(oc, "style_blend"))
                 if k == 0:
                     input_img = core_model.initialize_input(contents[0], oc.init_method)
                 else:

@@ -27,7 +27,7 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
-from . import ops, plan
+from . import ops, plan, style_mix
 from .optimizers import HipAdam
 
 HALO_ROWS = 160
@@ -134,12 +134,23 @@ class _StripLossHead:
             self.parts2[self._content_slot:self._content_slot + n_c].copy_(self.flat[n_r:n_r + n_c])
 
 
+def _refuse_layer_weights(style_layer_weights) -> None:
+    """Style layer weights other than all ones are refused here, as ``tv_w > 0`` is (blended targets need nothing: the
+    strips take ``style_targets`` as they are)."""
+    if not style_mix.is_trivial(style_layer_weights):
+        msg = (f"style layer weights {list(style_layer_weights)} are not available on the row-strip path: its combine scales "
+               "and seed coefficients are one per kind; use weights of 1 here, or a whole image")
+        raise ValueError(msg)
+
+
 class SpatialShard:
     """This rank's share of one image: buffers, the two programs around the all-reduce, Adam state."""
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
-                 style_w: float, content_w: float, tv_w: float = 0.0) -> None:
+                 style_w: float, content_w: float, tv_w: float = 0.0,
+                 style_layer_weights: list[float] | None = None) -> None:
+        _refuse_layer_weights(style_layer_weights)
         if tv_w:
             msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
                    "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
@@ -250,7 +261,9 @@ class HaloShard:
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
-                 style_w: float, content_w: float, group=None, split: bool = False, tv_w: float = 0.0) -> None:
+                 style_w: float, content_w: float, group=None, split: bool = False, tv_w: float = 0.0,
+                 style_layer_weights: list[float] | None = None) -> None:
+        _refuse_layer_weights(style_layer_weights)
         if tv_w:
             msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
                    "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")

@@ -17,10 +17,16 @@ TensorList = list[torch.Tensor]
 
 @dataclass(slots=True)
 class InputPaths:
-    """Content and style image paths."""
+    """Content and style image paths; ``extra_style_paths``: further style images, blended with the first (``style_mix.py``)."""
 
     content_path: str
     style_path: str
+    extra_style_paths: tuple[str, ...] = ()
+
+    @property
+    def style_paths(self) -> tuple[str, ...]:
+        """Every style image, ``style_path`` first."""
+        return (self.style_path, *self.extra_style_paths)
 
 
 @dataclass(slots=True)
