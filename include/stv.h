@@ -270,6 +270,41 @@ int stv_content_grad(const void* F, const void* target, void* dF, size_t n, floa
  * dimension, C*H*W*4 >= 2 GiB, a flag other than STV_ACCUM. */
 int stv_tv(const float* x_nchw, float* loss_part, float* dx_nchw, int C, int H, int W, float coef, int flags, void* stream);
 
+/* ---- Laplacian loss of the image against the content image (Li et al., "Laplacian-steered neural style transfer", ACM MM
+ *      2017; no counterpart in the reference).  Since version 111.  For a pool size p (1, 2, 4, 8, 16 or 32):
+ *        Hp = H / p, Wp = W / p (rows and columns past Hp*p and Wp*p take no part, as in avg_pool2d);
+ *        P(x)[c,i,j] = the mean of cell (i, j) of plane c;   t = P(content), captured once;   e = P(x) - t;
+ *        r = L e,  (L e)[i,j] = sum over the EXISTING 4-neighbours n of (e[i,j] - n), inside one plane (stv_tv's stencil);
+ *        lap(x) = sum r^2 / (C*Hp*Wp);   d lap / dx[c,y,x] = 2 / (C*Hp*Wp*p*p) * (L r)[c, y/p, x/p] for y < Hp*p and x < Wp*p.
+ *      Arithmetic, fixed to the bit (every add, subtraction and product rounded to fp32 on its own, no FMA contraction):
+ *        cell mean: each of the p rows of the cell summed left to right, the p row sums summed top to bottom (the first
+ *                   element starts a sum), then * 1/p^2 (a power of two: exact);
+ *        residual:  e = mean - t, one subtraction (POOL stores the mean itself);
+ *        stencil:   s = +0, then s = s + (e - n) for the existing neighbours in the order up, down, left, right;
+ *        gradient:  g = L r with the same stencil, out = coef * g, dx = out, or dx = dx + out with STV_ACCUM. ---------------- */
+enum { STV_LAP_POOL = 0, STV_LAP_LOSS = 1, STV_LAP_GRAD = 2 };
+/* launch constants: every kernel runs workgroups of STV_LAP_THREADS.  LOSS: a workgroup owns a tile of STV_LAP_TILE_H x
+ * STV_LAP_TILE_W cells of one plane and always runs as a grid of STV_LAP_LOSS_PARTS workgroups with a stride loop over the
+ * tiles (planes, then tile rows, then tiles of a row).  GRAD: a work item is four consecutive pixels of one row, a pass of
+ * the capped grid covers STV_LAP_GRAD_MAX_BLOCKS * STV_LAP_THREADS items. */
+#define STV_LAP_THREADS 256
+#define STV_LAP_TILE_H 8
+#define STV_LAP_TILE_W 32
+#define STV_LAP_LOSS_PARTS 256
+#define STV_LAP_GRAD_MAX_BLOCKS 512
+/* x NCHW fp32 [C][H][W] (H, W always the image's); target, cells fp32 [C][Hp][Wp]; dx NCHW fp32 [C][H][W].
+ *   STV_LAP_POOL: cells = P(x).                                              needs x, cells
+ *   STV_LAP_LOSS: cells = r; loss_part = STV_LAP_LOSS_PARTS raw partial sums of r^2 (unscaled; stv_loss_combine applies
+ *                 the scale), one per workgroup, fixed order, no atomics, every entry written on every launch.
+ *                                                                            needs x, target, cells, loss_part
+ *   STV_LAP_GRAD: cells holds r (input); dx (=|+=, STV_ACCUM) coef * (L r) of the pixel's cell.  With STV_ACCUM the pixels
+ *                 outside Hp*p x Wp*p are left untouched, without it they are written +0.     needs cells, dx
+ * STV_ERR_ARG, before any HIP call: a null pointer the mode needs; C, H or W <= 0; a pool other than 1, 2, 4, 8, 16, 32;
+ * H / pool == 0 or W / pool == 0; C*H*W*4 >= 2 GiB; an unknown mode; a flag other than STV_ACCUM, or STV_ACCUM outside
+ * STV_LAP_GRAD; dx sharing a byte with cells. */
+int stv_lap(const float* x_nchw, const float* target, float* cells, float* loss_part, float* dx_nchw, int C, int H, int W,
+            int pool, float coef, int mode, int flags, void* stream);
+
 /* ---- 2x resize of the image between the levels of a coarse-to-fine run (no counterpart in the reference).  Since
  *      version 106.  Every product and every sum below is rounded to fp32 on its own (no FMA contraction), in the order
  *      written, so that an fp32 twin reproduces every output bit.
@@ -385,6 +420,7 @@ int stv_image_to_u8(const float* x_nchw, uint8_t* out_hwc, int H, int W, const f
  *  kind 2 (since version 105): a term that belongs to neither score - the total-variation term, whose weight the host
  *  folds into its scale, fp32(tv_w / (C*H*W)).  After total = style_w*style + content_w*content is formed as before,
  *  the kind-2 terms are added to it in index order, one fp32 add each; losses[k] is the weighted term.
+ *  Since version 111 the Laplacian terms are kind-2 rows too, one per pool size, scale fp32(lap_w / (C*Hp*Wp)).
  *  n_terms <= 64 (STV_ERR_ARG beyond). */
 int stv_loss_combine(const float* parts, const int32_t* table, const float* scale,
                      int n_terms, float style_w, float content_w, float* losses,
@@ -465,7 +501,8 @@ enum {
   STV_OP_CONV_FIRST_FWD = 1, STV_OP_CONV_FIRST_DGRAD, STV_OP_CONV, STV_OP_POOL_FWD,
   STV_OP_POOL_BWD, STV_OP_RELU_FWD, STV_OP_RELU_BWD, STV_OP_GRAM_PARTIAL,
   STV_OP_GRAM_FINISH, STV_OP_CONTENT_LOSS, STV_OP_CONTENT_GRAD, STV_OP_LOSS_COMBINE,
-  STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER, STV_OP_TV
+  STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER, STV_OP_TV,
+  STV_OP_LAP
 };
 /* Operands follow the direct entry points' argument order (inputs p0.., outputs q0..).
  * CONV_FIRST_FWD takes the stv_conv_first_pack buffer in p3 (p1 unused) and gram_partials, or NULL, in q1;
@@ -482,7 +519,9 @@ enum {
  * between the two.
  * LBFGS_ITER runs stv_lbfgsc_iter in the same place with the same operands, plus p1 = loss (device fp32 scalar: the
  * total score LOSS_COMBINE wrote) and taps = iters_per_step: the one program replays for every iteration of every step.
- * TV (since version 105) runs stv_tv: p0 = x, q0 = loss_part, q1 = dx, cin = C, H, W, f0 = coef, flags. */
+ * TV (since version 105) runs stv_tv: p0 = x, q0 = loss_part, q1 = dx, cin = C, H, W, f0 = coef, flags.
+ * LAP (since version 111) runs stv_lap: p0 = x, p1 = target, q0 = cells, q1 = loss_part, q2 = dx, cin = C, H, W, cout = pool,
+ * taps = mode, f0 = coef, flags. */
 typedef struct {
   int32_t op, dtype, flags, taps;
   int32_t H, W, cin, cout;

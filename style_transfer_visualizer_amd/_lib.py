@@ -18,7 +18,7 @@ RELU_IN, RELU_OUT, MASK, ACCUM, W_BLOCKED, POOL_IDX, POOL_ROUTE, POOL_ONLY = 1, 
 
 (OP_CONV_FIRST_FWD, OP_CONV_FIRST_DGRAD, OP_CONV, OP_POOL_FWD, OP_POOL_BWD, OP_RELU_FWD,
  OP_RELU_BWD, OP_GRAM_PARTIAL, OP_GRAM_FINISH, OP_CONTENT_LOSS, OP_CONTENT_GRAD,
- OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER, OP_TV) = range(1, 18)
+ OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER, OP_TV, OP_LAP) = range(1, 19)
 
 CONTENT_LOSS_PARTS = 256
 TV_LOSS_PARTS = 256       # stv.h STV_TV_LOSS_PARTS: one loss partial per workgroup of stv_tv, which is also its grid cap
@@ -26,6 +26,13 @@ TV_LOSS_PARTS = 256       # stv.h STV_TV_LOSS_PARTS: one loss partial per workgr
 # pixels of one row, a pass of the capped grid covers TV_LOSS_PARTS * TV_THREADS items
 TV_THREADS, TV_VEC = 1024, 4
 KIND_STYLE, KIND_CONTENT, KIND_EXTRA = 0, 1, 2      # third column of the combine table
+# stv_lap (stv.h STV_LAP_*; csrc/lap.hip): its modes; the pool sizes it takes; its launch constants - workgroups of LAP_THREADS,
+# the LOSS mode one tile of LAP_TILE_H x LAP_TILE_W pooled cells per workgroup on a grid of always LAP_LOSS_PARTS workgroups
+# (one loss partial each) with a stride loop over the tiles, the GRAD mode LAP_VEC consecutive pixels of a row per work item,
+# a pass of its capped grid LAP_GRAD_MAX_BLOCKS * LAP_THREADS items
+LAP_POOL, LAP_LOSS, LAP_GRAD = 0, 1, 2
+LAP_POOLS = (1, 2, 4, 8, 16, 32)
+LAP_THREADS, LAP_TILE_H, LAP_TILE_W, LAP_LOSS_PARTS, LAP_GRAD_MAX_BLOCKS, LAP_VEC = 256, 8, 32, 256, 512, 4
 RESIZE_DOWN2, RESIZE_UP2 = 0, 1                     # stv.h STV_RESIZE_*: the modes of stv_resize2x
 # launch constants of stv_resize2x (stv.h STV_RESIZE_THREADS, STV_RESIZE_MAX_BLOCKS; pixels per work item): a work item is
 # RESIZE_VEC consecutive OUTPUT pixels of one row, a pass of the capped grid covers RESIZE_MAX_BLOCKS * RESIZE_THREADS items
@@ -115,6 +122,7 @@ SIGNATURES = {
     "stv_content_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_int, c_void_p]),
     "stv_content_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_int, c_int, c_void_p]),
     "stv_tv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "stv_lap": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
     "stv_resize2x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "stv_resize_axis": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "stv_color_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -4,7 +4,7 @@ Options that only have meaning for presentation features outside this build (com
 are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,bf16x3}``, ``--tv-w``,
 ``--pyramid-levels`` / ``--pyramid-steps``, ``--preserve-color {off,match,luma}``, ``--content-size`` / ``--style-size`` /
 ``--style-scale`` / ``--resize-filter {bilinear,bicubic,lanczos}``, ``--style-also`` / ``--style-blend`` /
-``--style-layer-weights`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
+``--style-layer-weights``, ``--lap-w`` / ``--lap-pool`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
 """
 from __future__ import annotations
 
@@ -46,6 +46,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     opt.add_argument("--style-w", type=float, default=S, help="Style weight")
     opt.add_argument("--content-w", type=float, default=S, help="Content weight")
     opt.add_argument("--tv-w", type=float, default=S, help="Total-variation weight (0 = off, the default)")
+    opt.add_argument("--lap-w", type=float, default=S,
+                     help="Weight of the Laplacian loss against the content image (0 = off, the default)")
+    opt.add_argument("--lap-pool", type=str,
+                     help="Comma-separated pool sizes of the Laplacian loss, powers of two from 1 to 32 (default: 4)")
     opt.add_argument("--pyramid-levels", type=int, default=S,
                      help="Coarse-to-fine levels, each twice the size of the one before (1 = off, the default)")
     opt.add_argument("--pyramid-steps", type=str,
@@ -134,6 +138,10 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
     if o.tv_w > 0:
         rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Content Weight") + 1,
                     ("Total Variation Weight", f"{o.tv_w:g}"))
+    if o.lap_w > 0:
+        behind = "Total Variation Weight" if o.tv_w > 0 else "Content Weight"
+        at = next(i for i, (label, _) in enumerate(rows) if label == behind) + 1
+        rows[at:at] = [("Laplacian Weight", f"{o.lap_w:g}"), ("Laplacian Pool Sizes", ",".join(str(p) for p in o.lap_pools))]
     if o.pyramid_levels > 1:
         at = next(i for i, (label, _) in enumerate(rows) if label == "Steps") + 1
         rows[at:at] = [("Pyramid Levels", o.pyramid_levels),

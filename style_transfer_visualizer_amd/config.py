@@ -8,7 +8,8 @@ additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf1
 ``optimization.preserve_color`` ("off" | "match" | "luma": keep the content image's colours, ``color.py``) and
 ``optimization.content_size`` / ``style_size`` / ``style_scale`` / ``resize_filter`` (resize the inputs on the device before
 the run, ``resize.py``; 0 = keep the file's size) and ``optimization.style_blend`` / ``style_layer_weights`` (blend weights of
-several style images, a weight per style layer, ``style_mix.py``; ``None`` = not set).
+several style images, a weight per style layer, ``style_mix.py``; ``None`` = not set) and ``optimization.lap_w`` /
+``lap_pools`` (weight and pool sizes of the Laplacian loss against the content image, 0 = off).
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from collections.abc import Callable, Mapping
 from pathlib import Path
 from typing import Any
 
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, field_validator
 
 from . import config_defaults as d
 from .constants import VIDEO_QUALITY_MAX, VIDEO_QUALITY_MIN
@@ -31,6 +32,8 @@ class OptimizationConfig(BaseModel):
     style_w: float = Field(d.DEFAULT_STYLE_WEIGHT, ge=0)
     content_w: float = Field(d.DEFAULT_CONTENT_WEIGHT, ge=0)
     tv_w: float = Field(d.DEFAULT_TV_WEIGHT, ge=0)
+    lap_w: float = Field(d.DEFAULT_LAP_WEIGHT, ge=0, allow_inf_nan=False)
+    lap_pools: list[int] = Field(default_factory=lambda: list(d.DEFAULT_LAP_POOLS))
     pyramid_levels: int = Field(d.DEFAULT_PYRAMID_LEVELS, ge=1, le=6)
     pyramid_steps: list[int] | None = d.DEFAULT_PYRAMID_STEPS
     preserve_color: PreserveColor = Field(d.DEFAULT_PRESERVE_COLOR)
@@ -48,6 +51,15 @@ class OptimizationConfig(BaseModel):
     lbfgs_max_eval: int = Field(d.DEFAULT_LBFGS_MAX_EVAL, ge=1)
     style_layers: list[int] = Field(default_factory=lambda: list(d.DEFAULT_STYLE_LAYERS))
     content_layers: list[int] = Field(default_factory=lambda: list(d.DEFAULT_CONTENT_LAYERS))
+
+    @field_validator("lap_pools")
+    @classmethod
+    def _lap_pools_allowed(cls, value: list[int]) -> list[int]:
+        allowed = (1, 2, 4, 8, 16, 32)
+        if not 1 <= len(value) <= 4 or len(set(value)) != len(value) or any(v not in allowed for v in value):
+            msg = f"lap_pools takes one to four different pool sizes out of {list(allowed)}, got {value}"
+            raise ValueError(msg)
+        return value
 
 
 class VideoConfig(BaseModel):
@@ -140,7 +152,8 @@ def parse_float_list(value: str | list[float]) -> list[float]:
 _DIRECT = {
     "output": ("output", "output"), "log_every": ("output", "log_every"), "log_loss": ("output", "log_loss"),
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
-    "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lr": ("optimization", "lr"),
+    "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lap_w": ("optimization", "lap_w"),
+    "lr": ("optimization", "lr"),
     "pyramid_levels": ("optimization", "pyramid_levels"), "preserve_color": ("optimization", "preserve_color"),
     "content_size": ("optimization", "content_size"), "style_size": ("optimization", "style_size"),
     "style_scale": ("optimization", "style_scale"), "resize_filter": ("optimization", "resize_filter"),
@@ -206,6 +219,8 @@ def _apply_optimization_overrides(cfg: StyleTransferConfig, args: Mapping[str, A
         cfg.optimization.content_layers = parse_int_list(args["content_layers"])
     if args.get("pyramid_steps"):
         cfg.optimization.pyramid_steps = parse_int_list(args["pyramid_steps"])
+    if args.get("lap_pool"):
+        cfg.optimization.lap_pools = OptimizationConfig(lap_pools=parse_int_list(args["lap_pool"])).lap_pools
     if args.get("style_blend"):
         cfg.optimization.style_blend = parse_float_list(args["style_blend"])
     if args.get("style_layer_weights"):

@@ -15,6 +15,8 @@ DEFAULT_STYLE_SCALE = 0.0    # build-specific: the style's longer side as a mult
 DEFAULT_RESIZE_FILTER = "lanczos"  # build-specific: "bilinear" | "bicubic" | "lanczos", antialiased on a downscale
 DEFAULT_STYLE_BLEND = None   # build-specific: one blend weight per style image, --style's first (None = equal weights)
 DEFAULT_STYLE_LAYER_WEIGHTS = None  # build-specific: one weight per entry of style_layers (None = every layer counts 1)
+DEFAULT_LAP_WEIGHT = 0.0     # build-specific: weight of the Laplacian loss against the content image (0 = off)
+DEFAULT_LAP_POOLS = [4]      # build-specific: its pool sizes (powers of two from 1 to 32, one to four of them)
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"
 DEFAULT_SEED = 0

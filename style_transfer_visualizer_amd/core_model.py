@@ -19,6 +19,7 @@ from urllib.parse import urlparse
 
 import torch
 from torch import nn
+from torch.nn import functional as F
 
 from . import _lib, ops, plan, style_mix, synthetic
 from .constants import GRAM_MATRIX_CLAMP_MAX
@@ -148,6 +149,66 @@ def tv_scale(tv_w: float, C: int, H: int, W: int) -> float:
 def tv_coef(tv_w: float, C: int, H: int, W: int) -> float:
     """The gradient coefficient of the TV term: ``fp32(tv_w * 2 / (C*H*W))``."""
     return _fp32(float(tv_w) * 2.0 / float(C * H * W))
+
+
+# ---------------------------------------------------------------- Laplacian loss
+LAP_MAX_POOLS = 4
+
+
+def check_lap_pools(pools) -> tuple[int, ...]:
+    """The pool sizes of the Laplacian loss as a tuple: one to ``LAP_MAX_POOLS`` of them, each a power of two from 1 to 32,
+    no duplicates (an empty sequence or ``None``: no pools, the term is not available)."""
+    if pools is None:
+        return ()
+    out = tuple(pools)
+    if any(isinstance(v, bool) or not isinstance(v, int) or v not in _lib.LAP_POOLS for v in out):
+        msg = f"lap_pools must be powers of two from 1 to 32 (one of {list(_lib.LAP_POOLS)}), got {list(out)}"
+        raise ValueError(msg)
+    if len(out) > LAP_MAX_POOLS or len(set(out)) != len(out):
+        msg = f"lap_pools takes one to {LAP_MAX_POOLS} different pool sizes, got {list(out)}"
+        raise ValueError(msg)
+    return out
+
+
+def check_lap_fits(pools, H: int, W: int, where: str = "") -> None:
+    """Every pool needs a pooled grid of at least 2 x 2 cells at the image size, or the Laplacian has nothing to difference."""
+    for p in pools:
+        if min(H, W) // p < 2:
+            msg = (f"lap_pools: pool size {p} leaves {H // p} x {W // p} cells of a {H} x {W} image{where}; "
+                   "at least 2 x 2 are needed (use a smaller pool size or a larger image)")
+            raise ValueError(msg)
+
+
+def laplacian_loss(x: torch.Tensor, content: torch.Tensor, pool: int) -> torch.Tensor:
+    """Laplacian loss of an image against the content image (``[1, C, H, W]`` or ``[C, H, W]``, same shape), differentiable, on
+    any device (Li et al., "Laplacian-steered neural style transfer", 2017):
+
+        e = avg_pool(x, pool) - avg_pool(content, pool);   r = L e;   lap = sum r^2 / (C * (H//pool) * (W//pool))
+
+    with ``L`` the ``[[0,-1,0],[-1,4,-1],[0,-1,0]]`` filter per channel under replicate padding - the sum over the existing
+    4-neighbours ``n`` of ``(e - n)``.  The fused step forms ``lap_w * sum_p lap_p`` and its gradient in the ``stv_lap`` kernel
+    (``StyleContentModel(..., lap_pools=).loss_and_grad(..., lap_w=)``); this is the same definition as torch ops."""
+    if x.shape != content.shape or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
+        msg = (f"laplacian_loss expects two images of one shape [1, C, H, W] or [C, H, W], got {tuple(x.shape)} "
+               f"and {tuple(content.shape)}")
+        raise ValueError(msg)
+    (pool,) = check_lap_pools((pool,))
+    C = int(x.shape[-3])
+    a, b = (t.reshape(1, C, t.shape[-2], t.shape[-1]) for t in (x, content))
+    e = F.avg_pool2d(a, pool) - F.avg_pool2d(b, pool)
+    kernel = torch.tensor([[0.0, -1.0, 0.0], [-1.0, 4.0, -1.0], [0.0, -1.0, 0.0]], dtype=e.dtype, device=e.device)
+    r = F.conv2d(F.pad(e, (1, 1, 1, 1), mode="replicate"), kernel.expand(C, 1, 3, 3), groups=C)
+    return r.square().sum() / r.numel()
+
+
+def lap_scale(lap_w: float, C: int, Hp: int, Wp: int) -> float:
+    """The combine-table scale of one pool's Laplacian term: ``fp32(lap_w / (C*Hp*Wp))`` - the weight rides in the scale."""
+    return _fp32(float(lap_w) / float(C * Hp * Wp))
+
+
+def lap_coef(lap_w: float, C: int, Hp: int, Wp: int, pool: int) -> float:
+    """The gradient coefficient of one pool's Laplacian term: ``fp32(lap_w * 2 / (C*Hp*Wp*pool*pool))``."""
+    return _fp32(float(lap_w) * 2.0 / float(C * Hp * Wp * pool * pool))
 
 
 # ------------------------------------------------------------------- initialisation
@@ -343,8 +404,10 @@ class _Engine:
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  H: int, W: int, dtype: torch.dtype, device: torch.device, *, split: bool = False,
-                 assume_device: bool = False) -> None:
-        """``assume_device``: as for ``plan.Schedule`` - the step a GPU engine builds, on host tensors, to be inspected."""
+                 assume_device: bool = False, lap_pools: tuple = ()) -> None:
+        """``assume_device``: as for ``plan.Schedule`` - the step a GPU engine builds, on host tensors, to be inspected.
+        ``lap_pools``: the pool sizes of the Laplacian loss; the engine then owns, per pool, a target, a residual scratch and
+        ``LAP_LOSS_PARTS`` loss partials."""
         self.layers, self.style_at, self.content_at = layers, style_at, content_at
         self.H, self.W, self.dtype, self.device = H, W, dtype, device
         self.split = split
@@ -369,7 +432,10 @@ class _Engine:
             scale.append(1.0 / float(tap.buf.act.numel()))
         # (the partial sums of the total-variation term sit behind every tap's; only a tv_w > 0 step reads or writes them)
         self.tv_parts_off = off
-        self.parts = torch.zeros(off + _lib.TV_LOSS_PARTS, device=device, dtype=torch.float32)
+        # (and those of the Laplacian terms, one block per pool, behind them: an engine without pools allocates none)
+        self.lap_pools = check_lap_pools(lap_pools)
+        self.lap_parts_off = off + _lib.TV_LOSS_PARTS
+        self.parts = torch.zeros(self.lap_parts_off + len(self.lap_pools) * _lib.LAP_LOSS_PARTS, device=device, dtype=torch.float32)
         self.table = torch.tensor(rows, dtype=torch.int32, device=device).reshape(-1, 3)
         self.scale = torch.tensor(scale, dtype=torch.float32, device=device)
         self.losses = torch.zeros(max(n_terms, 1), device=device, dtype=torch.float32)
@@ -378,7 +444,12 @@ class _Engine:
         self._programs: dict = {}
         self._tv_heads: dict = {}        # tv_w -> (table, scale, losses) of the combine op with the extra kind-2 row
         self._layer_heads: dict = {}     # style layer weights -> (table, scale, losses) of the combine op of a weighted step
+        self._lap_heads: dict = {}       # (tv_w, lap_w, layer weights) -> (table, scale, losses) with the Laplacian rows
         self.image_channels = int(s.nodes[0].cin)
+        check_lap_fits(self.lap_pools, H, W)
+        cells = [(self.image_channels, H // p, W // p) for p in self.lap_pools]
+        self.lap_targets: list[torch.Tensor | None] = [None] * len(cells)
+        self.lap_resid = [torch.zeros(shape, device=device, dtype=torch.float32) for shape in cells]
         self.use_graph = s.switches.hip_graph
         # Every evaluation overwrites the shared activation buffers; an autograd backward is only
         # valid against the forward that filled them last.  `generation` counts evaluations.
@@ -467,14 +538,53 @@ class _Engine:
                                f0=tv_coef(tv_w, self.image_channels, self.H, self.W) if grad is not None else 0.0,
                                flags=_lib.ACCUM if grad is not None else 0)
 
+    def lap_head(self, tv_w: float, lap_w: float, layer_w: tuple | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(table, scale, losses) of the combine op of a ``lap_w > 0`` step: the rows of the same step without the term
+        (:meth:`tv_head` with ``tv_w``, else :meth:`layer_head` with ``layer_w``, else the engine's), then one kind-2 row
+        per pool in the order of ``lap_pools``, each scale carrying the weight, and a losses vector with those terms' slots
+        at the end.  One triple per (tv_w, lap_w, layer_w)."""
+        key = (tv_w, lap_w, layer_w)
+        head = self._lap_heads.get(key)
+        if head is None:
+            if tv_w:
+                table, scale = self.tv_head(tv_w, layer_w)[:2]
+            else:
+                table, scale = (self.table, self.scale) if layer_w is None else self.layer_head(layer_w)[:2]
+            if len(self._lap_heads) >= 16:
+                self._lap_heads.pop(next(iter(self._lap_heads)))
+            rows = [[self.lap_parts_off + k * _lib.LAP_LOSS_PARTS, _lib.LAP_LOSS_PARTS, _lib.KIND_EXTRA]
+                    for k in range(len(self.lap_pools))]
+            sc = [lap_scale(lap_w, *r.shape) for r in self.lap_resid]
+            head = self._lap_heads[key] = (
+                torch.cat([table, torch.tensor(rows, dtype=torch.int32, device=self.device)]),
+                torch.cat([scale, torch.tensor(sc, dtype=torch.float32, device=self.device)]),
+                torch.zeros(table.shape[0] + len(rows), device=self.device, dtype=torch.float32))
+        return head
+
+    def _lap_ops(self, x: torch.Tensor, *, grad: torch.Tensor | None = None, lap_w: float = 0.0) -> list:
+        """The Laplacian ops on the image, one per pool: the LOSS form (residual and loss partials), or with ``grad`` the
+        GRAD form, ``grad += coef * (L r)`` from the residual the LOSS form left."""
+        out = []
+        for k, (p, resid) in enumerate(zip(self.lap_pools, self.lap_resid, strict=True)):
+            common = dict(op=_lib.OP_LAP, q0=resid, cin=self.image_channels, H=self.H, W=self.W, cout=p)
+            if grad is None:
+                out.append(self.sched.emit(p0=x, p1=self.lap_targets[k], q1=self.parts[self.lap_parts_off + k * _lib.LAP_LOSS_PARTS:],
+                                           taps=_lib.LAP_LOSS, **common))
+            else:
+                out.append(self.sched.emit(q2=grad, taps=_lib.LAP_GRAD, flags=_lib.ACCUM,
+                                           f0=lap_coef(lap_w, *resid.shape, p), **common))
+        return out
+
     def _combine_op(self, style_w: float, content_w: float, score_log: tuple | None = None, tv_w: float = 0.0,
-                    layer_w: tuple | None = None):
+                    layer_w: tuple | None = None, lap_w: float = 0.0):
         """``score_log`` = (ring fp32 [3, capacity], device counter int32 [1][, host-visible record count int32 [1]]):
         the combine kernel also appends the three scores to the caller's history ring (stv_loss_combine_log).
         ``tv_w`` > 0: the table with the total-variation row (:meth:`tv_head`); ``layer_w``: the scale rows that carry the
-        style layer weights (:meth:`layer_head`)."""
+        style layer weights (:meth:`layer_head`); ``lap_w`` > 0: the table with the Laplacian rows (:meth:`lap_head`)."""
         ring, count, seq = (tuple(score_log) + (None,))[:3] if score_log is not None else (None, None, None)
-        if tv_w:
+        if lap_w:
+            table, scale, losses = self.lap_head(tv_w, lap_w, layer_w)
+        elif tv_w:
             table, scale, losses = self.tv_head(tv_w, layer_w)
         elif layer_w is not None:
             table, scale, losses = self.layer_head(layer_w)
@@ -513,6 +623,28 @@ class _Engine:
         for tap, t in zip(self.sched.content_taps, targets, strict=True):
             tap.target = t
         return targets
+
+    def capture_lap(self, content_img: torch.Tensor) -> list[torch.Tensor]:
+        """The pooled content image per pool size (one POOL launch each): the Laplacian loss's targets."""
+        x = content_img.detach().contiguous().float()
+        targets = [torch.empty_like(r) for r in self.lap_resid]
+        for p, t in zip(self.lap_pools, targets, strict=True):
+            ops.lap_pool(x, t, p)
+        self.bind_lap_targets(targets)
+        return targets
+
+    def bind_lap_targets(self, targets: list[torch.Tensor] | None) -> None:
+        """Re-point the Laplacian ops at the model's pooled targets (they may have been replaced)."""
+        if targets is None or len(targets) != len(self.lap_pools):
+            msg = "Laplacian targets do not match the model's lap_pools: call set_targets() first"
+            raise RuntimeError(msg)
+        changed = False
+        for k, (t, r) in enumerate(zip(targets, self.lap_resid, strict=True)):
+            t = self._as_target(t, tuple(r.shape), torch.float32)
+            changed |= self.lap_targets[k] is None or self.lap_targets[k].data_ptr() != t.data_ptr()
+            self.lap_targets[k] = t
+        if changed:
+            self._programs.clear()
 
     def capture_style(self, style_img: torch.Tensor) -> list[torch.Tensor]:
         self.generation += 1
@@ -583,7 +715,7 @@ class _Engine:
     # -- execution -------------------------------------------------------------
     def loss_and_grad(self, x: torch.Tensor, grad: torch.Tensor, style_w: float, content_w: float, *,
                       score_log: tuple | None = None, then_step=None, tv_w: float = 0.0,
-                      layer_w: tuple | None = None) -> None:
+                      layer_w: tuple | None = None, lap_w: float = 0.0) -> None:
         """``then_step`` (an ``optimizers.StepRequest`` for ``x``): the L-BFGS update of ``x`` from ``grad`` is the
         schedule's last op - closure and update are one launch (one hipGraph).
         ``tv_w`` > 0 adds ``tv_w * TV(x)`` to the total and its gradient to ``grad`` in two launches of ``stv_tv``: the
@@ -592,15 +724,25 @@ class _Engine:
         the first-layer dgrad, which WRITES ``grad``.  ``tv_w`` = 0: the step as it always was, under the same key.
         ``layer_w`` (one weight per style tap, in tap order, not all 1.0): the same op list with ``style_w * layer_w[l]`` as
         tap ``l``'s seed coefficient and ``layer_w[l] / (C*C)`` as its combine scale; the tuple is part of the key.
-        ``None``: the step as it always was, under the same key."""
+        ``None``: the step as it always was, under the same key.
+        ``lap_w`` > 0 (an engine with ``lap_pools``) adds ``lap_w * sum_p lap_p(x)`` and its gradient in two launches of
+        ``stv_lap`` per pool: the LOSS forms at the head of the forward half behind TV's, the GRAD forms behind the
+        first-layer dgrad and TV's accumulate op, in front of the L-BFGS op.  ``lap_w`` = 0: same ops, same key."""
         if layer_w is not None and len(layer_w) != self.n_style:
             msg = f"{len(layer_w)} style layer weights for {self.n_style} style taps"
             raise ValueError(msg)
+        if lap_w and not self.lap_pools:
+            msg = f"lap_w = {lap_w:g} on an engine without lap_pools: the Laplacian term would be dropped"
+            raise ValueError(msg)
+        if lap_w and any(t is None for t in self.lap_targets):
+            msg = "Laplacian targets must be set before computing losses."
+            raise RuntimeError(msg)
         self.generation += 1
         key = ("fused", x.data_ptr(), grad.data_ptr(), style_w, content_w,
                None if score_log is None else (tuple(t.data_ptr() for t in score_log), tuple(score_log[0].shape)),
                None if then_step is None else then_step.key()) + ((("tv", tv_w),) if tv_w else ()) + (
-                   (("layer_w", layer_w),) if layer_w is not None else ())
+                   (("layer_w", layer_w),) if layer_w is not None else ()) + (
+                   (("lap", lap_w, self.lap_pools),) if lap_w else ())
 
         def build():
             s = self.sched
@@ -623,7 +765,12 @@ class _Engine:
                 fwd.insert(0, self._tv_op(x, loss=True))
                 k = max(i for i, o in enumerate(bwd) if o.op == plan.OP_CONV_FIRST_DGRAD)
                 bwd.insert(k + 1, self._tv_op(x, grad=grad, tv_w=tv_w))
-            return fwd + [self._combine_op(style_w, content_w, score_log, tv_w, layer_w)] + bwd + tail
+            if lap_w:
+                at = 1 if tv_w else 0
+                fwd[at:at] = self._lap_ops(x)
+                k = max(i for i, o in enumerate(bwd) if o.op == plan.OP_CONV_FIRST_DGRAD) + (2 if tv_w else 1)
+                bwd[k:k] = self._lap_ops(x, grad=grad, lap_w=lap_w)
+            return fwd + [self._combine_op(style_w, content_w, score_log, tv_w, layer_w, lap_w)] + bwd + tail
         self._program(key, build).run(self.use_graph)
 
     def forward_losses(self, x: torch.Tensor) -> None:
@@ -686,8 +833,11 @@ class StyleContentModel(nn.Module):
     """
 
     def __init__(self, style_layers: list[int], content_layers: list[int], *,
-                 precision: str | None = None, style_layer_weights: list[float] | None = None) -> None:
+                 precision: str | None = None, style_layer_weights: list[float] | None = None,
+                 lap_pools: tuple | list = ()) -> None:
         super().__init__()
+        self.lap_pools = check_lap_pools(lap_pools)     # pool sizes of the Laplacian loss; empty: the term is not available
+        self.lap_targets: list[torch.Tensor] | None = None
         self._style_layers_given = [int(v) for v in style_layers]
         self.style_layer_weights = style_layer_weights      # (refusals before the stack is built)
         vgg = initialize_vgg()
@@ -750,7 +900,8 @@ class StyleContentModel(nn.Module):
         key = (H, W, x.device.index)
         eng = self._engines.get(key)
         if eng is None:
-            eng = _Engine(self._layers(), self._style_at, self._content_at, H, W, self._dtype, x.device, split=self._split)
+            eng = _Engine(self._layers(), self._style_at, self._content_at, H, W, self._dtype, x.device, split=self._split,
+                          **({"lap_pools": self.lap_pools} if self.lap_pools else {}))
             self._engines[key] = eng
         return eng
 
@@ -767,6 +918,8 @@ class StyleContentModel(nn.Module):
             msg = f"between 1 and {style_mix.MAX_STYLES} style images can be blended, got {len(styles)}"
             raise ValueError(msg)
         blend = style_mix.blend_weights(style_blend, len(styles))       # (refusals before the first launch)
+        if self.lap_pools and isinstance(content_img, torch.Tensor) and content_img.dim() >= 2:
+            check_lap_fits(self.lap_pools, int(content_img.shape[-2]), int(content_img.shape[-1]))
         eng = self._engine_for(content_img)
         for img in styles:
             if not isinstance(img, torch.Tensor) or not img.is_cuda:
@@ -783,6 +936,8 @@ class StyleContentModel(nn.Module):
         # public form as in the reference (core_model.py:230-232): [1, C, H, W].  They are zero-copy
         # NCHW views of the engine's NHWC buffers (channels-last strides, storage dtype).
         self.content_targets = [t.permute(2, 0, 1).unsqueeze(0) for t in eng.capture_content(content_img)]
+        # the Laplacian loss's targets: the content image box-pooled, one [C, H//p, W//p] fp32 table per pool size
+        self.lap_targets = eng.capture_lap(content_img) if self.lap_pools else None
 
     def _require_targets(self) -> None:
         # same order and texts as reference core_model.py:255-258, 287-290
@@ -804,9 +959,9 @@ class StyleContentModel(nn.Module):
         return style, content
 
     def loss_and_grad(self, x: torch.Tensor, style_w: float, content_w: float, *, live_scores: bool = False,
-                      score_log: tuple | None = None, tv_w: float = 0.0,
+                      score_log: tuple | None = None, tv_w: float = 0.0, lap_w: float = 0.0,
                       ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """Fused step: writes d(style_w*S + content_w*C + tv_w*TV)/dx into ``x.grad``.
+        """Fused step: writes d(style_w*S + content_w*C + tv_w*TV + lap_w*sum_p lap_p)/dx into ``x.grad``.
 
         Equivalent to reference optimization.py:292-313 (forward, weighted sum,
         ``loss.backward()``) in one command-buffer launch with no host sync.
@@ -818,14 +973,26 @@ class StyleContentModel(nn.Module):
         ``tv_w`` > 0 adds the total-variation term (:func:`total_variation`) to the total (not to the two scores)
         and its gradient to ``x.grad``; :meth:`last_tv_term` returns the weighted term.
         With :attr:`style_layer_weights` the style score is ``sum_l w_l * loss_l`` and the gradient follows.
+        ``lap_w`` > 0 (a model built with ``lap_pools``) adds the Laplacian terms (:func:`laplacian_loss` against the content
+        image, one per pool size) to the total and their gradient to ``x.grad``; :meth:`last_lap_terms` returns them.
         """
         tv_w = float(tv_w)
         if not 0.0 <= tv_w < float("inf"):
             msg = f"tv_w must be a finite weight >= 0, got {tv_w}"
             raise ValueError(msg)
+        lap_w = float(lap_w)
+        if not 0.0 <= lap_w < float("inf"):
+            msg = f"lap_w must be a finite weight >= 0, got {lap_w}"
+            raise ValueError(msg)
+        if lap_w and not self.lap_pools:
+            msg = (f"lap_w = {lap_w:g}, but the model was built without lap_pools: the Laplacian term would be dropped "
+                   "(StyleContentModel(..., lap_pools=[4]))")
+            raise ValueError(msg)
         self._require_targets()
         eng = self._engine_for(x)
         eng.bind_targets(self.style_targets, self.content_targets)
+        if lap_w:
+            eng.bind_lap_targets(self.lap_targets)
         if x.dtype != torch.float32 or not x.is_contiguous():
             msg = "loss_and_grad needs a contiguous float32 image"
             raise RuntimeError(msg)
@@ -836,8 +1003,16 @@ class StyleContentModel(nn.Module):
         from . import optimizers  # noqa: PLC0415
         # inside HipLBFGS.step(closure) for this very tensor: the update rides at the end of the same launch
         eng.loss_and_grad(x.detach(), grad, float(style_w), float(content_w), score_log=score_log,
-                          then_step=optimizers.claim_step(x), tv_w=tv_w, layer_w=self._tap_weights)
-        self._tv_term = eng.tv_head(tv_w, self._tap_weights)[2][eng.n_style + eng.n_content] if tv_w else None
+                          then_step=optimizers.claim_step(x), tv_w=tv_w, layer_w=self._tap_weights,
+                          **({"lap_w": lap_w} if lap_w else {}))
+        n_terms = eng.n_style + eng.n_content
+        if lap_w:
+            losses = eng.lap_head(tv_w, lap_w, self._tap_weights)[2]
+            self._tv_term = losses[n_terms] if tv_w else None
+            self._lap_terms = losses[n_terms + (1 if tv_w else 0):]
+        else:
+            self._tv_term = eng.tv_head(tv_w, self._tap_weights)[2][n_terms] if tv_w else None
+            self._lap_terms = None
         x.grad = grad
         scores = eng.scores if live_scores else eng.scores.clone()
         return scores[0], scores[1], scores[2]
@@ -846,6 +1021,20 @@ class StyleContentModel(nn.Module):
         """``tv_w * TV(x)`` of the last ``loss_and_grad`` as a 0-d device view (valid until the next evaluation with
         that weight), or ``None`` when that evaluation ran with ``tv_w == 0``."""
         return getattr(self, "_tv_term", None)
+
+    def last_lap_terms(self) -> torch.Tensor | None:
+        """The weighted Laplacian terms ``lap_w * lap_p(x)`` of the last ``loss_and_grad``, one per pool size in the order of
+        ``lap_pools``, as a 1-d device view (valid until the next evaluation with those weights), or ``None`` when that
+        evaluation ran with ``lap_w == 0``."""
+        return getattr(self, "_lap_terms", None)
+
+
+def lap_option_kwargs(optimization) -> dict:
+    """``{"lap_pools": [...]}`` when ``optimization.lap_w`` > 0, else no keyword at all: a run without the term builds the
+    model exactly as before."""
+    if float(getattr(optimization, "lap_w", 0.0) or 0.0) > 0:
+        return {"lap_pools": list(getattr(optimization, "lap_pools", None) or [])}
+    return {}
 
 
 def prepare_model_and_input(
@@ -861,7 +1050,8 @@ def prepare_model_and_input(
     ``precision`` (keyword-only extension): "fp32" | "bf16" activation storage, or "bf16x3"
     (fp32 storage, conv / Gram products from split bf16 operands);
     default from ``STV_PRECISION`` or fp32.  ``style_img`` may be a list of style images; ``optimization.style_blend``
-    and ``optimization.style_layer_weights`` (``style_mix.py``) are read where the object has them.
+    and ``optimization.style_layer_weights`` (``style_mix.py``) are read where the object has them; ``optimization.lap_pools``
+    is handed to the model only when ``optimization.lap_w`` > 0.
     """
     from .optimizers import make_lbfgs  # noqa: PLC0415
 
@@ -870,6 +1060,7 @@ def prepare_model_and_input(
         content_layers=optimization.content_layers,
         precision=precision,
         **style_mix.option_kwargs(optimization, "style_layer_weights"),
+        **lap_option_kwargs(optimization),
     ).to(device)
     model.set_targets(style_img, content_img, **style_mix.option_kwargs(optimization, "style_blend"))
     input_img = initialize_input(content_img, optimization.init_method)

@@ -81,6 +81,9 @@ int run_op(const stv_op_t& o, void* st) {
     case STV_OP_TV:   // p0 = x; q0 = loss_part, q1 = dx (either may be unset); cin = C; f0 = coef
       return stv_tv(static_cast<const float*>(o.p0), static_cast<float*>(o.q0), static_cast<float*>(o.q1), o.cin, o.H, o.W,
                     o.f0, o.flags, st);
+    case STV_OP_LAP:  // p0 = x, p1 = target; q0 = cells, q1 = loss_part, q2 = dx; cin = C; cout = pool; taps = mode; f0 = coef
+      return stv_lap(static_cast<const float*>(o.p0), static_cast<const float*>(o.p1), static_cast<float*>(o.q0),
+                     static_cast<float*>(o.q1), static_cast<float*>(o.q2), o.cin, o.H, o.W, o.cout, o.f0, o.taps, o.flags, st);
     case STV_OP_MEMSET:
       if (hipMemsetAsync(o.q0, 0, (size_t)o.n, static_cast<hipStream_t>(st)) != hipSuccess)
         return STV_ERR_LAUNCH;
@@ -119,7 +122,7 @@ int run_all(stv_program* p, void* st) {
 
 }  // namespace
 
-extern "C" int stv_version(void) { return 110; }
+extern "C" int stv_version(void) { return 111; }
 
 extern "C" int stv_program_create(const stv_op_t* ops, int n_ops, stv_program** out) {
   if (!ops || n_ops <= 0 || !out) return STV_ERR_ARG;

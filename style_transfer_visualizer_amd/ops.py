@@ -585,6 +585,34 @@ def gram_blend(stack: torch.Tensor, weights, out: torch.Tensor | None = None) ->
     return out
 
 
+def _lap(x, target, cells, loss_part, dx, shape, pool: int, coef: float, mode: int, flags: int) -> None:
+    lib = _lib.load()
+    C, H, W = (int(v) for v in shape)
+    _lib.check(lib.stv_lap(_ptr(x), _ptr(target), _ptr(cells), _ptr(loss_part), _ptr(dx), C, H, W, int(pool), coef, mode, flags,
+                           _stream()), "stv_lap")
+
+
+def lap_pool(x: torch.Tensor | None, out: torch.Tensor | None, pool: int, *, shape: tuple | None = None) -> None:
+    """Cell means of the NCHW fp32 image ``x`` (``stv_lap``, mode POOL): ``out[C, H//pool, W//pool]`` receives the
+    ``pool x pool`` box means (the Laplacian loss's target when ``x`` is the content image).  ``shape`` = the image's
+    (C, H, W), default ``x.shape[-3:]``."""
+    _lap(x, None, out, None, None, shape if shape is not None else x.shape[-3:], pool, 0.0, _lib.LAP_POOL, 0)
+
+
+def lap_loss(x: torch.Tensor | None, target: torch.Tensor | None, resid: torch.Tensor | None, loss_part: torch.Tensor | None,
+             pool: int, *, shape: tuple | None = None, flags: int = 0) -> None:
+    """Laplacian loss of ``x`` against the pooled ``target`` (``stv_lap``, mode LOSS): ``resid[C, H//pool, W//pool]`` receives
+    ``r = L (P(x) - target)``, ``loss_part`` ``LAP_LOSS_PARTS`` raw partial sums of ``r**2``."""
+    _lap(x, target, resid, loss_part, None, shape if shape is not None else x.shape[-3:], pool, 0.0, _lib.LAP_LOSS, flags)
+
+
+def lap_grad(resid: torch.Tensor | None, dx: torch.Tensor | None, pool: int, *, coef: float = 0.0, flags: int = 0,
+             shape: tuple | None = None) -> None:
+    """Gradient of the Laplacian loss from its residual (``stv_lap``, mode GRAD): ``dx`` (written, or accumulated onto with
+    ``ACCUM``) ``coef * (L resid)`` of each pixel's cell.  ``shape`` = the image's (C, H, W), default ``dx.shape[-3:]``."""
+    _lap(None, None, resid, None, dx, shape if shape is not None else dx.shape[-3:], pool, coef, _lib.LAP_GRAD, flags)
+
+
 class HostMailbox:
     """Pinned host memory the GPU writes while the CPU reads (``stv_host_mailbox_alloc``: mapped under the same
     pointer on the device, fine-grained coherent, zeroed).  ``tensor`` / ``array`` are views; every view keeps this

@@ -278,9 +278,14 @@ class OptimizationRunner:
         oc = self.config.optimization
         self.optimizer.zero_grad()
         tv_w = float(getattr(oc, "tv_w", 0.0))
+        lap_w = float(getattr(oc, "lap_w", 0.0))
         if self._fused:
-            style_score, content_score, loss = self._fused_eval(oc.style_w, oc.content_w, tv_w)
+            style_score, content_score, loss = self._fused_eval(oc.style_w, oc.content_w, tv_w, lap_w)
         else:
+            if lap_w > 0:
+                msg = (f"optimization.lap_w = {lap_w:g}, but the model has no fused loss_and_grad(): this path has no content "
+                       "image to form the Laplacian term against, and the term would be dropped")
+                raise ValueError(msg)
             style_losses, content_losses = self.model(self.input_img)
             zero = torch.zeros((), device=self.input_img.device, dtype=self.input_img.dtype)
             # (style layer weights, style_mix.py: forward() returns the unweighted per-layer losses, the score is weighted)
@@ -297,10 +302,12 @@ class OptimizationRunner:
             self._check_finite(style_score, content_score, loss, step_idx)
         return StepTensors(step=step_idx, style_score=style_score, content_score=content_score, total_loss=loss)
 
-    def _fused_eval(self, style_w: float, content_w: float, tv_w: float = 0.0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def _fused_eval(self, style_w: float, content_w: float, tv_w: float = 0.0,
+                    lap_w: float = 0.0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """The model's fused step; its scores are recorded before the next evaluation, so views of the
         live score buffer are enough where the model offers them (models without the keyword: plain call).
-        ``tv_w`` > 0 is handed to the model, or refused: a fused step that cannot form the term must not drop it."""
+        ``tv_w`` > 0 is handed to the model, or refused: a fused step that cannot form the term must not drop it.
+        ``lap_w`` > 0 (the Laplacian loss) likewise."""
         if self._live_scores is None:
             import inspect
             try:
@@ -316,6 +323,12 @@ class OptimizationRunner:
                        "the total-variation term would be dropped")
                 raise ValueError(msg)
             kwargs["tv_w"] = tv_w
+        if lap_w > 0:
+            if "lap_w" not in self._model_kwargs:
+                msg = (f"optimization.lap_w = {lap_w:g}, but the model's loss_and_grad() takes no lap_w keyword: "
+                       "the Laplacian term would be dropped")
+                raise ValueError(msg)
+            kwargs["lap_w"] = lap_w
         if self._live_scores:
             kwargs["live_scores"] = True
         if self._single_eval and "score_log" in self._model_kwargs and self._loss_accumulator is not None:

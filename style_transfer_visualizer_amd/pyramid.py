@@ -85,6 +85,11 @@ def _validate(content_img: torch.Tensor, style_img: torch.Tensor, config, video_
             msg = (f"{name} {size} is {size // factor} at the coarsest of {levels} pyramid levels; "
                    f"the minimum dimension is {MIN_DIMENSION}")
             raise ValueError(msg)
+    oc = config.optimization
+    if float(getattr(oc, "lap_w", 0.0) or 0.0) > 0:        # every level pools its own content: the coarsest decides
+        from .core_model import check_lap_fits, check_lap_pools  # noqa: PLC0415
+        check_lap_fits(check_lap_pools(oc.lap_pools), H // factor, W // factor,
+                       f" (the coarsest of {levels} pyramid levels)" if levels > 1 else "")
     return levels, Hs, Ws
 
 
@@ -171,7 +176,8 @@ def run_pyramid(  # noqa: PLR0913
                     runtime.setup_random_seed(seed)
                 model = core_model.StyleContentModel(style_layers=oc.style_layers, content_layers=oc.content_layers,
                                                      precision=config.hardware.precision,
-                                                     **style_mix.option_kwargs(oc, "style_layer_weights")).to(device)
+                                                     **style_mix.option_kwargs(oc, "style_layer_weights"),
+                                                     **core_model.lap_option_kwargs(oc)).to(device)
                 model.set_targets(styles[k], contents[k], **style_mix.option_kwargs(oc, "style_blend"))
                 if k == 0:
                     input_img = core_model.initialize_input(contents[0], oc.init_method)

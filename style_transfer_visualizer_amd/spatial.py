@@ -143,14 +143,23 @@ def _refuse_layer_weights(style_layer_weights) -> None:
         raise ValueError(msg)
 
 
+def _refuse_lap(lap_w: float) -> None:
+    """The Laplacian loss is refused here as ``tv_w > 0`` is."""
+    if lap_w:
+        msg = ("the Laplacian loss (lap_w > 0) is not available on the row-strip path: its pooled cells and differences across "
+               "strip borders and the all-reduced terms are not implemented; use lap_w = 0 here, or a whole image")
+        raise ValueError(msg)
+
+
 class SpatialShard:
     """This rank's share of one image: buffers, the two programs around the all-reduce, Adam state."""
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
                  style_w: float, content_w: float, tv_w: float = 0.0,
-                 style_layer_weights: list[float] | None = None) -> None:
+                 style_layer_weights: list[float] | None = None, lap_w: float = 0.0) -> None:
         _refuse_layer_weights(style_layer_weights)
+        _refuse_lap(lap_w)
         if tv_w:
             msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
                    "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
@@ -262,8 +271,9 @@ class HaloShard:
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
                  style_w: float, content_w: float, group=None, split: bool = False, tv_w: float = 0.0,
-                 style_layer_weights: list[float] | None = None) -> None:
+                 style_layer_weights: list[float] | None = None, lap_w: float = 0.0) -> None:
         _refuse_layer_weights(style_layer_weights)
+        _refuse_lap(lap_w)
         if tv_w:
             msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
                    "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
