@@ -402,6 +402,25 @@ int stv_luma_transfer(const float* result, const float* content, float* out, int
  * or not finite, a stack of 2 GiB or more, `out` overlapping the stack. */
 int stv_gram_blend(const float* stack, float* out, const float* weights, int K, long long n, void* stream);
 
+/* ---- Spatial guidance (--content-mask, --style-mask; no counterpart in the reference; Gatys et al. 2017, "Controlling
+ *      perceptual factors in neural style transfer", section 4.2, the guided Gram matrices).  Since version 112.  One launch
+ *      per style tap and evaluation, in front of that tap's Gram chains:
+ *   out[r][p][c] = labels[p] == r ? F[p][c] : +0        r < R,  p < n_pixels,  c < C
+ *      No arithmetic: an element of a slab holds the bits of its source (NaN payloads and -0 survive) or the bits of +0.
+ *      A label >= R (255 by convention: no region) leaves the pixel zero in every slab.  Every element is written. ------ */
+/* launch constants: a work item is 16 bytes of one pixel's channels (one 16-byte load, R 16-byte stores: F is read once,
+ * whatever R), a pass of the capped grid covers STV_MASK_SPLIT_MAX_BLOCKS * STV_MASK_SPLIT_THREADS items.  Vector path:
+ * C * element size a multiple of 16 behind 16-byte aligned F and out; otherwise a work item is one element. */
+#define STV_MASK_MAX_REGIONS 4
+#define STV_MASK_SPLIT_THREADS 256
+#define STV_MASK_SPLIT_MAX_BLOCKS 1024
+/* F: NHWC [n_pixels][C] in `dtype` storage (STV_F32 | STV_BF16; STV_BF16X3 is STV_ERR_ARG as for every op that forms no
+ * product - its storage is fp32); labels: uint8 [n_pixels] on the device; out: [R][n_pixels][C], contiguous slabs, the
+ * offsets between them 64-bit.
+ * STV_ERR_ARG, before any HIP call: a null pointer, R < 1 or R > STV_MASK_MAX_REGIONS, n_pixels < 1, C < 1, a slab of
+ * 2 GiB or more, `out` overlapping F or labels. */
+int stv_mask_split(const void* F, const uint8_t* labels, void* out, size_t n_pixels, int C, int R, int dtype, void* stream);
+
 /* ---- Frame / PNG export: prepare_image_for_output (image_io.py:129-152: denormalise,
  *      nan_to_num(nan=0, posinf=1, neginf=0), clamp 0..1) fused with the uint8 conversion, on the
  *      device, so only H*W*3 bytes cross to the host.  x NCHW fp32 [3][H][W] -> out HWC uint8.
@@ -502,7 +521,7 @@ enum {
   STV_OP_POOL_BWD, STV_OP_RELU_FWD, STV_OP_RELU_BWD, STV_OP_GRAM_PARTIAL,
   STV_OP_GRAM_FINISH, STV_OP_CONTENT_LOSS, STV_OP_CONTENT_GRAD, STV_OP_LOSS_COMBINE,
   STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER, STV_OP_TV,
-  STV_OP_LAP
+  STV_OP_LAP, STV_OP_MASK_SPLIT
 };
 /* Operands follow the direct entry points' argument order (inputs p0.., outputs q0..).
  * CONV_FIRST_FWD takes the stv_conv_first_pack buffer in p3 (p1 unused) and gram_partials, or NULL, in q1;
@@ -521,7 +540,8 @@ enum {
  * total score LOSS_COMBINE wrote) and taps = iters_per_step: the one program replays for every iteration of every step.
  * TV (since version 105) runs stv_tv: p0 = x, q0 = loss_part, q1 = dx, cin = C, H, W, f0 = coef, flags.
  * LAP (since version 111) runs stv_lap: p0 = x, p1 = target, q0 = cells, q1 = loss_part, q2 = dx, cin = C, H, W, cout = pool,
- * taps = mode, f0 = coef, flags. */
+ * taps = mode, f0 = coef, flags.
+ * MASK_SPLIT (since version 112) runs stv_mask_split: p0 = F, p1 = labels, q0 = out, n = n_pixels, cin = C, cout = R. */
 typedef struct {
   int32_t op, dtype, flags, taps;
   int32_t H, W, cin, cout;

@@ -18,7 +18,7 @@ RELU_IN, RELU_OUT, MASK, ACCUM, W_BLOCKED, POOL_IDX, POOL_ROUTE, POOL_ONLY = 1, 
 
 (OP_CONV_FIRST_FWD, OP_CONV_FIRST_DGRAD, OP_CONV, OP_POOL_FWD, OP_POOL_BWD, OP_RELU_FWD,
  OP_RELU_BWD, OP_GRAM_PARTIAL, OP_GRAM_FINISH, OP_CONTENT_LOSS, OP_CONTENT_GRAD,
- OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER, OP_TV, OP_LAP) = range(1, 19)
+ OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER, OP_TV, OP_LAP, OP_MASK_SPLIT) = range(1, 20)
 
 CONTENT_LOSS_PARTS = 256
 TV_LOSS_PARTS = 256       # stv.h STV_TV_LOSS_PARTS: one loss partial per workgroup of stv_tv, which is also its grid cap
@@ -33,6 +33,9 @@ KIND_STYLE, KIND_CONTENT, KIND_EXTRA = 0, 1, 2      # third column of the combin
 LAP_POOL, LAP_LOSS, LAP_GRAD = 0, 1, 2
 LAP_POOLS = (1, 2, 4, 8, 16, 32)
 LAP_THREADS, LAP_TILE_H, LAP_TILE_W, LAP_LOSS_PARTS, LAP_GRAD_MAX_BLOCKS, LAP_VEC = 256, 8, 32, 256, 512, 4
+# launch constants of stv_mask_split (stv.h STV_MASK_*; csrc/guide.hip): at most MASK_MAX_REGIONS slabs, a work item is 16 bytes
+# of one pixel's channels, a pass of the capped grid covers MASK_SPLIT_MAX_BLOCKS * MASK_SPLIT_THREADS items
+MASK_MAX_REGIONS, MASK_SPLIT_THREADS, MASK_SPLIT_MAX_BLOCKS = 4, 256, 1024
 RESIZE_DOWN2, RESIZE_UP2 = 0, 1                     # stv.h STV_RESIZE_*: the modes of stv_resize2x
 # launch constants of stv_resize2x (stv.h STV_RESIZE_THREADS, STV_RESIZE_MAX_BLOCKS; pixels per work item): a work item is
 # RESIZE_VEC consecutive OUTPUT pixels of one row, a pass of the capped grid covers RESIZE_MAX_BLOCKS * RESIZE_THREADS items
@@ -77,13 +80,13 @@ class StvGramTap(ctypes.Structure):
 
     def fill(self, *, n_pixels: int, channels: int, clamp_max: float, coef: float, partials: int, F: int | None = None,
              target: int | None = None, gram_out: int | None = None, loss_part: int | None = None,
-             sgrad: int | None = None, coef_dev: int | None = None) -> None:
+             sgrad: int | None = None, coef_dev: int | None = None, norm: float | None = None) -> None:
         """One tap of a batched Gram chain from device addresses (None: absent; ``F`` absent: the slabs are already
-        filled).  ``norm`` is the reference's ``b*c*h*w``."""
+        filled).  ``norm`` is the reference's ``b*c*h*w`` unless given (a guided region: ``c`` times its pixel count)."""
         self.F, self.partials, self.target, self.gram_out = F, partials, target, gram_out
         self.loss_part, self.sgrad, self.coef_dev = loss_part, sgrad, coef_dev
         self.n_pixels, self.channels = n_pixels, channels
-        self.clamp_max, self.norm, self.coef = clamp_max, float(channels * n_pixels), float(coef)
+        self.clamp_max, self.norm, self.coef = clamp_max, float(channels * n_pixels) if norm is None else float(norm), float(coef)
 
 
 # name -> (restype, argtypes); every symbol include/stv.h declares
@@ -123,6 +126,7 @@ SIGNATURES = {
     "stv_content_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_int, c_int, c_void_p]),
     "stv_tv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "stv_lap": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
+    "stv_mask_split": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "stv_resize2x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "stv_resize_axis": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "stv_color_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),

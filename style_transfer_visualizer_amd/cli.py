@@ -4,7 +4,8 @@ Options that only have meaning for presentation features outside this build (com
 are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,bf16x3}``, ``--tv-w``,
 ``--pyramid-levels`` / ``--pyramid-steps``, ``--preserve-color {off,match,luma}``, ``--content-size`` / ``--style-size`` /
 ``--style-scale`` / ``--resize-filter {bilinear,bicubic,lanczos}``, ``--style-also`` / ``--style-blend`` /
-``--style-layer-weights``, ``--lap-w`` / ``--lap-pool`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
+``--style-layer-weights``, ``--lap-w`` / ``--lap-pool``, ``--content-mask`` / ``--style-mask`` / ``--mask-regions`` /
+``--region-weights`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
 """
 from __future__ import annotations
 
@@ -13,7 +14,7 @@ import sys
 
 from . import config as stv_config
 from . import main as stv_main
-from . import style_mix
+from . import guidance, style_mix
 from .config_defaults import DEFAULT_LOG_EVERY
 from .constants import VIDEO_QUALITY_MAX, VIDEO_QUALITY_MIN
 from .logging_utils import logger
@@ -72,6 +73,14 @@ def build_arg_parser() -> argparse.ArgumentParser:
     opt.add_argument("--style-layer-weights", type=str,
                      help="Comma-separated weights of the style layers, paired by position with --style-layers "
                           "(default: every layer counts 1)")
+    opt.add_argument("--content-mask", type=str, default=S, metavar="PATH",
+                     help="Grey mask of the content image (same pixel size): spatial guidance, together with --style-mask")
+    opt.add_argument("--style-mask", type=str, default=S, metavar="PATH",
+                     help="Grey mask of the style image (same pixel size): region r of the content takes region r of the style")
+    opt.add_argument("--mask-regions", type=int, default=S,
+                     help="Regions of the two masks, 2 to 4 uniform grey bands (default: 2, black and white)")
+    opt.add_argument("--region-weights", type=str,
+                     help="Comma-separated weights of the regions (default: every region counts 1; 0 leaves a region unstyled)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
     opt.add_argument("--init-method", choices=["random", "white", "content"], default=S, help="Initialization method")
     opt.add_argument("--seed", type=int, default=S, help="Random seed")
@@ -165,6 +174,11 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
     if o.style_layer_weights is not None:
         rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Style Layers") + 1,
                     ("Style Layer Weights", o.style_layer_weights))
+    if paths.content_mask_path or paths.style_mask_path:
+        weights = guidance.check_region_weights(o.region_weights, o.mask_regions)
+        at = next(i for i, (label, _) in enumerate(rows) if label == "Style image loaded") + 1
+        rows[at:at] = [("Content mask", paths.content_mask_path), ("Style mask", paths.style_mask_path),
+                       ("Mask Regions", o.mask_regions), ("Region Weights", [float(w) for w in weights])]
     for label, value in rows:
         logger.info("%s: %s", label, value)
 
@@ -183,7 +197,8 @@ def run_from_args(args: argparse.Namespace) -> None:
             sys.exit(0)
     cfg = stv_config.build_config_from_cli(vars(args), base_config=base_cfg)
     paths = InputPaths(content_path=args.content, style_path=args.style,
-                       extra_style_paths=tuple(getattr(args, "style_also", ())))
+                       extra_style_paths=tuple(getattr(args, "style_also", ())),
+                       content_mask_path=getattr(args, "content_mask", None), style_mask_path=getattr(args, "style_mask", None))
     log_parameters(paths, cfg, args)
     stv_main.style_transfer(paths, cfg)
     if args.compare_inputs or args.compare_result:

@@ -9,7 +9,8 @@ additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf1
 ``optimization.content_size`` / ``style_size`` / ``style_scale`` / ``resize_filter`` (resize the inputs on the device before
 the run, ``resize.py``; 0 = keep the file's size) and ``optimization.style_blend`` / ``style_layer_weights`` (blend weights of
 several style images, a weight per style layer, ``style_mix.py``; ``None`` = not set) and ``optimization.lap_w`` /
-``lap_pools`` (weight and pool sizes of the Laplacian loss against the content image, 0 = off).
+``lap_pools`` (weight and pool sizes of the Laplacian loss against the content image, 0 = off) and ``optimization.mask_regions``
+/ ``region_weights`` (regions of the two masks of a guided run and their weights, ``guidance.py``; read only with masks).
 """
 from __future__ import annotations
 
@@ -43,6 +44,8 @@ class OptimizationConfig(BaseModel):
     resize_filter: ResizeFilter = Field(d.DEFAULT_RESIZE_FILTER)
     style_blend: list[float] | None = d.DEFAULT_STYLE_BLEND
     style_layer_weights: list[float] | None = d.DEFAULT_STYLE_LAYER_WEIGHTS
+    mask_regions: int = Field(d.DEFAULT_MASK_REGIONS, ge=2, le=4)
+    region_weights: list[float] | None = d.DEFAULT_REGION_WEIGHTS
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
     seed: int = Field(d.DEFAULT_SEED, ge=0)
@@ -153,6 +156,7 @@ _DIRECT = {
     "output": ("output", "output"), "log_every": ("output", "log_every"), "log_loss": ("output", "log_loss"),
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
     "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lap_w": ("optimization", "lap_w"),
+    "mask_regions": ("optimization", "mask_regions"),
     "lr": ("optimization", "lr"),
     "pyramid_levels": ("optimization", "pyramid_levels"), "preserve_color": ("optimization", "preserve_color"),
     "content_size": ("optimization", "content_size"), "style_size": ("optimization", "style_size"),
@@ -221,6 +225,8 @@ def _apply_optimization_overrides(cfg: StyleTransferConfig, args: Mapping[str, A
         cfg.optimization.pyramid_steps = parse_int_list(args["pyramid_steps"])
     if args.get("lap_pool"):
         cfg.optimization.lap_pools = OptimizationConfig(lap_pools=parse_int_list(args["lap_pool"])).lap_pools
+    if args.get("region_weights"):
+        cfg.optimization.region_weights = parse_float_list(args["region_weights"])
     if args.get("style_blend"):
         cfg.optimization.style_blend = parse_float_list(args["style_blend"])
     if args.get("style_layer_weights"):

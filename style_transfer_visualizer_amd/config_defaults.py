@@ -17,6 +17,8 @@ DEFAULT_STYLE_BLEND = None   # build-specific: one blend weight per style image,
 DEFAULT_STYLE_LAYER_WEIGHTS = None  # build-specific: one weight per entry of style_layers (None = every layer counts 1)
 DEFAULT_LAP_WEIGHT = 0.0     # build-specific: weight of the Laplacian loss against the content image (0 = off)
 DEFAULT_LAP_POOLS = [4]      # build-specific: its pool sizes (powers of two from 1 to 32, one to four of them)
+DEFAULT_MASK_REGIONS = 2     # build-specific: regions of --content-mask / --style-mask, 2 to 4 uniform grey bands
+DEFAULT_REGION_WEIGHTS = None  # build-specific: one weight per region (None = every region counts 1; 0 = left unstyled)
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"
 DEFAULT_SEED = 0

@@ -21,7 +21,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from . import _lib, ops, plan, style_mix, synthetic
+from . import _lib, guidance, ops, plan, style_mix, synthetic
 from .constants import GRAM_MATRIX_CLAMP_MAX
 from .logging_utils import logger
 
@@ -404,26 +404,40 @@ class _Engine:
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  H: int, W: int, dtype: torch.dtype, device: torch.device, *, split: bool = False,
-                 assume_device: bool = False, lap_pools: tuple = ()) -> None:
+                 assume_device: bool = False, lap_pools: tuple = (), guide: guidance.Guide | None = None) -> None:
         """``assume_device``: as for ``plan.Schedule`` - the step a GPU engine builds, on host tensors, to be inspected.
         ``lap_pools``: the pool sizes of the Laplacian loss; the engine then owns, per pool, a target, a residual scratch and
-        ``LAP_LOSS_PARTS`` loss partials."""
+        ``LAP_LOSS_PARTS`` loss partials.
+        ``guide`` (spatial guidance): every style tap runs one Gram chain per active region on the slabs ``stv_mask_split``
+        fills; the combine table has one kind-0 row per (layer, region), in layer then region order, and the style targets
+        are ``[Ra, C, C]`` per layer.  ``None``: no allocation, no op, the engine as it always was."""
         self.layers, self.style_at, self.content_at = layers, style_at, content_at
         self.H, self.W, self.dtype, self.device = H, W, dtype, device
         self.split = split
         # (the A/B switches as they stand now, for every program of this engine)
         self.sched = plan.Schedule(layers, style_at, content_at, H, W, dtype, device, with_grad=True, split=split,
-                                   switches=plan.Switches.from_env(), assume_device=assume_device)
+                                   switches=plan.Switches.from_env(), assume_device=assume_device,
+                                   **({"guide": guide.n} if guide is not None else {}))
         s = self.sched
+        self.guide = guide
         self.n_style, self.n_content = len(s.style_taps), len(s.content_taps)
-        n_terms = self.n_style + self.n_content
+        if guide is not None:
+            if tuple(guide.content_labels.shape) != (H, W):
+                msg = f"content_labels are {tuple(guide.content_labels.shape)}, the image is {(H, W)}"
+                raise ValueError(msg)
+            guidance.check_rows(self.n_style, guide.n, self.n_content + 1 + len(lap_pools))
+            maps = guidance.tap_maps(guide.content_labels, [(t.buf.H, t.buf.W) for t in s.style_taps])
+            s.attach_regions(maps, guidance.check_counts(maps, guide.n, "content", guide.active, style_at))
+        # one combine row per Gram chain: per style tap, or per (tap, region) under guidance
+        self.n_style_rows = len(s.all_chains())
+        n_terms = self.n_style_rows + self.n_content
         off = 0
         rows, scale = [], []
-        for tap in s.style_taps:
+        for tap in s.all_chains():
             tap.parts_off, tap.parts_cnt = off, ops.gram_loss_parts(tap.buf.C)
             off += tap.parts_cnt
             rows.append([tap.parts_off, tap.parts_cnt, 0])
-            scale.append(1.0 / float(tap.buf.C * tap.buf.C))
+            scale.append(self._style_scale(tap, None))
             tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C, device=device, dtype=dtype)
         for tap in s.content_taps:
             tap.parts_off, tap.parts_cnt = off, ops._lib.CONTENT_LOSS_PARTS
@@ -445,6 +459,7 @@ class _Engine:
         self._tv_heads: dict = {}        # tv_w -> (table, scale, losses) of the combine op with the extra kind-2 row
         self._layer_heads: dict = {}     # style layer weights -> (table, scale, losses) of the combine op of a weighted step
         self._lap_heads: dict = {}       # (tv_w, lap_w, layer weights) -> (table, scale, losses) with the Laplacian rows
+        self._region_head: tuple | None = None      # (scale, losses, scores) of last_region_losses()' own combine launch
         self.image_channels = int(s.nodes[0].cin)
         check_lap_fits(self.lap_pools, H, W)
         cells = [(self.image_channels, H // p, W // p) for p in self.lap_pools]
@@ -455,6 +470,19 @@ class _Engine:
         # valid against the forward that filled them last.  `generation` counts evaluations.
         self.generation = 0
         self._stage: torch.Tensor | None = None      # fp32 contiguous copy of a non-conforming input
+
+    def _region_weight(self, tap) -> float:
+        """``lambda_r`` of a Gram chain's tap (1.0 without guidance)."""
+        return 1.0 if self.guide is None else self.guide.weights[tap.order % self.guide.n]
+
+    def _style_scale(self, tap, layer_w: tuple | None) -> float:
+        """The combine scale of a Gram chain's row, formed in double: ``w_l * lambda_r / C^2`` (without guidance ``w_l / C^2``,
+        without layer weights ``1 / C^2``, exactly as those steps always formed it)."""
+        cc = float(tap.buf.C * tap.buf.C)
+        if self.guide is None:
+            return 1.0 / cc if layer_w is None else float(layer_w[tap.order]) / cc
+        w = 1.0 if layer_w is None else float(layer_w[tap.parent.order])
+        return w * self._region_weight(tap) / cc
 
     # -- op list pieces -------------------------------------------------------
     def _forward_with_losses(self, x: torch.Tensor, *, style_coef: float, with_seed: bool,
@@ -468,6 +496,8 @@ class _Engine:
         s = self.sched
 
         def coef_of(tap) -> float:
+            if self.guide is not None:      # style_w * w_l * lambda_r, formed in double
+                return style_coef * (1.0 if layer_w is None else layer_w[tap.parent.order]) * self._region_weight(tap)
             return style_coef if layer_w is None else style_coef * layer_w[tap.order]
         if content_coef is not None:
             s.alloc_grads()          # the content term's gradient is written during the forward half
@@ -481,15 +511,21 @@ class _Engine:
                            q1=tap.buf.grad if fused else None, n=tap.buf.act.numel(), f0=content_coef if fused else 0.0)]
         batch = [dict(tap=tap, target=tap.target, loss_part=self.parts[tap.parts_off:],
                       sgrad=tap.sgrad if with_seed else None, coef=coef_of(tap), partials_ready=tap.finish_late)
-                 for tap in s.style_taps if tap.in_tail or tap.finish_late]
-        tail = [s.gram_multi_op(batch)] if batch else []
+                 for tap in s.all_chains() if tap.in_tail or tap.finish_late]
+        # (a batched launch takes 8 entries; without guidance a batch never holds more)
+        tail = [s.gram_multi_op(batch[i:i + 8]) for i in range(0, len(batch), 8)]
         for tap in s.content_taps:
             if tap.in_tail:
                 tail += chain(tap)
 
         def after(node) -> list:
             out = []
-            for tap in node.dst.taps:
+            taps = []
+            for tap in node.dst.taps:      # (guided: the split right behind the producer, then the regions' chains)
+                if tap.kind == "style" and s.guide:
+                    out.append(s.mask_split_op(tap))
+                taps += s.chains(tap) if tap.kind == "style" else [tap]
+            for tap in taps:
                 if tap.finish_late:      # partial sums here (unless the first layer left them itself), finish in the tail
                     out += s.gram_ops(tap, gram_out=None, target=None, loss_part=None, sgrad=None, coef=0.0,
                                       coef_dev=None, finish=False)
@@ -509,7 +545,7 @@ class _Engine:
         if head is None:
             if len(self._layer_heads) >= 16:
                 self._layer_heads.pop(next(iter(self._layer_heads)))
-            sc = [float(w) / float(tap.buf.C * tap.buf.C) for w, tap in zip(layer_w, self.sched.style_taps, strict=True)]
+            sc = [self._style_scale(tap, layer_w) for tap in self.sched.all_chains()]
             sc += [1.0 / float(tap.buf.act.numel()) for tap in self.sched.content_taps]
             head = self._layer_heads[layer_w] = (self.table, torch.tensor(sc, dtype=torch.float32, device=self.device),
                                                  torch.zeros_like(self.losses))
@@ -528,7 +564,7 @@ class _Engine:
             row = torch.tensor([[self.tv_parts_off, _lib.TV_LOSS_PARTS, _lib.KIND_EXTRA]], dtype=torch.int32, device=self.device)
             sc = torch.tensor([tv_scale(tv_w, self.image_channels, self.H, self.W)], dtype=torch.float32, device=self.device)
             head = cache[key] = (torch.cat([table, row]), torch.cat([scale, sc]),
-                                 torch.zeros(self.n_style + self.n_content + 1, device=self.device, dtype=torch.float32))
+                                 torch.zeros(self.n_style_rows + self.n_content + 1, device=self.device, dtype=torch.float32))
         return head
 
     def _tv_op(self, x: torch.Tensor, *, loss: bool = False, grad: torch.Tensor | None = None, tv_w: float = 0.0):
@@ -650,6 +686,8 @@ class _Engine:
         self.generation += 1
         x = style_img.detach().contiguous().float()
         Hs, Ws = x.shape[-2:]
+        if self.guide is not None:
+            return self._capture_style_guided(x)
         sched = (self.sched if (Hs, Ws) == (self.H, self.W) else
                  plan.Schedule(self.layers, self.style_at, self.content_at, Hs, Ws, self.dtype, self.device,
                                with_grad=False, split=self.split, switches=self.sched.switches))
@@ -662,6 +700,31 @@ class _Engine:
             tap.target = g
         return grams
 
+    def _capture_style_guided(self, x: torch.Tensor) -> list[torch.Tensor]:
+        """Guided Gram targets ``[Ra, C, C]`` per style layer: the style image at its own size with its own label maps and
+        pixel counts, through the same split and the same Gram ops as the step (a schedule of its own, also at the
+        content's size: the engine's taps hold the content's maps)."""
+        g = self.guide
+        Hs, Ws = (int(v) for v in x.shape[-2:])
+        if tuple(g.style_labels.shape) != (Hs, Ws):
+            msg = f"style_labels are {tuple(g.style_labels.shape)}, the style image is {(Hs, Ws)}"
+            raise ValueError(msg)
+        sched = plan.Schedule(self.layers, self.style_at, self.content_at, Hs, Ws, self.dtype, self.device, with_grad=False,
+                              split=self.split, switches=self.sched.switches, guide=g.n)
+        maps = guidance.tap_maps(g.style_labels, [(t.buf.H, t.buf.W) for t in sched.style_taps])
+        sched.attach_regions(maps, guidance.check_counts(maps, g.n, "style", g.active, self.style_at))
+        grams = [torch.empty(g.n, tap.buf.C, tap.buf.C, device=self.device, dtype=torch.float32) for tap in sched.style_taps]
+        op_list = sched.forward_ops(x)
+        for tap, table in zip(sched.style_taps, grams, strict=True):
+            op_list.append(sched.mask_split_op(tap))
+            for r, c in enumerate(tap.regions):
+                op_list += sched.gram_ops(c, gram_out=table[r], target=None, loss_part=None, sgrad=None, coef=0.0, coef_dev=None)
+        plan.Program(op_list, extra=(sched,)).run()
+        for tap, table in zip(self.sched.style_taps, grams, strict=True):
+            for r, c in enumerate(tap.regions):
+                c.target = table[r]
+        return grams
+
     def bind_targets(self, style_targets: list[torch.Tensor], content_targets: list[torch.Tensor]) -> None:
         """Re-point taps at the model's public target lists (they may have been replaced)."""
         if len(style_targets) != self.n_style or len(content_targets) != self.n_content:
@@ -669,6 +732,12 @@ class _Engine:
             raise RuntimeError(msg)
         changed = False
         for tap, t in zip(self.sched.style_taps, style_targets, strict=True):
+            if self.guide is not None:      # [Ra, C, C]: region r's chain reads table r
+                t = self._as_target(t, (self.guide.n, tap.buf.C, tap.buf.C), torch.float32)
+                for r, c in enumerate(tap.regions):
+                    changed |= c.target is None or c.target.data_ptr() != t[r].data_ptr()
+                    c.target = t[r]
+                continue
             t = self._as_target(t, (tap.buf.C, tap.buf.C), torch.float32)
             changed |= tap.target is None or tap.target.data_ptr() != t.data_ptr()
             tap.target = t
@@ -742,7 +811,8 @@ class _Engine:
                None if score_log is None else (tuple(t.data_ptr() for t in score_log), tuple(score_log[0].shape)),
                None if then_step is None else then_step.key()) + ((("tv", tv_w),) if tv_w else ()) + (
                    (("layer_w", layer_w),) if layer_w is not None else ()) + (
-                   (("lap", lap_w, self.lap_pools),) if lap_w else ())
+                   (("lap", lap_w, self.lap_pools),) if lap_w else ()) + (
+                   (self.guide.key(),) if self.guide is not None else ())
 
         def build():
             s = self.sched
@@ -773,7 +843,28 @@ class _Engine:
             return fwd + [self._combine_op(style_w, content_w, score_log, tv_w, layer_w, lap_w)] + bwd + tail
         self._program(key, build).run(self.use_graph)
 
+    def region_losses(self) -> torch.Tensor:
+        """The unweighted terms ``loss_{l,r}`` of the last evaluation, ``[L, Ra]``: one more launch of the combine kernel
+        over the style rows of the loss partials that evaluation left, with ``1 / C^2`` as every row's scale."""
+        if self.guide is None:
+            msg = "region losses exist on a guided model only (guide_regions > 0)"
+            raise RuntimeError(msg)
+        if self._region_head is None:
+            sc = [1.0 / float(tap.buf.C * tap.buf.C) for tap in self.sched.all_chains()]
+            self._region_head = (torch.tensor(sc, dtype=torch.float32, device=self.device),
+                                 torch.zeros(self.n_style_rows, device=self.device, dtype=torch.float32),
+                                 torch.zeros(4, device=self.device, dtype=torch.float32))
+        scale, losses, scores = self._region_head
+        ops.loss_combine(self.parts, self.table[:self.n_style_rows].contiguous(), scale, 1.0, 1.0, losses, scores)
+        return losses.view(self.n_style, self.guide.n)
+
+    def _refuse_autograd(self) -> None:
+        if self.guide is not None:
+            msg = "the autograd path (forward / backward) has no guided form: a guided engine runs loss_and_grad() only"
+            raise RuntimeError(msg)
+
     def forward_losses(self, x: torch.Tensor) -> None:
+        self._refuse_autograd()
         self.generation += 1
         key = ("fwd", x.data_ptr())
 
@@ -783,6 +874,7 @@ class _Engine:
         self._program(key, build).run(self.use_graph)
 
     def backward_from(self, gout: torch.Tensor, grad: torch.Tensor) -> None:
+        self._refuse_autograd()
         self.coef_buf.copy_(gout)
         key = ("bwd", grad.data_ptr())
 
@@ -834,8 +926,13 @@ class StyleContentModel(nn.Module):
 
     def __init__(self, style_layers: list[int], content_layers: list[int], *,
                  precision: str | None = None, style_layer_weights: list[float] | None = None,
-                 lap_pools: tuple | list = ()) -> None:
+                 lap_pools: tuple | list = (), guide_regions: int = 0, region_weights: list[float] | None = None) -> None:
+        """``guide_regions`` = R > 0 (1 to ``guidance.MAX_REGIONS``): spatial guidance - ``set_targets`` then takes one label map
+        per image and the style term is ``sum_l w_l * sum_r lambda_r * loss_{l,r}`` with ``region_weights`` = lambda (default all
+        1; a region of weight 0 is left unstyled).  0: no guidance, the model as it always was."""
         super().__init__()
+        self._guide: guidance.Guide | None = None
+        self.set_guidance(guide_regions, region_weights, _init=True)
         self.lap_pools = check_lap_pools(lap_pools)     # pool sizes of the Laplacian loss; empty: the term is not available
         self.lap_targets: list[torch.Tensor] | None = None
         self._style_layers_given = [int(v) for v in style_layers]
@@ -867,6 +964,32 @@ class StyleContentModel(nn.Module):
     def style_tap_weights(self) -> tuple[float, ...] | None:
         """The layer weights in the order of ``forward()``'s style losses (the layers sorted), ``None`` when every one is 1."""
         return self._tap_weights
+
+    # -- spatial guidance ----------------------------------------------------------
+    def set_guidance(self, guide_regions: int, region_weights: list[float] | None = None, *, _init: bool = False) -> None:
+        """Switch spatial guidance on (``guide_regions`` = R > 0) or off (0).  Targets and engines of the other mode are
+        dropped: ``set_targets`` has to be called again."""
+        if guide_regions == 0 and not isinstance(guide_regions, bool):
+            if region_weights is not None:
+                msg = f"region_weights {list(region_weights)} without guide_regions: the weights would be dropped"
+                raise ValueError(msg)
+            self.guide_regions, self.region_weights = 0, None
+        else:
+            regions = guidance.check_regions(guide_regions)
+            self.guide_regions, self.region_weights = regions, guidance.check_region_weights(region_weights, regions)
+        self._guide = None
+        if not _init:
+            self._engines.clear()
+            self.style_targets = self.content_targets = self.lap_targets = None
+
+    def last_region_losses(self) -> torch.Tensor:
+        """The unweighted guided style terms ``loss_{l,r}`` of the last ``loss_and_grad``, ``[L, Ra]`` (layers sorted, active
+        regions in ascending order)."""
+        eng = getattr(self, "_last_engine", None)
+        if eng is None or eng.guide is None:
+            msg = "last_region_losses() needs a guided model (guide_regions > 0) and an evaluation by loss_and_grad()"
+            raise RuntimeError(msg)
+        return eng.region_losses()
 
     # -- engine plumbing ---------------------------------------------------------
     def _layers(self) -> list[nn.Module]:
@@ -901,12 +1024,14 @@ class StyleContentModel(nn.Module):
         eng = self._engines.get(key)
         if eng is None:
             eng = _Engine(self._layers(), self._style_at, self._content_at, H, W, self._dtype, x.device, split=self._split,
-                          **({"lap_pools": self.lap_pools} if self.lap_pools else {}))
+                          **({"lap_pools": self.lap_pools} if self.lap_pools else {}),
+                          **({"guide": self._guide} if self._guide is not None else {}))
             self._engines[key] = eng
         return eng
 
     def set_targets(self, style_img: torch.Tensor | list[torch.Tensor] | tuple[torch.Tensor, ...], content_img: torch.Tensor, *,
-                    style_blend: list[float] | None = None) -> None:
+                    style_blend: list[float] | None = None, content_labels: torch.Tensor | None = None,
+                    style_labels: torch.Tensor | None = None) -> None:
         """Capture Gram targets from the style image and activations from the content image.
 
         ``style_img`` may be a list or tuple of 1 to ``style_mix.MAX_STYLES`` images of any sizes: each is captured as a
@@ -918,6 +1043,10 @@ class StyleContentModel(nn.Module):
             msg = f"between 1 and {style_mix.MAX_STYLES} style images can be blended, got {len(styles)}"
             raise ValueError(msg)
         blend = style_mix.blend_weights(style_blend, len(styles))       # (refusals before the first launch)
+        self._guide = self._check_guidance(styles, content_img, content_labels, style_labels)
+        if self._guide is not None and isinstance(content_img, torch.Tensor) and content_img.dim() == 4:
+            # a guided engine is built from its label maps: new maps, a new engine
+            self._engines.pop((int(content_img.shape[-2]), int(content_img.shape[-1]), content_img.device.index), None)
         if self.lap_pools and isinstance(content_img, torch.Tensor) and content_img.dim() >= 2:
             check_lap_fits(self.lap_pools, int(content_img.shape[-2]), int(content_img.shape[-1]))
         eng = self._engine_for(content_img)
@@ -939,6 +1068,29 @@ class StyleContentModel(nn.Module):
         # the Laplacian loss's targets: the content image box-pooled, one [C, H//p, W//p] fp32 table per pool size
         self.lap_targets = eng.capture_lap(content_img) if self.lap_pools else None
 
+    def _check_guidance(self, styles: list, content_img, content_labels, style_labels) -> guidance.Guide | None:
+        """The label maps are required exactly when ``guide_regions`` > 0; every refusal comes before the first launch."""
+        given = [name for name, t in (("content_labels", content_labels), ("style_labels", style_labels)) if t is not None]
+        if not self.guide_regions:
+            if given:
+                msg = f"{' and '.join(given)} given, but the model was built without guide_regions: the labels would be dropped"
+                raise ValueError(msg)
+            return None
+        if len(given) != 2:
+            msg = (f"a model with guide_regions = {self.guide_regions} needs content_labels and style_labels, "
+                   f"got {' and '.join(given) or 'neither'}")
+            raise ValueError(msg)
+        if len(styles) != 1:
+            msg = f"spatial guidance takes one style image, got {len(styles)} (masks with several style images are not built)"
+            raise ValueError(msg)
+        guide = guidance.make_guide(self.guide_regions, self.region_weights, content_labels, style_labels)
+        for name, labels, img in (("content_labels", guide.content_labels, content_img), ("style_labels", guide.style_labels, styles[0])):
+            if isinstance(img, torch.Tensor) and img.dim() >= 2 and tuple(labels.shape) != tuple(int(v) for v in img.shape[-2:]):
+                msg = f"{name} are {tuple(labels.shape)}, their image is {tuple(int(v) for v in img.shape[-2:])}"
+                raise ValueError(msg)
+        guidance.check_maps(guide, self._layers(), self._style_at)
+        return guide
+
     def _require_targets(self) -> None:
         # same order and texts as reference core_model.py:255-258, 287-290
         if self.style_targets is None:
@@ -950,6 +1102,10 @@ class StyleContentModel(nn.Module):
 
     def forward(self, x: torch.Tensor) -> tuple[list[torch.Tensor], list[torch.Tensor]]:
         """Per-layer style and content losses for ``x`` (``[1, C, H, W]``)."""
+        if self.guide_regions:
+            msg = (f"forward() is the unguided autograd path and this model has guide_regions = {self.guide_regions}: it would "
+                   "return unguided losses (use loss_and_grad())")
+            raise RuntimeError(msg)
         self._require_targets()
         eng = self._engine_for(x)
         eng.bind_targets(self.style_targets, self.content_targets)
@@ -1005,7 +1161,8 @@ class StyleContentModel(nn.Module):
         eng.loss_and_grad(x.detach(), grad, float(style_w), float(content_w), score_log=score_log,
                           then_step=optimizers.claim_step(x), tv_w=tv_w, layer_w=self._tap_weights,
                           **({"lap_w": lap_w} if lap_w else {}))
-        n_terms = eng.n_style + eng.n_content
+        self._last_engine = eng
+        n_terms = eng.n_style_rows + eng.n_content
         if lap_w:
             losses = eng.lap_head(tv_w, lap_w, self._tap_weights)[2]
             self._tv_term = losses[n_terms] if tv_w else None
@@ -1044,6 +1201,8 @@ def prepare_model_and_input(
     optimization,
     *,
     precision: str | None = None,
+    content_labels: torch.Tensor | None = None,
+    style_labels: torch.Tensor | None = None,
 ) -> tuple[nn.Module, torch.Tensor, torch.optim.Optimizer]:
     """Build model, start image and optimizer (reference core_model.py:331-350).
 
@@ -1051,18 +1210,32 @@ def prepare_model_and_input(
     (fp32 storage, conv / Gram products from split bf16 operands);
     default from ``STV_PRECISION`` or fp32.  ``style_img`` may be a list of style images; ``optimization.style_blend``
     and ``optimization.style_layer_weights`` (``style_mix.py``) are read where the object has them; ``optimization.lap_pools``
-    is handed to the model only when ``optimization.lap_w`` > 0.
+    is handed to the model only when ``optimization.lap_w`` > 0.  ``content_labels`` / ``style_labels`` (uint8 ``[H, W]`` label
+    maps of the two images, ``guidance.py``): the model is guided, with ``optimization.mask_regions`` and
+    ``optimization.region_weights``; one without the other is refused.
     """
     from .optimizers import make_lbfgs  # noqa: PLC0415
 
+    guide_kw, label_kw = {}, {}
+    if content_labels is not None or style_labels is not None:
+        if content_labels is None or style_labels is None:
+            msg = "content_labels and style_labels go together: one label map without the other"
+            raise ValueError(msg)
+        if isinstance(style_img, (list, tuple)) and len(style_img) > 1:
+            msg = f"spatial guidance takes one style image, got {len(style_img)} (masks with several style images are not built)"
+            raise ValueError(msg)
+        guide_kw = {"guide_regions": guidance.check_regions(getattr(optimization, "mask_regions", 2), minimum=2, what="mask_regions"),
+                    "region_weights": getattr(optimization, "region_weights", None)}
+        label_kw = {"content_labels": content_labels, "style_labels": style_labels}
     model = StyleContentModel(
         style_layers=optimization.style_layers,
         content_layers=optimization.content_layers,
         precision=precision,
         **style_mix.option_kwargs(optimization, "style_layer_weights"),
         **lap_option_kwargs(optimization),
+        **guide_kw,
     ).to(device)
-    model.set_targets(style_img, content_img, **style_mix.option_kwargs(optimization, "style_blend"))
+    model.set_targets(style_img, content_img, **style_mix.option_kwargs(optimization, "style_blend"), **label_kw)
     input_img = initialize_input(content_img, optimization.init_method)
     optimizer = make_lbfgs(
         input_img,

@@ -84,6 +84,8 @@ int run_op(const stv_op_t& o, void* st) {
     case STV_OP_LAP:  // p0 = x, p1 = target; q0 = cells, q1 = loss_part, q2 = dx; cin = C; cout = pool; taps = mode; f0 = coef
       return stv_lap(static_cast<const float*>(o.p0), static_cast<const float*>(o.p1), static_cast<float*>(o.q0),
                      static_cast<float*>(o.q1), static_cast<float*>(o.q2), o.cin, o.H, o.W, o.cout, o.f0, o.taps, o.flags, st);
+    case STV_OP_MASK_SPLIT:  // p0 = F, p1 = labels; q0 = out; n = n_pixels; cin = C; cout = R
+      return stv_mask_split(o.p0, static_cast<const uint8_t*>(o.p1), o.q0, (size_t)o.n, o.cin, o.cout, o.dtype, st);
     case STV_OP_MEMSET:
       if (hipMemsetAsync(o.q0, 0, (size_t)o.n, static_cast<hipStream_t>(st)) != hipSuccess)
         return STV_ERR_LAUNCH;
@@ -122,7 +124,7 @@ int run_all(stv_program* p, void* st) {
 
 }  // namespace
 
-extern "C" int stv_version(void) { return 111; }
+extern "C" int stv_version(void) { return 112; }
 
 extern "C" int stv_program_create(const stv_op_t* ops, int n_ops, stv_program** out) {
   if (!ops || n_ops <= 0 || !out) return STV_ERR_ARG;

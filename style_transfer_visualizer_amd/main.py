@@ -17,6 +17,11 @@ run all see the images the run sees.  With all three at 0 the stage is not enter
 ``InputPaths.extra_style_paths`` / ``optimization.style_blend`` / ``optimization.style_layer_weights`` (``style_mix.py``, no
 counterpart in the reference): every style image is loaded, resized and colour-matched on its own by the rules above, and the
 list is handed to the model, which blends the Gram targets.  With no extra style and both options unset nothing here changes.
+
+``InputPaths.content_mask_path`` / ``style_mask_path`` with ``optimization.mask_regions`` / ``region_weights`` (``guidance.py``, no
+counterpart in the reference): the two masks are read and checked before the first launch, their label maps follow the images
+through the resize stage and through every level of a coarse-to-fine run, and the model is a guided one.  Without masks nothing
+here changes.
 """
 from __future__ import annotations
 
@@ -25,7 +30,7 @@ from pathlib import Path
 
 import torch
 
-from . import color, core_model, image_io, ops, optimization, pyramid, runtime, style_mix
+from . import color, core_model, guidance, image_io, ops, optimization, pyramid, runtime, style_mix
 from . import resize as resize_rules
 from .logging_utils import logger
 from .type_defs import InputPaths, SaveOptions
@@ -61,6 +66,33 @@ def _resize_extra_style(style_img: torch.Tensor, content_hw: tuple[int, int], oc
     return ops.resize(style_img.contiguous(), style_hw, oc.resize_filter)
 
 
+def _load_masks(paths: InputPaths, oc) -> tuple[torch.Tensor, torch.Tensor] | None:
+    """The label maps of the two masks (host uint8, at the pixel size of the image files), or ``None`` without masks.  Every
+    refusal that needs no device comes from here: one mask without the other, masks with several style images, the number
+    of regions, the region weights, a mask of another size than its image."""
+    content_mask, style_mask = getattr(paths, "content_mask_path", None), getattr(paths, "style_mask_path", None)
+    if not content_mask and not style_mask:
+        return None
+    if not content_mask or not style_mask:
+        msg = (f"--content-mask and --style-mask go together: got content mask {content_mask!r} and style mask {style_mask!r} "
+               "(region r of the content takes the statistics of region r of the style)")
+        raise ValueError(msg)
+    extra = tuple(getattr(paths, "extra_style_paths", ()))
+    if extra:
+        msg = f"masks cannot be combined with --style-also ({len(extra)} further style images): masks with several style images are not built"
+        raise ValueError(msg)
+    regions = guidance.check_regions(getattr(oc, "mask_regions", 2), minimum=2, what="mask_regions")
+    guidance.check_region_weights(getattr(oc, "region_weights", None), regions)
+    from PIL import Image  # noqa: PLC0415
+    maps = []
+    for which, image_path, mask_path in (("content", paths.content_path, content_mask), ("style", paths.style_path, style_mask)):
+        runtime.validate_input_paths(image_path, mask_path)
+        with Image.open(image_path) as img:
+            W, H = img.size
+        maps.append(guidance.load_mask(mask_path, (H, W), regions, which))
+    return maps[0], maps[1]
+
+
 def _style_stem(paths: InputPaths) -> str:
     """The style part of the output names: the stems of the style images joined by ``+``."""
     return "+".join(Path(p).stem for p in (paths.style_path, *getattr(paths, "extra_style_paths", ())))
@@ -84,6 +116,8 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     if layer_weights is not None:
         style_mix.check_layer_weights(layer_weights, config.optimization.style_layers)
 
+    labels = _load_masks(paths, config.optimization)      # (refusals before the first launch)
+
     if config.video.final_only:                 # reference main.py:30-33
         config.video.create_video = False
         config.video.create_gif = False
@@ -104,18 +138,22 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
         loaded_hw = tuple(int(v) for v in content_img.shape[-2:])
         content_img, style_img = _resize_inputs(content_img, style_img, oc)
         extra_styles = [_resize_extra_style(img, loaded_hw, oc) for img in extra_styles]
+        if labels is not None:                  # the maps follow their images: nearest sampling in integer arithmetic
+            labels = (guidance.resample_labels(labels[0], *(int(v) for v in content_img.shape[-2:])),
+                      guidance.resample_labels(labels[1], *(int(v) for v in style_img.shape[-2:])))
     preserve_color = config.optimization.preserve_color
     if preserve_color == "match":               # once per run, on the full-size images: a coarse-to-fine run halves the matched style
         style_img = color.match_style_to_content(style_img, content_img)
         extra_styles = [color.match_style_to_content(img, content_img) for img in extra_styles]
     if extra_styles:                            # (one style: the tensor itself, as always)
         style_img = [style_img, *extra_styles]
+    label_kw = {"content_labels": labels[0], "style_labels": labels[1]} if labels is not None else {}
     coarse_to_fine = config.optimization.pyramid_levels > 1
     if not coarse_to_fine:
         with _SETUP_LOCK:
             runtime.setup_random_seed(config.optimization.seed)
             model, input_img, optimizer = core_model.prepare_model_and_input(
-                content_img, style_img, device, config.optimization, precision=config.hardware.precision)
+                content_img, style_img, device, config.optimization, precision=config.hardware.precision, **label_kw)
 
     output_path = runtime.setup_output_directory(config.output.output)
     content_name, style_name = Path(paths.content_path).stem, _style_stem(paths) + (output_tag if tag_png else "")
@@ -126,7 +164,7 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     if coarse_to_fine:                          # (refuses frame sinks: frames would change size between levels)
         input_img, loss_metrics, elapsed = pyramid.run_pyramid(
             content_img, style_img, device, config, video_writer=video_writer, gif_collector=gif_collector,
-            seed=config.optimization.seed, setup_lock=_SETUP_LOCK)
+            seed=config.optimization.seed, setup_lock=_SETUP_LOCK, **label_kw)
     else:
         runner = optimization.OptimizationRunner(model, input_img, config, optimizer=optimizer,
                                                  video_writer=video_writer, gif_collector=gif_collector)

@@ -585,6 +585,28 @@ def gram_blend(stack: torch.Tensor, weights, out: torch.Tensor | None = None) ->
     return out
 
 
+def mask_split(F: torch.Tensor, labels: torch.Tensor, regions: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Region slabs of an NHWC activation (``stv_mask_split``): ``out[r, p, c]`` holds the bits of ``F[p, c]`` where
+    ``labels[p] == r`` and ``+0`` elsewhere, for ``r < regions`` <= ``MASK_MAX_REGIONS``; a label >= ``regions`` (255) puts
+    the pixel in no slab.  ``F``: ``[H, W, C]`` or ``[n, C]``, fp32 or bf16; ``labels``: uint8, one per pixel; ``out``:
+    ``[regions, *F.shape]`` of ``F``'s dtype, sharing no byte with either; returns ``out`` (a new tensor by default)."""
+    lib = _lib.load()
+    C = int(F.shape[-1])
+    n = F.numel() // max(C, 1)
+    if labels.dtype != torch.uint8 or labels.numel() != n:
+        msg = f"mask_split: labels are {tuple(labels.shape)} {labels.dtype}, expected {n} uint8 labels for features {tuple(F.shape)}"
+        raise RuntimeError(msg)
+    shape = (int(regions), *F.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=F.dtype, device=F.device)
+    elif tuple(out.shape) != shape or out.dtype != F.dtype:
+        msg = f"mask_split: out is {tuple(out.shape)} {out.dtype}, expected {shape} {F.dtype}"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_mask_split(_ptr(F), _ptr(labels), _ptr(out), n, C, int(regions), dtype_code(F.dtype), _stream()),
+               "stv_mask_split")
+    return out
+
+
 def _lap(x, target, cells, loss_part, dx, shape, pool: int, coef: float, mode: int, flags: int) -> None:
     lib = _lib.load()
     C, H, W = (int(v) for v in shape)

@@ -39,7 +39,7 @@ from torch import nn
 from . import _lib, ops
 from ._lib import (ACCUM, MASK, POOL_IDX, POOL_ONLY, POOL_ROUTE, W_BLOCKED, OP_GRAM_MULTI, OP_CONTENT_GRAD, OP_CONTENT_LOSS, OP_CONV, OP_CONV_FIRST_DGRAD,
                    OP_CONV_FIRST_FWD, OP_GRAM_FINISH, OP_GRAM_PARTIAL, OP_LOSS_COMBINE, OP_POOL_BWD,
-                   OP_POOL_FWD, OP_RELU_BWD, OP_RELU_FWD, OP_TV, RELU_IN, RELU_OUT, StvOp)
+                   OP_MASK_SPLIT, OP_POOL_FWD, OP_RELU_BWD, OP_RELU_FWD, OP_TV, RELU_IN, RELU_OUT, StvOp)
 
 GRAM_CLAMP_MAX = 5e5  # reference constants.py:15
 
@@ -130,6 +130,14 @@ class Tap:
     in_tail: bool = False             # in the batched tail behind the last conv; False: right behind its producer
     finish_late: bool = False         # style: partial sums behind the producer, only the finish pass in the tail
     grad_fused: bool = False          # content: the fused step forms loss and gradient in one pass (stv_content_loss_grad)
+    # spatial guidance (Schedule.attach_regions): a guided style tap owns a label map, the region slabs stv_mask_split fills
+    # and one child tap per active region - its `buf` is the slab, its `norm` C times the region's pixel count; the child
+    # carries the Gram chain (partials, target, seed, loss partials) and takes the placement of its parent
+    labels: torch.Tensor | None = None
+    slabs: torch.Tensor | None = None
+    regions: list | None = None
+    norm: float | None = None         # the Gram's divisor; None: C * H * W of the buffer (the reference's b*c*h*w)
+    parent: Tap | None = None
 
 
 def _check_layer(layer: nn.Module, idx: int) -> str:
@@ -163,7 +171,7 @@ class Schedule:
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  H: int, W: int, dtype: torch.dtype, device: torch.device, *, with_grad: bool, halo: int = 0,
                  split: bool = False, switches: Switches | None = None, fuse_first_gram: bool = True,
-                 assume_device: bool = False) -> None:
+                 assume_device: bool = False, guide: int = 0) -> None:
         """``halo`` = 1: the schedule of one ROW STRIP of a larger image (spatial.py).  ``H`` is the
         strip's own row count; every activation (and the image) carries ``halo`` extra rows above and
         below that the owner fills before each 3x3 convolution reads them (neighbour's rows, or zeros
@@ -174,8 +182,14 @@ class Schedule:
         strip's own rows only (strip heights are multiples of 16, so no window straddles two strips).
         ``fuse_first_gram=False``: the Gram of a tapped first layer runs over a sub-range of its buffer
         (spatial.SpatialShard), so the first-layer kernel must not leave slabs of the whole map.
-        ``assume_device``: take the decisions of a GPU schedule on host tensors - to be inspected, never run."""
+        ``assume_device``: take the decisions of a GPU schedule on host tensors - to be inspected, never run.
+        ``guide`` > 0: spatial guidance with that many active regions - every style tap runs one Gram chain per region
+        (``attach_regions`` hands it the label maps), so the two fusions that assume one Gram per tap are off."""
         self.H, self.W, self.dtype, self.device = H, W, dtype, device
+        if guide and halo:
+            msg = "spatial guidance (masks) runs on whole images only (no row strips)"
+            raise ValueError(msg)
+        self.guide = int(guide)
         if split and (dtype != torch.float32 or halo):
             msg = "bf16x3 (split-bf16 products) runs on fp32 storage and whole images only (no row strips)"
             raise ValueError(msg)
@@ -307,7 +321,7 @@ class Schedule:
             # a tapped first layer leaves the Gram slabs of its own output (no second pass over the map).
             # One slab per workgroup: pays once a workgroup walks >= 4 tiles of 8 x 32 pixels (1024^2: 8,
             # -11 us; at 512^2, 2 tiles each, the slab reduction costs what the separate pass did)
-            if (nd.kind == "conv_first" and tap is not None and whole and fuse_first_gram and sw.fuse_gram_first
+            if (nd.kind == "conv_first" and tap is not None and whole and fuse_first_gram and sw.fuse_gram_first and not self.guide
                     and ops.conv_first_gram_supported(d.H, d.W, nd.cin, d.C, self.dtype)
                     and (sw.fuse_gram_first == 2 or d.H * d.W >= 4 * 256 * ops.gram_ksplit(d.H * d.W, d.C))):
                 tap.partials_fused = True
@@ -341,7 +355,8 @@ class Schedule:
             # A Gram tap on the pre-ReLU output s: its gradient term F.S lands on the same buffer
             # as this dgrad.  One launch computes mask * dgrad + F.S (stv_conv_igemm_dual) instead
             # of a second launch that re-reads and re-writes s.grad.
-            if sw.fuse_gram and not (s.relu_fused and s.taps) and s.C % (32 // s.act.element_size()) == 0:
+            # (a guided tap has one term per region, each on a slab of its own: they stay 1x1 products)
+            if sw.fuse_gram and not self.guide and not (s.relu_fused and s.taps) and s.C % (32 // s.act.element_size()) == 0:
                 nd.gram = next((t for t in s.taps if t.kind == "style"), None)
             # s is a pooled map (arg-max byte map available, nothing else contributes to its gradient):
             # the dgrad's epilogue routes straight into the pre-pool gradient - no pooled-resolution
@@ -398,6 +413,40 @@ class Schedule:
             b = tap.buf
             tap.partials = torch.empty(ops.gram_ksplit(b.H * b.W, b.C), b.C, b.C, device=self.device, dtype=torch.float32)
         return tap.partials
+
+    def attach_regions(self, maps: list[torch.Tensor], counts: list[list[int]]) -> None:
+        """Spatial guidance: hand every style tap its label map (uint8 ``[H_l, W_l]``, values ``< guide`` or 255) and the
+        pixel counts ``n_{l,r}`` of its regions (all > 0: guidance.check_counts).  The tap gets the slabs ``[Ra, H, W, C]``
+        ``stv_mask_split`` fills and one child tap per region, ``order = l * Ra + r``, with the parent's placement."""
+        if not self.guide or len(maps) != len(self.style_taps) or len(counts) != len(maps):
+            msg = f"{len(maps)} label maps for {len(self.style_taps)} style taps of a schedule with {self.guide} regions"
+            raise ValueError(msg)
+        for tap, m, row in zip(self.style_taps, maps, counts, strict=True):
+            b = tap.buf
+            if tuple(m.shape) != (b.H, b.W) or m.dtype != torch.uint8 or len(row) != self.guide or min(row) < 1:
+                msg = f"label map {tuple(m.shape)} {m.dtype} with counts {row} for a {b.H}x{b.W} style tap, {self.guide} regions"
+                raise ValueError(msg)
+            tap.labels = m.to(self.device).contiguous()
+            tap.slabs = torch.empty(self.guide, b.H, b.W, b.C, device=self.device, dtype=self.dtype)
+            tap.regions = [Tap("style", tap.order * self.guide + r, Buf(b.H, b.W, b.C, tap.slabs[r]), in_tail=tap.in_tail,
+                               finish_late=tap.finish_late, norm=float(b.C * n), parent=tap) for r, n in enumerate(row)]
+
+    def chains(self, tap: Tap) -> list[Tap]:
+        """The taps that carry the Gram chains of style tap ``tap``: its regions under guidance, else the tap itself."""
+        if self.guide:
+            if tap.regions is None:
+                msg = "internal: guided schedule without label maps (attach_regions)"
+                raise RuntimeError(msg)
+            return tap.regions
+        return [tap]
+
+    def all_chains(self) -> list[Tap]:
+        return [c for tap in self.style_taps for c in self.chains(tap)]
+
+    def mask_split_op(self, tap: Tap) -> StvOp:
+        """The split of a guided style tap's activation into its region slabs (stv_mask_split)."""
+        b = tap.buf
+        return self.emit(op=OP_MASK_SPLIT, p0=b.act, p1=tap.labels, q0=tap.slabs, n=b.H * b.W, cin=b.C, cout=self.guide)
 
     # ------------------------------------------------------------------ op emission
     def emit(self, **kw) -> StvOp:
@@ -457,7 +506,7 @@ class Schedule:
         if not finish:          # (the finish pass runs later, in a batched launch: gram_multi_op with partials_ready)
             return out
         out.append(self.emit(op=OP_GRAM_FINISH, p0=self._partials(tap), p1=target, p2=coef_dev, q0=gram_out, q1=loss_part,
-                             q2=sgrad, n=n, cin=b.C, f0=GRAM_CLAMP_MAX, f1=float(b.C * n), f2=coef))
+                             q2=sgrad, n=n, cin=b.C, f0=GRAM_CLAMP_MAX, f1=float(b.C * n) if tap.norm is None else tap.norm, f2=coef))
         return out
 
     def gram_multi_op(self, specs: list[dict]) -> StvOp:
@@ -474,7 +523,7 @@ class Schedule:
         for e, sp in zip(table, specs, strict=True):
             tap = sp["tap"]
             b = tap.buf
-            e.fill(n_pixels=b.H * b.W, channels=b.C, clamp_max=GRAM_CLAMP_MAX, coef=sp.get("coef", 0.0),
+            e.fill(n_pixels=b.H * b.W, channels=b.C, clamp_max=GRAM_CLAMP_MAX, coef=sp.get("coef", 0.0), norm=tap.norm,
                    F=None if (tap.partials_fused or sp.get("partials_ready")) else ptr(b.act), partials=ptr(self._partials(tap)),
                    **{k: ptr(sp.get(k)) for k in ("target", "gram_out", "loss_part", "sgrad", "coef_dev")})
         op = self.emit(op=OP_GRAM_MULTI, p0=ctypes.addressof(table), n=len(specs))
@@ -588,8 +637,10 @@ class Schedule:
                 if tap.kind == "style":
                     if tune:
                         ops.conv_tune(d.H, d.W, d.C, d.C, 1, self.dtype, split=self.split)
-                    out.append(self.emit(op=OP_CONV, p0=d.act, p1=tap.sgrad, q0=wr(d), H=d.H, W=d.W,
-                                         cin=d.C, cout=d.C, taps=1, flags=acc_flag(d)))
+                    for c in self.chains(tap):      # (guided: dF += F_r . S_r per region, x = the region's slab)
+                        out.append(self.emit(op=OP_CONV, p0=c.buf.act, p1=c.sgrad, q0=wr(d), H=d.H, W=d.W,
+                                             cin=d.C, cout=d.C, taps=1, flags=acc_flag(d)))
+                        written.add(id(d))
                 else:
                     cd = coef_dev[n_style + tap.order:] if coef_dev is not None else None
                     coef = content_coef[tap.order] if isinstance(content_coef, (list, tuple)) else content_coef

@@ -101,6 +101,34 @@ def _halvings(img: torch.Tensor, levels: int) -> list[torch.Tensor]:
     return chain[::-1]
 
 
+def level_labels(content_labels, style_labels, style_hw: tuple[int, int], levels: int, n_styles: int, oc) -> list | None:
+    """Per level, coarsest first, the keyword arguments of a guided level: (those of the model, those of ``set_targets``);
+    ``None`` without label maps.  The style's map is cropped by the slice the style image was cropped by; a level's maps
+    are resampled (``guidance.resample_labels``) from the maps of the next finer level - the stage in front of it."""
+    if content_labels is None and style_labels is None:
+        return None
+    if content_labels is None or style_labels is None:
+        msg = "content_labels and style_labels go together: one label map without the other"
+        raise ValueError(msg)
+    if n_styles != 1:
+        msg = f"spatial guidance takes one style image, got {n_styles} (masks with several style images are not built)"
+        raise ValueError(msg)
+    from . import guidance  # noqa: PLC0415
+    model_kw = {"guide_regions": guidance.check_regions(getattr(oc, "mask_regions", 2), minimum=2, what="mask_regions"),
+                "region_weights": getattr(oc, "region_weights", None)}
+    Hs, Ws = style_hw
+    chain = [(content_labels, style_labels[:Hs, :Ws].contiguous())]
+    for _ in range(levels - 1):
+        c, s = chain[-1]
+        chain.append((guidance.resample_labels(c, c.shape[0] // 2, c.shape[1] // 2),
+                      guidance.resample_labels(s, s.shape[0] // 2, s.shape[1] // 2)))
+    from . import synthetic  # noqa: PLC0415
+    for c, s in chain[::-1]:            # an active region that vanishes at a tap of some level: refused before the first launch
+        guidance.check_maps(guidance.make_guide(model_kw["guide_regions"], model_kw["region_weights"], c, s),
+                            synthetic.VGG19_CFG, oc.style_layers)
+    return [(model_kw, {"content_labels": c, "style_labels": s}) for c, s in chain[::-1]]
+
+
 def _merge_csv(target: Path, parts: list[tuple[Path, int]]) -> None:
     """One header and the levels' rows in order, ``step`` shifted by the steps before each level; removes the parts."""
     with target.open("w", newline="", encoding="utf-8") as out:
@@ -128,6 +156,8 @@ def run_pyramid(  # noqa: PLR0913
     gif_collector: optimization.FrameSink | None = None,
     seed: int | None = None,
     setup_lock=None,
+    content_labels: torch.Tensor | None = None,
+    style_labels: torch.Tensor | None = None,
 ) -> tuple[torch.Tensor, LossHistory, float]:
     """Run ``config.optimization.pyramid_levels`` levels, coarsest first; returns (image, history, elapsed) like
     ``OptimizationRunner.run``: the final level's image, the levels' histories concatenated per key, the seconds the
@@ -136,7 +166,9 @@ def run_pyramid(  # noqa: PLR0913
     ``video_writer`` / ``gif_collector`` exist to be refused.  ``seed``: seed the generators right before the coarsest
     level is built; ``setup_lock``: held while that happens and while any level's model is constructed (constructing one
     draws from the process-wide CPU generator) - ``main.style_transfer`` passes both, as it seeds under its lock in a
-    single-level run."""
+    single-level run.  ``content_labels`` / ``style_labels`` (both or neither; ``guidance.py``): the label maps of a guided
+    run at the full size - the style's is cropped by the style's slice, each level's map is resampled from the next finer
+    level's, and every level is a fresh guided model."""
     style_list = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
     crops = [_validate(content_img, img, config, video_writer, gif_collector) for img in style_list]
     levels = crops[0][0]
@@ -150,6 +182,7 @@ def run_pyramid(  # noqa: PLR0913
                         img.shape[-1], img.shape[-2], Ws, Hs, 1 << (levels - 1))
             style_list[i] = img[..., :Hs, :Ws]
     contents, per_style = _halvings(content_img, levels), [_halvings(img, levels) for img in style_list]
+    label_chain = level_labels(content_labels, style_labels, crops[0][1:], levels, len(style_list), oc)
     # level k's style: the tensor itself for one image (as always), the list of that level's images for a blend
     styles = per_style[0] if len(per_style) == 1 else [[chain[k] for chain in per_style] for k in range(levels)]
 
@@ -177,8 +210,10 @@ def run_pyramid(  # noqa: PLR0913
                 model = core_model.StyleContentModel(style_layers=oc.style_layers, content_layers=oc.content_layers,
                                                      precision=config.hardware.precision,
                                                      **style_mix.option_kwargs(oc, "style_layer_weights"),
-                                                     **core_model.lap_option_kwargs(oc)).to(device)
-                model.set_targets(styles[k], contents[k], **style_mix.option_kwargs(oc, "style_blend"))
+                                                     **core_model.lap_option_kwargs(oc),
+                                                     **(label_chain[k][0] if label_chain else {})).to(device)
+                model.set_targets(styles[k], contents[k], **style_mix.option_kwargs(oc, "style_blend"),
+                                  **(label_chain[k][1] if label_chain else {}))
                 if k == 0:
                     input_img = core_model.initialize_input(contents[0], oc.init_method)
                 else:

@@ -151,15 +151,24 @@ def _refuse_lap(lap_w: float) -> None:
         raise ValueError(msg)
 
 
+def _refuse_guidance(guide_regions: int) -> None:
+    """Spatial guidance (masks) is refused here as ``tv_w > 0`` is."""
+    if guide_regions:
+        msg = (f"spatial guidance (guide_regions = {guide_regions}, masks) is not available on the row-strip path: the label maps, "
+               "slabs and region counts of a strip and the all-reduced region Grams are not implemented; run the whole image")
+        raise ValueError(msg)
+
+
 class SpatialShard:
     """This rank's share of one image: buffers, the two programs around the all-reduce, Adam state."""
 
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
                  style_w: float, content_w: float, tv_w: float = 0.0,
-                 style_layer_weights: list[float] | None = None, lap_w: float = 0.0) -> None:
+                 style_layer_weights: list[float] | None = None, lap_w: float = 0.0, guide_regions: int = 0) -> None:
         _refuse_layer_weights(style_layer_weights)
         _refuse_lap(lap_w)
+        _refuse_guidance(guide_regions)
         if tv_w:
             msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
                    "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
@@ -271,9 +280,10 @@ class HaloShard:
     def __init__(self, layers: list[nn.Module], style_at: list[int], content_at: list[int],
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
                  style_w: float, content_w: float, group=None, split: bool = False, tv_w: float = 0.0,
-                 style_layer_weights: list[float] | None = None, lap_w: float = 0.0) -> None:
+                 style_layer_weights: list[float] | None = None, lap_w: float = 0.0, guide_regions: int = 0) -> None:
         _refuse_layer_weights(style_layer_weights)
         _refuse_lap(lap_w)
+        _refuse_guidance(guide_regions)
         if tv_w:
             msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
                    "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")

@@ -17,11 +17,14 @@ TensorList = list[torch.Tensor]
 
 @dataclass(slots=True)
 class InputPaths:
-    """Content and style image paths; ``extra_style_paths``: further style images, blended with the first (``style_mix.py``)."""
+    """Content and style image paths; ``extra_style_paths``: further style images, blended with the first (``style_mix.py``);
+    ``content_mask_path`` / ``style_mask_path``: the two masks of a guided run (``guidance.py``), both or neither."""
 
     content_path: str
     style_path: str
     extra_style_paths: tuple[str, ...] = ()
+    content_mask_path: str | None = None
+    style_mask_path: str | None = None
 
     @property
     def style_paths(self) -> tuple[str, ...]:
