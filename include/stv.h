@@ -202,6 +202,29 @@ int stv_conv_uses_ws(int H, int W, int cin, int cout, int taps, int dtype, int f
 int stv_maxpool_fwd(const void* x, void* y, int H, int W, int C, int dtype, void* stream);
 int stv_maxpool_bwd(const void* x, const void* dy, void* dx, int H, int W, int C,
                     int flags, int dtype, void* stream);
+/* ---- AvgPool2d(2,2) forward / backward (--pooling avg; Gatys et al. 2016 replace VGG's max pooling by the mean).  Since
+ *      version 113.  H, W: the un-pooled size; Hp = H / 2, Wp = W / 2 (floor: an odd last row / column takes no part).
+ *   forward, per channel, in fp32, every sum rounded on its own (no FMA contraction), in exactly this order:
+ *     y[i,j] = (((x[2i,2j] + x[2i,2j+1]) + x[2i+1,2j]) + x[2i+1,2j+1]) * 0.25f
+ *   rounded once to the storage type (bf16: to nearest even); with STV_RELU_IN each operand is max(0, x) first.  This is
+ *   what torch's CPU avg_pool2d computes, bit for bit, in fp32 and in bf16; the pairwise order (a+b)+(c+d) is not.
+ *   backward:  v = 0.25f * dy[y/2, x/2] for y < 2*Hp and x < 2*Wp, else 0;  with STV_MASK v = 0 where !(ref > 0)
+ *     (ref: the un-pooled activation, read only with STV_MASK);  dx = v, or with STV_ACCUM dx = dx + v - one fp32 sum,
+ *     rounded once to storage.  Without STV_ACCUM the rows and columns the floor drops are written +0 (as stv_maxpool_bwd
+ *     does); with it they are left as they are. ------------------------------------------------------------------------- */
+/* launch constants: a work item is 16 bytes of one pooled pixel's channels (forward) or of one 2x2 window's channels, odd
+ * tails included (backward); a pass of the capped grid covers STV_AVGPOOL_MAX_BLOCKS * STV_AVGPOOL_THREADS items.  Vector
+ * path: C * element size a multiple of 16 behind 16-byte aligned bases; otherwise a work item is one element (forward: of
+ * y, backward: of dx). */
+#define STV_AVGPOOL_THREADS 256
+#define STV_AVGPOOL_MAX_BLOCKS 2048
+/* x, ref, dx: NHWC [H][W][C]; y, dy: NHWC [Hp][Wp][C]; all in `dtype` storage (STV_F32 | STV_BF16; STV_BF16X3 is
+ * STV_ERR_ARG as for every op that forms no product - its storage is fp32).  flags: forward STV_RELU_IN; backward STV_MASK,
+ * STV_ACCUM.
+ * STV_ERR_ARG, before any HIP call: another dtype; a null pointer the mode needs (ref only with STV_MASK); H, W or C <= 0;
+ * H / 2 == 0 or W / 2 == 0; a tensor of 2 GiB or more; any other flag. */
+int stv_avgpool_fwd(const void* x, void* y, int H, int W, int C, int flags, int dtype, void* stream);
+int stv_avgpool_bwd(const void* ref, const void* dy, void* dx, int H, int W, int C, int flags, int dtype, void* stream);
 int stv_relu_fwd(const void* x, void* y, size_t n, int dtype, void* stream);
 /* dx (=|+=) (x > 0) * dy ; dx may alias dy */
 int stv_relu_bwd(const void* x, const void* dy, void* dx, size_t n, int flags,
@@ -521,7 +544,7 @@ enum {
   STV_OP_POOL_BWD, STV_OP_RELU_FWD, STV_OP_RELU_BWD, STV_OP_GRAM_PARTIAL,
   STV_OP_GRAM_FINISH, STV_OP_CONTENT_LOSS, STV_OP_CONTENT_GRAD, STV_OP_LOSS_COMBINE,
   STV_OP_MEMSET, STV_OP_GRAM_MULTI, STV_OP_LBFGS_STEP, STV_OP_LBFGS_ITER, STV_OP_TV,
-  STV_OP_LAP, STV_OP_MASK_SPLIT
+  STV_OP_LAP, STV_OP_MASK_SPLIT, STV_OP_AVGPOOL_FWD, STV_OP_AVGPOOL_BWD
 };
 /* Operands follow the direct entry points' argument order (inputs p0.., outputs q0..).
  * CONV_FIRST_FWD takes the stv_conv_first_pack buffer in p3 (p1 unused) and gram_partials, or NULL, in q1;
@@ -541,7 +564,10 @@ enum {
  * TV (since version 105) runs stv_tv: p0 = x, q0 = loss_part, q1 = dx, cin = C, H, W, f0 = coef, flags.
  * LAP (since version 111) runs stv_lap: p0 = x, p1 = target, q0 = cells, q1 = loss_part, q2 = dx, cin = C, H, W, cout = pool,
  * taps = mode, f0 = coef, flags.
- * MASK_SPLIT (since version 112) runs stv_mask_split: p0 = F, p1 = labels, q0 = out, n = n_pixels, cin = C, cout = R. */
+ * MASK_SPLIT (since version 112) runs stv_mask_split: p0 = F, p1 = labels, q0 = out, n = n_pixels, cin = C, cout = R.
+ * AVGPOOL_FWD (= 20, since version 113) runs stv_avgpool_fwd: p0 = x, q0 = y, H, W, cin = C, flags.
+ * AVGPOOL_BWD (= 21, since version 113) runs stv_avgpool_bwd: p0 = ref (or unset), p1 = dy, q0 = dx, H, W, cin = C, flags;
+ * the operand slots of POOL_FWD / POOL_BWD. */
 typedef struct {
   int32_t op, dtype, flags, taps;
   int32_t H, W, cin, cout;

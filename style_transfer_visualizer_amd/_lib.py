@@ -18,7 +18,7 @@ RELU_IN, RELU_OUT, MASK, ACCUM, W_BLOCKED, POOL_IDX, POOL_ROUTE, POOL_ONLY = 1, 
 
 (OP_CONV_FIRST_FWD, OP_CONV_FIRST_DGRAD, OP_CONV, OP_POOL_FWD, OP_POOL_BWD, OP_RELU_FWD,
  OP_RELU_BWD, OP_GRAM_PARTIAL, OP_GRAM_FINISH, OP_CONTENT_LOSS, OP_CONTENT_GRAD,
- OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER, OP_TV, OP_LAP, OP_MASK_SPLIT) = range(1, 20)
+ OP_LOSS_COMBINE, OP_MEMSET, OP_GRAM_MULTI, OP_LBFGS_STEP, OP_LBFGS_ITER, OP_TV, OP_LAP, OP_MASK_SPLIT, OP_AVGPOOL_FWD, OP_AVGPOOL_BWD) = range(1, 22)
 
 CONTENT_LOSS_PARTS = 256
 TV_LOSS_PARTS = 256       # stv.h STV_TV_LOSS_PARTS: one loss partial per workgroup of stv_tv, which is also its grid cap
@@ -36,6 +36,10 @@ LAP_THREADS, LAP_TILE_H, LAP_TILE_W, LAP_LOSS_PARTS, LAP_GRAD_MAX_BLOCKS, LAP_VE
 # launch constants of stv_mask_split (stv.h STV_MASK_*; csrc/guide.hip): at most MASK_MAX_REGIONS slabs, a work item is 16 bytes
 # of one pixel's channels, a pass of the capped grid covers MASK_SPLIT_MAX_BLOCKS * MASK_SPLIT_THREADS items
 MASK_MAX_REGIONS, MASK_SPLIT_THREADS, MASK_SPLIT_MAX_BLOCKS = 4, 256, 1024
+# launch constants of stv_avgpool_fwd / stv_avgpool_bwd (stv.h STV_AVGPOOL_*; csrc/avgpool.hip): a work item is 16 bytes of one
+# pooled pixel's (forward) or one 2x2 window's (backward, odd tails included) channels, a pass of the capped grid covers
+# AVGPOOL_MAX_BLOCKS * AVGPOOL_THREADS items
+AVGPOOL_THREADS, AVGPOOL_MAX_BLOCKS = 256, 2048
 RESIZE_DOWN2, RESIZE_UP2 = 0, 1                     # stv.h STV_RESIZE_*: the modes of stv_resize2x
 # launch constants of stv_resize2x (stv.h STV_RESIZE_THREADS, STV_RESIZE_MAX_BLOCKS; pixels per work item): a work item is
 # RESIZE_VEC consecutive OUTPUT pixels of one row, a pass of the capped grid covers RESIZE_MAX_BLOCKS * RESIZE_THREADS items
@@ -116,6 +120,8 @@ SIGNATURES = {
     "stv_conv_config": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "stv_maxpool_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "stv_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "stv_avgpool_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "stv_avgpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "stv_relu_fwd": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "stv_relu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "stv_gram_partial": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -81,6 +81,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
                      help="Regions of the two masks, 2 to 4 uniform grey bands (default: 2, black and white)")
     opt.add_argument("--region-weights", type=str,
                      help="Comma-separated weights of the regions (default: every region counts 1; 0 leaves a region unstyled)")
+    opt.add_argument("--pooling", choices=["max", "avg"], default=S,
+                     help="Pooling layers of the feature stack: max (VGG as trained, the default) or avg (the mean of each 2x2 window)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
     opt.add_argument("--init-method", choices=["random", "white", "content"], default=S, help="Initialization method")
     opt.add_argument("--seed", type=int, default=S, help="Random seed")
@@ -151,6 +153,8 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
         behind = "Total Variation Weight" if o.tv_w > 0 else "Content Weight"
         at = next(i for i, (label, _) in enumerate(rows) if label == behind) + 1
         rows[at:at] = [("Laplacian Weight", f"{o.lap_w:g}"), ("Laplacian Pool Sizes", ",".join(str(p) for p in o.lap_pools))]
+    if o.pooling != "max":
+        rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Content Layers") + 1, ("Pooling", o.pooling))
     if o.pyramid_levels > 1:
         at = next(i for i, (label, _) in enumerate(rows) if label == "Steps") + 1
         rows[at:at] = [("Pyramid Levels", o.pyramid_levels),

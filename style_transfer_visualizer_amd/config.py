@@ -10,7 +10,8 @@ additions are ``hardware.precision`` ("fp32" parity mode | "bf16" storage | "bf1
 the run, ``resize.py``; 0 = keep the file's size) and ``optimization.style_blend`` / ``style_layer_weights`` (blend weights of
 several style images, a weight per style layer, ``style_mix.py``; ``None`` = not set) and ``optimization.lap_w`` /
 ``lap_pools`` (weight and pool sizes of the Laplacian loss against the content image, 0 = off) and ``optimization.mask_regions``
-/ ``region_weights`` (regions of the two masks of a guided run and their weights, ``guidance.py``; read only with masks).
+/ ``region_weights`` (regions of the two masks of a guided run and their weights, ``guidance.py``; read only with masks) and
+``optimization.pooling`` ("max" | "avg": the pooling layers of the feature stack, "max" = VGG as trained).
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ from pydantic import BaseModel, Field, field_validator
 from . import config_defaults as d
 from .constants import VIDEO_QUALITY_MAX, VIDEO_QUALITY_MIN
 from .logging_utils import logger
-from .type_defs import InitMethod, Precision, PreserveColor, ResizeFilter, VideoMode
+from .type_defs import InitMethod, Pooling, Precision, PreserveColor, ResizeFilter, VideoMode
 
 
 class OptimizationConfig(BaseModel):
@@ -46,6 +47,7 @@ class OptimizationConfig(BaseModel):
     style_layer_weights: list[float] | None = d.DEFAULT_STYLE_LAYER_WEIGHTS
     mask_regions: int = Field(d.DEFAULT_MASK_REGIONS, ge=2, le=4)
     region_weights: list[float] | None = d.DEFAULT_REGION_WEIGHTS
+    pooling: Pooling = Field(d.DEFAULT_POOLING)
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
     seed: int = Field(d.DEFAULT_SEED, ge=0)
@@ -156,7 +158,7 @@ _DIRECT = {
     "output": ("output", "output"), "log_every": ("output", "log_every"), "log_loss": ("output", "log_loss"),
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
     "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lap_w": ("optimization", "lap_w"),
-    "mask_regions": ("optimization", "mask_regions"),
+    "mask_regions": ("optimization", "mask_regions"), "pooling": ("optimization", "pooling"),
     "lr": ("optimization", "lr"),
     "pyramid_levels": ("optimization", "pyramid_levels"), "preserve_color": ("optimization", "preserve_color"),
     "content_size": ("optimization", "content_size"), "style_size": ("optimization", "style_size"),

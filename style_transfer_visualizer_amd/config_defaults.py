@@ -19,6 +19,7 @@ DEFAULT_LAP_WEIGHT = 0.0     # build-specific: weight of the Laplacian loss agai
 DEFAULT_LAP_POOLS = [4]      # build-specific: its pool sizes (powers of two from 1 to 32, one to four of them)
 DEFAULT_MASK_REGIONS = 2     # build-specific: regions of --content-mask / --style-mask, 2 to 4 uniform grey bands
 DEFAULT_REGION_WEIGHTS = None  # build-specific: one weight per region (None = every region counts 1; 0 = left unstyled)
+DEFAULT_POOLING = "max"      # build-specific: pooling layers of the feature stack, "max" (VGG as trained) or "avg" (the mean)
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"
 DEFAULT_SEED = 0

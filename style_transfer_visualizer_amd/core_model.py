@@ -371,6 +371,29 @@ def initialize_vgg() -> nn.Module:
     return vgg
 
 
+POOLINGS = ("max", "avg")
+
+
+def check_pooling(pooling) -> str:
+    """The pooling kind of the feature stack, ``"max"`` (VGG as trained) or ``"avg"`` (Gatys et al.: the mean); any other
+    value is refused, with the value named."""
+    if not isinstance(pooling, str) or pooling not in POOLINGS:
+        msg = f"pooling must be one of {list(POOLINGS)}, got {pooling!r}"
+        raise ValueError(msg)
+    return pooling
+
+
+def replace_pooling(vgg: nn.Module, pooling: str) -> nn.Module:
+    """``pooling = "avg"``: a stack with every ``MaxPool2d`` of ``vgg`` replaced by ``AvgPool2d(2, 2)`` - the other modules
+    are shared, not copied (a cached stack stays as it is), indices keep their meaning, no parameter is added and no
+    generator draw is made; the new stack is in the mode (train / eval) of ``vgg``.  ``"max"``: ``vgg`` itself."""
+    if check_pooling(pooling) == "max":
+        return vgg
+    out = nn.Sequential(*[nn.AvgPool2d(kernel_size=2, stride=2) if isinstance(layer, nn.MaxPool2d) else layer
+                          for layer in vgg.children()])
+    return out.train(vgg.training)          # (the mode of the stack it stands in for: initialize_vgg() returns .eval())
+
+
 def create_feature_blocks(
     vgg: nn.Module,
     style_layers: list[int],
@@ -420,6 +443,8 @@ class _Engine:
                                    **({"guide": guide.n} if guide is not None else {}))
         s = self.sched
         self.guide = guide
+        # the pooling kind of the stack, part of every step's program key ("max": the key as it always was)
+        self.pooling = "avg" if any(nd.kind == "avgpool" for nd in s.nodes) else "max"
         self.n_style, self.n_content = len(s.style_taps), len(s.content_taps)
         if guide is not None:
             if tuple(guide.content_labels.shape) != (H, W):
@@ -812,6 +837,7 @@ class _Engine:
                None if then_step is None else then_step.key()) + ((("tv", tv_w),) if tv_w else ()) + (
                    (("layer_w", layer_w),) if layer_w is not None else ()) + (
                    (("lap", lap_w, self.lap_pools),) if lap_w else ()) + (
+                   (("pooling", self.pooling),) if self.pooling != "max" else ()) + (
                    (self.guide.key(),) if self.guide is not None else ())
 
         def build():
@@ -926,18 +952,23 @@ class StyleContentModel(nn.Module):
 
     def __init__(self, style_layers: list[int], content_layers: list[int], *,
                  precision: str | None = None, style_layer_weights: list[float] | None = None,
-                 lap_pools: tuple | list = (), guide_regions: int = 0, region_weights: list[float] | None = None) -> None:
-        """``guide_regions`` = R > 0 (1 to ``guidance.MAX_REGIONS``): spatial guidance - ``set_targets`` then takes one label map
+                 lap_pools: tuple | list = (), guide_regions: int = 0, region_weights: list[float] | None = None,
+                 pooling: str = "max") -> None:
+        """``pooling``: ``"max"`` - the stack ``initialize_vgg()`` returns, the model as it always was - or ``"avg"``: its
+        ``MaxPool2d`` modules replaced by ``AvgPool2d(2, 2)`` (``stv_avgpool_fwd`` / ``stv_avgpool_bwd`` as ops of their own in
+        the step; ``forward()`` runs the replaced modules through autograd as it runs the others).
+        ``guide_regions`` = R > 0 (1 to ``guidance.MAX_REGIONS``): spatial guidance - ``set_targets`` then takes one label map
         per image and the style term is ``sum_l w_l * sum_r lambda_r * loss_{l,r}`` with ``region_weights`` = lambda (default all
         1; a region of weight 0 is left unstyled).  0: no guidance, the model as it always was."""
         super().__init__()
+        self.pooling = check_pooling(pooling)        # (refusals before the stack is built)
         self._guide: guidance.Guide | None = None
         self.set_guidance(guide_regions, region_weights, _init=True)
         self.lap_pools = check_lap_pools(lap_pools)     # pool sizes of the Laplacian loss; empty: the term is not available
         self.lap_targets: list[torch.Tensor] | None = None
         self._style_layers_given = [int(v) for v in style_layers]
         self.style_layer_weights = style_layer_weights      # (refusals before the stack is built)
-        vgg = initialize_vgg()
+        vgg = replace_pooling(initialize_vgg(), self.pooling)
         self.vgg_blocks, self.content_ids, self.style_ids = create_feature_blocks(
             vgg, style_layers, content_layers)
         self.style_targets: list[torch.Tensor] | None = None
@@ -1007,6 +1038,10 @@ class StyleContentModel(nn.Module):
                    f"got {int(x.shape[1])} channels in shape {tuple(x.shape)}")
             raise RuntimeError(msg)
 
+    def _engine_key(self, H: int, W: int, index: int | None) -> tuple:
+        """What an engine of this model is kept under: size and device, and the pooling kind where it is not ``"max"``."""
+        return (H, W, index) + ((("pooling", self.pooling),) if self.pooling != "max" else ())
+
     def _engine_for(self, x: torch.Tensor) -> _Engine:
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             msg = ("StyleContentModel runs on the MI355X HIP kernels only: the image must be a GPU tensor "
@@ -1020,7 +1055,7 @@ class StyleContentModel(nn.Module):
             raise RuntimeError(msg)
         self._check_image(x)
         H, W = int(x.shape[-2]), int(x.shape[-1])
-        key = (H, W, x.device.index)
+        key = self._engine_key(H, W, x.device.index)
         eng = self._engines.get(key)
         if eng is None:
             eng = _Engine(self._layers(), self._style_at, self._content_at, H, W, self._dtype, x.device, split=self._split,
@@ -1046,7 +1081,7 @@ class StyleContentModel(nn.Module):
         self._guide = self._check_guidance(styles, content_img, content_labels, style_labels)
         if self._guide is not None and isinstance(content_img, torch.Tensor) and content_img.dim() == 4:
             # a guided engine is built from its label maps: new maps, a new engine
-            self._engines.pop((int(content_img.shape[-2]), int(content_img.shape[-1]), content_img.device.index), None)
+            self._engines.pop(self._engine_key(int(content_img.shape[-2]), int(content_img.shape[-1]), content_img.device.index), None)
         if self.lap_pools and isinstance(content_img, torch.Tensor) and content_img.dim() >= 2:
             check_lap_fits(self.lap_pools, int(content_img.shape[-2]), int(content_img.shape[-1]))
         eng = self._engine_for(content_img)
@@ -1194,6 +1229,13 @@ def lap_option_kwargs(optimization) -> dict:
     return {}
 
 
+def pooling_option_kwargs(optimization) -> dict:
+    """``{"pooling": "avg"}`` when ``optimization.pooling`` is ``"avg"``, else no keyword at all: a default run builds the
+    model exactly as before.  Any other value is refused, with the value named."""
+    pooling = check_pooling(getattr(optimization, "pooling", "max"))
+    return {"pooling": pooling} if pooling != "max" else {}
+
+
 def prepare_model_and_input(
     content_img: torch.Tensor,
     style_img: torch.Tensor | list[torch.Tensor],
@@ -1233,6 +1275,7 @@ def prepare_model_and_input(
         precision=precision,
         **style_mix.option_kwargs(optimization, "style_layer_weights"),
         **lap_option_kwargs(optimization),
+        **pooling_option_kwargs(optimization),
         **guide_kw,
     ).to(device)
     model.set_targets(style_img, content_img, **style_mix.option_kwargs(optimization, "style_blend"), **label_kw)

@@ -43,6 +43,10 @@ int run_op(const stv_op_t& o, void* st) {
       return stv_maxpool_fwd(o.p0, o.q0, o.H, o.W, o.cin, o.dtype, st);
     case STV_OP_POOL_BWD:
       return stv_maxpool_bwd(o.p0, o.p1, o.q0, o.H, o.W, o.cin, o.flags, o.dtype, st);
+    case STV_OP_AVGPOOL_FWD:
+      return stv_avgpool_fwd(o.p0, o.q0, o.H, o.W, o.cin, o.flags, o.dtype, st);
+    case STV_OP_AVGPOOL_BWD:  // p0 = ref (read with STV_MASK only), p1 = dy; q0 = dx
+      return stv_avgpool_bwd(o.p0, o.p1, o.q0, o.H, o.W, o.cin, o.flags, o.dtype, st);
     case STV_OP_RELU_FWD:
       return stv_relu_fwd(o.p0, o.q0, (size_t)o.n, o.dtype, st);
     case STV_OP_RELU_BWD:
@@ -124,7 +128,7 @@ int run_all(stv_program* p, void* st) {
 
 }  // namespace
 
-extern "C" int stv_version(void) { return 112; }
+extern "C" int stv_version(void) { return 113; }
 
 extern "C" int stv_program_create(const stv_op_t* ops, int n_ops, stv_program** out) {
   if (!ops || n_ops <= 0 || !out) return STV_ERR_ARG;

@@ -146,7 +146,7 @@ def tap_shapes(H: int, W: int, layers, style_at) -> list[tuple[int, int]]:
     if isinstance(layers, tuple):
         pools = [p for v in layers for p in ((True,) if v == "M" else (False, False))]
     else:
-        pools = [isinstance(layer, nn.MaxPool2d) for layer in layers]
+        pools = [isinstance(layer, (nn.MaxPool2d, nn.AvgPool2d)) for layer in layers]
     out, want = [], sorted(set(style_at))
     for i, is_pool in enumerate(pools):
         if is_pool:

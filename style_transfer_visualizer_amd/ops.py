@@ -325,6 +325,47 @@ def maxpool_bwd(x: torch.Tensor, dy: torch.Tensor, out: torch.Tensor | None = No
     return out
 
 
+def avgpool_fwd(x: torch.Tensor, out: torch.Tensor | None = None, relu_in: bool = False) -> torch.Tensor:
+    """``AvgPool2d(2, 2)`` of an NHWC map (``stv_avgpool_fwd``): ``(((a + b) + c) + d) * 0.25`` in fp32 over each window
+    in scan order, rounded once to storage; ``relu_in``: of ``max(0, x)``."""
+    H, W, C = x.shape
+    if out is None:
+        out = torch.empty(H // 2, W // 2, C, device=x.device, dtype=x.dtype)
+    elif tuple(out.shape) != (H // 2, W // 2, C) or out.dtype != x.dtype:
+        msg = f"avgpool_fwd: out is {tuple(out.shape)} {out.dtype}, expected {(H // 2, W // 2, C)} {x.dtype}"
+        raise RuntimeError(msg)
+    lib = _lib.load()
+    _lib.check(lib.stv_avgpool_fwd(_ptr(x), _ptr(out), H, W, C, RELU_IN if relu_in else 0, dtype_code(x.dtype), _stream()),
+               "stv_avgpool_fwd")
+    return out
+
+
+def avgpool_bwd(dy: torch.Tensor, H: int, W: int, ref: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                accumulate: bool = False) -> torch.Tensor:
+    """Backward of :func:`avgpool_fwd` (``stv_avgpool_bwd``; H, W: the un-pooled size): ``0.25 * dy`` to the four elements
+    of each window; ``ref`` (the un-pooled activation): zero where ``!(ref > 0)``; ``accumulate``: added onto ``out``, whose
+    rows and columns past the pooled range then keep their values (written as zeros otherwise)."""
+    C = int(dy.shape[-1])
+    shape = (int(H), int(W), C)
+    if tuple(dy.shape) != (H // 2, W // 2, C):
+        msg = f"avgpool_bwd: dy is {tuple(dy.shape)}, expected {(H // 2, W // 2, C)} for an un-pooled {H}x{W} map"
+        raise RuntimeError(msg)
+    if out is None:
+        if accumulate:
+            msg = "avgpool_bwd: accumulate=True needs the tensor to accumulate onto (out)"
+            raise RuntimeError(msg)
+        out = torch.empty(shape, device=dy.device, dtype=dy.dtype)
+    for name, t in (("out", out), ("ref", ref)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dy.dtype):
+            msg = f"avgpool_bwd: {name} is {tuple(t.shape)} {t.dtype}, expected {shape} {dy.dtype}"
+            raise RuntimeError(msg)
+    flags = (MASK if ref is not None else 0) | (ACCUM if accumulate else 0)
+    lib = _lib.load()
+    _lib.check(lib.stv_avgpool_bwd(_ptr(ref), _ptr(dy), _ptr(out), int(H), int(W), C, flags, dtype_code(dy.dtype), _stream()),
+               "stv_avgpool_bwd")
+    return out
+
+
 def relu_fwd(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     if out is None:
         out = torch.empty_like(x)

@@ -39,7 +39,7 @@ from torch import nn
 from . import _lib, ops
 from ._lib import (ACCUM, MASK, POOL_IDX, POOL_ONLY, POOL_ROUTE, W_BLOCKED, OP_GRAM_MULTI, OP_CONTENT_GRAD, OP_CONTENT_LOSS, OP_CONV, OP_CONV_FIRST_DGRAD,
                    OP_CONV_FIRST_FWD, OP_GRAM_FINISH, OP_GRAM_PARTIAL, OP_LOSS_COMBINE, OP_POOL_BWD,
-                   OP_MASK_SPLIT, OP_POOL_FWD, OP_RELU_BWD, OP_RELU_FWD, OP_TV, RELU_IN, RELU_OUT, StvOp)
+                   OP_AVGPOOL_BWD, OP_AVGPOOL_FWD, OP_MASK_SPLIT, OP_POOL_FWD, OP_RELU_BWD, OP_RELU_FWD, OP_TV, RELU_IN, RELU_OUT, StvOp)
 
 GRAM_CLAMP_MAX = 5e5  # reference constants.py:15
 
@@ -97,7 +97,11 @@ class Buf:
 
 @dataclass
 class Node:
-    kind: str                      # conv_first | conv | pool | relu
+    # conv_first | conv | pool | avgpool | relu.  An average pool is a kind of its own: every fusion below that tests for
+    # "pool" (the conv epilogue's pooled output, the arg-max byte map, the routed dgrad) is a max-pool fusion and stays off;
+    # an avgpool node is never `fused`, has no `idx`, is never a `route`, and its source map is always `stored`.
+    # Its `relu_in`: the node takes a pending ReLU itself (mean(relu(z)) != relu(mean(z)): it cannot be left to the consumer)
+    kind: str
     src: Buf | None
     dst: Buf
     relu_in: bool = False
@@ -158,6 +162,15 @@ def _check_layer(layer: nn.Module, idx: int) -> str:
             msg = f"layer {idx}: only MaxPool2d(2, 2) has a HIP kernel"
             raise RuntimeError(msg)
         return "pool"
+    if isinstance(layer, nn.AvgPool2d):
+        ks = layer.kernel_size if isinstance(layer.kernel_size, tuple) else (layer.kernel_size,) * 2
+        stv = layer.stride if isinstance(layer.stride, tuple) else (layer.stride,) * 2
+        pad = layer.padding if isinstance(layer.padding, tuple) else (layer.padding,) * 2
+        # (count_include_pad only matters with padding; a divisor_override would change the 0.25)
+        if ks != (2, 2) or stv != (2, 2) or pad != (0, 0) or layer.ceil_mode or layer.divisor_override is not None:
+            msg = f"layer {idx}: only AvgPool2d(2, 2) has a HIP kernel"
+            raise RuntimeError(msg)
+        return "avgpool"
     msg = f"layer {idx}: {type(layer).__name__} has no HIP kernel on this path"
     raise RuntimeError(msg)
 
@@ -279,16 +292,26 @@ class Schedule:
                     pending_relu = False
                 else:
                     pending_relu = True        # applied by the consumer while staging
-            else:  # pool
+            else:  # pool | avgpool
                 if cur is None:
-                    msg = "MaxPool directly on the input image is not supported"
+                    msg = f"{'AvgPool' if kind == 'avgpool' else 'MaxPool'} directly on the input image is not supported"
                     raise RuntimeError(msg)
+                if kind == "avgpool" and self.halo:
+                    msg = "average pooling (AvgPool2d) runs on whole images only (no row strips)"
+                    raise ValueError(msg)
                 H, W = H // 2, W // 2
                 if H < 1 or W < 1:
                     msg = "image too small for this many pooling layers"
                     raise RuntimeError(msg)
                 dst = self._new_buf(H, W, cur.C)
-                self.nodes.append(Node("pool", cur, dst, layer=i))
+                if kind == "avgpool":
+                    # relu(maxpool(z)) == maxpool(relu(z)) lets a max pool pass a pending ReLU on to its consumer; for the
+                    # mean that identity is false, so the node applies the ReLU itself (STV_RELU_IN) and nothing is pending
+                    # behind it
+                    self.nodes.append(Node("avgpool", cur, dst, relu_in=pending_relu, layer=i))
+                    pending_relu = False
+                else:
+                    self.nodes.append(Node("pool", cur, dst, layer=i))
                 cur = dst
                 if pending_relu and i in tapped:   # relu(pool(z)) must exist as data
                     r = self._new_buf(H, W, cur.C)
@@ -489,6 +512,9 @@ class Schedule:
             elif nd.kind == "pool":
                 src_i = self.interior(nd.src.act)
                 out.append(self.emit(op=OP_POOL_FWD, p0=src_i, q0=self.interior(d.act), H=src_i.shape[0], W=nd.src.W, cin=d.C))
+            elif nd.kind == "avgpool":
+                out.append(self.emit(op=OP_AVGPOOL_FWD, p0=nd.src.act, q0=d.act, H=nd.src.H, W=nd.src.W, cin=d.C,
+                                     flags=RELU_IN if nd.relu_in else 0))
             else:
                 out.append(self.emit(op=OP_RELU_FWD, p0=nd.src.act, q0=d.act, n=d.act.numel()))
             if after_node is not None:
@@ -687,6 +713,11 @@ class Schedule:
                     s_i = self.interior(s.act)
                     out.append(self.emit(op=OP_POOL_BWD, p0=s_i, p1=self.interior(rd(d)), q0=self.interior(wr(s)),
                                          H=s_i.shape[0], W=s.W, cin=s.C, flags=flags))
+            elif nd.kind == "avgpool":
+                # the ReLU mask where the max pool op gets it, and where the node took a pending ReLU itself (ref = z)
+                flags = (MASK if mask_src else 0) | acc_flag(s)
+                out.append(self.emit(op=OP_AVGPOOL_BWD, p0=s.act if mask_src else None, p1=rd(d), q0=wr(s), H=s.H, W=s.W,
+                                     cin=s.C, flags=flags))
             else:  # materialised relu
                 out.append(self.emit(op=OP_RELU_BWD, p0=s.act, p1=rd(d), q0=wr(s), n=s.act.numel(),
                                      flags=acc_flag(s)))

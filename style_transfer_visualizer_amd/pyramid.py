@@ -211,6 +211,7 @@ def run_pyramid(  # noqa: PLR0913
                                                      precision=config.hardware.precision,
                                                      **style_mix.option_kwargs(oc, "style_layer_weights"),
                                                      **core_model.lap_option_kwargs(oc),
+                                                     **core_model.pooling_option_kwargs(oc),
                                                      **(label_chain[k][0] if label_chain else {})).to(device)
                 model.set_targets(styles[k], contents[k], **style_mix.option_kwargs(oc, "style_blend"),
                                   **(label_chain[k][1] if label_chain else {}))

@@ -151,6 +151,14 @@ def _refuse_lap(lap_w: float) -> None:
         raise ValueError(msg)
 
 
+def _refuse_avgpool(layers) -> None:
+    """Average pooling (``pooling = "avg"``: a stack with ``AvgPool2d`` modules) is refused here as ``tv_w > 0`` is."""
+    if any(isinstance(layer, nn.AvgPool2d) for layer in layers):
+        msg = ("average pooling (pooling = 'avg') is not available on the row-strip path: the strips' pooling ops are the max-pool "
+               "kernels on their own rows; use pooling = 'max' here, or a whole image")
+        raise ValueError(msg)
+
+
 def _refuse_guidance(guide_regions: int) -> None:
     """Spatial guidance (masks) is refused here as ``tv_w > 0`` is."""
     if guide_regions:
@@ -169,6 +177,7 @@ class SpatialShard:
         _refuse_layer_weights(style_layer_weights)
         _refuse_lap(lap_w)
         _refuse_guidance(guide_regions)
+        _refuse_avgpool(layers)
         if tv_w:
             msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
                    "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
@@ -284,6 +293,7 @@ class HaloShard:
         _refuse_layer_weights(style_layer_weights)
         _refuse_lap(lap_w)
         _refuse_guidance(guide_regions)
+        _refuse_avgpool(layers)
         if tv_w:
             msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
                    "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")

@@ -11,6 +11,7 @@ VideoMode = Literal["realtime", "postprocess"]
 Precision = Literal["fp32", "bf16", "bf16x3"]
 PreserveColor = Literal["off", "match", "luma"]
 ResizeFilter = Literal["bilinear", "bicubic", "lanczos"]
+Pooling = Literal["max", "avg"]
 LossHistory = dict[str, list[float]]
 TensorList = list[torch.Tensor]
 
