@@ -408,6 +408,35 @@ int stv_color_affine(const float* x_nchw, float* y_nchw, const float* m12, int H
 int stv_luma_transfer(const float* result, const float* content, float* out, int H, int W, const float* mean3,
                       const float* std3, void* stream);
 
+/* ---- Automatic masks (--auto-mask; no counterpart in the reference): the assignment pass of a joint colour k-means over
+ *      the pooled content and style images, which gives the two label maps of a guided run.  Since version 114.  One launch
+ *      per image and iteration while the run is set up, none inside the step.  Per pixel p of x, NCHW fp32 [3][H][W]:
+ *   e_j  = x_j(p) - c_k[j]                          j = 0, 1, 2;  c: the K centroids
+ *   d_k  = ((e0*e0 + e1*e1) + e2*e2)                every difference, product and sum rounded to fp32 on its own (no FMA
+ *                                                   contraction): an fp32 twin reproduces every bit
+ *   label(p) = the first k, ascending, with d_k < the best so far, which starts at +inf (a strict `<`: the lowest index
+ *              wins a tie; a pixel whose every distance is NaN or +inf gets label 0)
+ *      Inputs are taken as finite.  A NaN distance never wins and nothing faults, but the sums are then meaningless. ---- */
+/* launch constants: a work item is four consecutive pixels of one row read from all three planes, as for the colour kernels
+ * (STV_COLOR_VEC), and their four labels; the kernel always launches STV_KMEANS_PARTS workgroups of STV_KMEANS_THREADS
+ * threads (one row of `parts` each: the constant is its grid and its grid cap), a stride loop over the items, so a pass
+ * covers STV_KMEANS_PARTS * STV_KMEANS_THREADS items.  Vector path (three 16-byte loads, one 32-bit load and store of the
+ * labels): W % 4 == 0 behind a 16-byte aligned x and 4-byte aligned labels; otherwise the same items with guarded scalar
+ * and byte accesses, same results in the same order. */
+#define STV_KMEANS_THREADS 256
+#define STV_KMEANS_PARTS 256
+#define STV_KMEANS_PART_DOUBLES 17
+/* centroids: fp32 [K][3] on the device, 1 <= K <= 4, uniform over the launch.  labels: uint8 [H][W] on the device; in: the
+ * labels of the previous iteration (any bytes before the first), out: the new ones - an item reads its four before it
+ * writes them and no other item touches them, so in place is the contract.  parts: double [STV_KMEANS_PARTS]
+ * [STV_KMEANS_PART_DOUBLES], one row per workgroup: for k < 4 at 4k .. 4k+3 the sums of x0, x1, x2 over the workgroup's
+ * pixels with label k and their number, at [16] the number of its pixels whose label changed.  Sums in double, fixed order -
+ * thread in item order, pixel by pixel, then wave, then workgroup -, no atomics; every entry is written on every launch,
+ * zeros for k >= K and for a workgroup without items.  The caller adds the rows (in float64, on the host).
+ * STV_ERR_ARG, before any HIP call: a null pointer, a non-positive dimension, K outside 1..4, 3*H*W*4 >= 2 GiB. */
+int stv_kmeans_assign(const float* x_nchw, const float* centroids, uint8_t* labels, double* parts, int H, int W, int K,
+                      void* stream);
+
 /* ---- Blended Gram targets (several style images with blend weights; no counterpart in the reference; jcjohnson's
  *      -style_blend_weights).  Since version 110.  One launch per style layer when targets are set, none inside the step.
  *   out[i] = (...((w[0]*G_0[i]) + w[1]*G_1[i]) + ...) + w[K-1]*G_{K-1}[i]      i < n

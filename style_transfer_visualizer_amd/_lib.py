@@ -51,6 +51,10 @@ RESIZE_AXIS_THREADS, RESIZE_AXIS_MAX_BLOCKS, RESIZE_AXIS_VEC = 256, 1024, 4
 # pixels of one row read from all three planes; stv_color_stats always runs COLOR_STATS_PARTS workgroups (one row of nine
 # doubles each), stv_color_affine and stv_luma_transfer at most COLOR_MAX_BLOCKS, all of COLOR_THREADS threads
 COLOR_VEC, COLOR_THREADS, COLOR_STATS_PARTS, COLOR_MAX_BLOCKS = 4, 256, 256, 1024
+# launch constants of stv_kmeans_assign (stv.h STV_KMEANS_*; csrc/kmeans.hip): the walk of the colour kernels, always
+# KMEANS_PARTS workgroups of KMEANS_THREADS threads, one row of KMEANS_PART_DOUBLES doubles each - for k < KMEANS_MAX_K at
+# 4k..4k+3 the sums of the three channels and the count of label k, at [16] the changed labels
+KMEANS_THREADS, KMEANS_PARTS, KMEANS_PART_DOUBLES, KMEANS_MAX_K = 256, 256, 17, 4
 # launch constants of stv_gram_blend (stv.h STV_BLEND_*; csrc/blend.hip): at most BLEND_MAX_TABLES tables per launch, a work
 # item is BLEND_VEC consecutive elements, a pass of the capped grid covers BLEND_MAX_BLOCKS * BLEND_THREADS items
 BLEND_MAX_TABLES, BLEND_VEC, BLEND_THREADS, BLEND_MAX_BLOCKS = 8, 4, 256, 128
@@ -138,6 +142,7 @@ SIGNATURES = {
     "stv_color_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "stv_color_affine": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int, c_void_p]),
     "stv_luma_transfer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),
+    "stv_kmeans_assign": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "stv_gram_blend": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int64, c_void_p]),
     "stv_image_to_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_void_p]),
     "stv_loss_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),

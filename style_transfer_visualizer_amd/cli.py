@@ -5,7 +5,7 @@ are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,b
 ``--pyramid-levels`` / ``--pyramid-steps``, ``--preserve-color {off,match,luma}``, ``--content-size`` / ``--style-size`` /
 ``--style-scale`` / ``--resize-filter {bilinear,bicubic,lanczos}``, ``--style-also`` / ``--style-blend`` /
 ``--style-layer-weights``, ``--lap-w`` / ``--lap-pool``, ``--content-mask`` / ``--style-mask`` / ``--mask-regions`` /
-``--region-weights`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
+``--region-weights``, ``--auto-mask`` / ``--auto-mask-cell`` / ``--save-masks`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
 """
 from __future__ import annotations
 
@@ -39,6 +39,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
     out.add_argument("--no-plot", action="store_true", help="Disable loss plotting")
     out.add_argument("--log-loss", type=str, help="CSV file for loss metrics (disables the loss plot)")
     out.add_argument("--log-every", type=int, default=DEFAULT_LOG_EVERY, help="Log losses every N steps")
+    out.add_argument("--save-masks", action="store_true",
+                     help="Write the two label maps of a guided run (from mask files or --auto-mask) as grey PNGs, at run size")
     out.add_argument("--compare-inputs", action="store_true", help="(not available in this build)")
     out.add_argument("--compare-result", action="store_true", help="(not available in this build)")
 
@@ -81,6 +83,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
                      help="Regions of the two masks, 2 to 4 uniform grey bands (default: 2, black and white)")
     opt.add_argument("--region-weights", type=str,
                      help="Comma-separated weights of the regions (default: every region counts 1; 0 leaves a region unstyled)")
+    opt.add_argument("--auto-mask", action="store_true",
+                     help="Spatial guidance without mask files: segment both images jointly into --mask-regions colour regions")
+    opt.add_argument("--auto-mask-cell", type=int, choices=[1, 2, 4, 8, 16, 32], default=S,
+                     help="Cell size of the --auto-mask segmentation in pixels (default: 8)")
     opt.add_argument("--pooling", choices=["max", "avg"], default=S,
                      help="Pooling layers of the feature stack: max (VGG as trained, the default) or avg (the mean of each 2x2 window)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
@@ -183,6 +189,11 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
         at = next(i for i, (label, _) in enumerate(rows) if label == "Style image loaded") + 1
         rows[at:at] = [("Content mask", paths.content_mask_path), ("Style mask", paths.style_mask_path),
                        ("Mask Regions", o.mask_regions), ("Region Weights", [float(w) for w in weights])]
+    if o.auto_mask:
+        at = next(i for i, (label, _) in enumerate(rows) if label == "Style image loaded") + 1
+        rows[at:at] = [("Automatic Masks", "Enabled"), ("Mask Regions", o.mask_regions), ("Automatic Mask Cell", o.auto_mask_cell)]
+    if cfg.output.save_masks:
+        rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Output Directory") + 1, ("Save Masks", "Yes"))
     for label, value in rows:
         logger.info("%s: %s", label, value)
 

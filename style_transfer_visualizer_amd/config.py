@@ -11,7 +11,9 @@ the run, ``resize.py``; 0 = keep the file's size) and ``optimization.style_blend
 several style images, a weight per style layer, ``style_mix.py``; ``None`` = not set) and ``optimization.lap_w`` /
 ``lap_pools`` (weight and pool sizes of the Laplacian loss against the content image, 0 = off) and ``optimization.mask_regions``
 / ``region_weights`` (regions of the two masks of a guided run and their weights, ``guidance.py``; read only with masks) and
-``optimization.pooling`` ("max" | "avg": the pooling layers of the feature stack, "max" = VGG as trained).
+``optimization.pooling`` ("max" | "avg": the pooling layers of the feature stack, "max" = VGG as trained) and
+``optimization.auto_mask`` / ``auto_mask_cell`` (the two label maps from a joint colour segmentation of the two images instead
+of mask files, and its cell size, ``segment.py``) and ``output.save_masks`` (write the label maps of a guided run as PNGs).
 """
 from __future__ import annotations
 
@@ -47,6 +49,8 @@ class OptimizationConfig(BaseModel):
     style_layer_weights: list[float] | None = d.DEFAULT_STYLE_LAYER_WEIGHTS
     mask_regions: int = Field(d.DEFAULT_MASK_REGIONS, ge=2, le=4)
     region_weights: list[float] | None = d.DEFAULT_REGION_WEIGHTS
+    auto_mask: bool = d.DEFAULT_AUTO_MASK
+    auto_mask_cell: int = Field(d.DEFAULT_AUTO_MASK_CELL)
     pooling: Pooling = Field(d.DEFAULT_POOLING)
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
@@ -63,6 +67,15 @@ class OptimizationConfig(BaseModel):
         allowed = (1, 2, 4, 8, 16, 32)
         if not 1 <= len(value) <= 4 or len(set(value)) != len(value) or any(v not in allowed for v in value):
             msg = f"lap_pools takes one to four different pool sizes out of {list(allowed)}, got {value}"
+            raise ValueError(msg)
+        return value
+
+    @field_validator("auto_mask_cell")
+    @classmethod
+    def _auto_mask_cell_allowed(cls, value: int) -> int:
+        allowed = (1, 2, 4, 8, 16, 32)
+        if value not in allowed:
+            msg = f"auto_mask_cell must be one of {list(allowed)}, got {value}"
             raise ValueError(msg)
         return value
 
@@ -102,6 +115,7 @@ class OutputConfig(BaseModel):
     log_every: int = Field(d.DEFAULT_LOG_EVERY, ge=1)
     log_loss: str | None = None
     plot_losses: bool = True
+    save_masks: bool = d.DEFAULT_SAVE_MASKS
 
 
 class StyleTransferConfig(BaseModel):
@@ -158,7 +172,8 @@ _DIRECT = {
     "output": ("output", "output"), "log_every": ("output", "log_every"), "log_loss": ("output", "log_loss"),
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
     "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lap_w": ("optimization", "lap_w"),
-    "mask_regions": ("optimization", "mask_regions"), "pooling": ("optimization", "pooling"),
+    "mask_regions": ("optimization", "mask_regions"), "auto_mask_cell": ("optimization", "auto_mask_cell"),
+    "pooling": ("optimization", "pooling"),
     "lr": ("optimization", "lr"),
     "pyramid_levels": ("optimization", "pyramid_levels"), "preserve_color": ("optimization", "preserve_color"),
     "content_size": ("optimization", "content_size"), "style_size": ("optimization", "style_size"),
@@ -176,6 +191,7 @@ _FLAGS = {
     "no_plot": ("output", "plot_losses", False), "no_normalize": ("optimization", "normalize", False),
     "no_video": ("video", "create_video", False), "no_intro": ("video", "intro_enabled", False),
     "final_only": ("video", "final_only", True),
+    "auto_mask": ("optimization", "auto_mask", True), "save_masks": ("output", "save_masks", True),
 }
 
 

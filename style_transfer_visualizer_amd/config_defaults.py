@@ -19,6 +19,8 @@ DEFAULT_LAP_WEIGHT = 0.0     # build-specific: weight of the Laplacian loss agai
 DEFAULT_LAP_POOLS = [4]      # build-specific: its pool sizes (powers of two from 1 to 32, one to four of them)
 DEFAULT_MASK_REGIONS = 2     # build-specific: regions of --content-mask / --style-mask, 2 to 4 uniform grey bands
 DEFAULT_REGION_WEIGHTS = None  # build-specific: one weight per region (None = every region counts 1; 0 = left unstyled)
+DEFAULT_AUTO_MASK = False    # build-specific: segment the two images into mask_regions colour regions instead of reading masks
+DEFAULT_AUTO_MASK_CELL = 8   # build-specific: cell size of that segmentation in pixels (1, 2, 4, 8, 16 or 32)
 DEFAULT_POOLING = "max"      # build-specific: pooling layers of the feature stack, "max" (VGG as trained) or "avg" (the mean)
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"
@@ -52,3 +54,4 @@ DEFAULT_PRECISION = "fp32"   # build-specific: "bf16" selects bf16 activation st
 # output
 DEFAULT_LOG_EVERY = 10
 DEFAULT_OUTPUT_DIR = "out"
+DEFAULT_SAVE_MASKS = False   # build-specific: write the two label maps of a guided run as grey PNGs into the output directory

@@ -9,6 +9,7 @@
 // operations: memory-bound where they are not launch-bound.  None of them runs inside the step.
 #include <hip/hip_runtime.h>
 
+#include "color_walk.h"
 #include "stv_common.h"
 
 namespace {
@@ -17,49 +18,6 @@ constexpr int kColorThreads = STV_COLOR_THREADS;
 constexpr int kColorStatsBlocks = STV_COLOR_STATS_PARTS;
 constexpr int kColorBlocks = STV_COLOR_MAX_BLOCKS;
 constexpr int kColorWaves = kColorThreads / STV_WAVE;
-
-// The four pixels of item i: px[c][k] = x[c][r][x0 + k], 0 where the row has ended (k >= nv).
-struct ColorItem { int r, x0, nv; };
-template <bool kVec>
-__device__ __forceinline__ ColorItem color_item(unsigned i, int W4, int W) {
-  ColorItem it;
-  it.r = (int)(i / (unsigned)W4);
-  it.x0 = (int)(i - (unsigned)it.r * (unsigned)W4) * 4;
-  it.nv = kVec ? 4 : (W - it.x0 < 4 ? W - it.x0 : 4);
-  return it;
-}
-template <bool kVec>
-__device__ __forceinline__ void color_load(const float* x, size_t plane, size_t at, int nv, float (&px)[3][4]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float* p = x + (size_t)c * plane + at;
-    if constexpr (kVec) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) px[c][k] = v[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) px[c][k] = k < nv ? p[k] : 0.0f;
-    }
-  }
-}
-template <bool kVec>
-__device__ __forceinline__ void color_store(float* y, size_t plane, size_t at, int nv, const float (&px)[3][4]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float* p = y + (size_t)c * plane + at;
-    if constexpr (kVec) {
-      f32x4 v;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = px[c][k];
-      *reinterpret_cast<f32x4*>(p) = v;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (k < nv) p[k] = px[c][k];
-    }
-  }
-}
 
 // ------------------------------------------------------------------ statistics
 // parts[blockIdx.x][0..8] = sum x0, x1, x2, x0x0, x0x1, x0x2, x1x1, x1x2, x2x2 over this workgroup's pixels.  Products
@@ -195,11 +153,6 @@ __global__ __launch_bounds__(kColorThreads) void luma_transfer_kernel(const floa
   }
 }
 
-// The shape check the three entry points share: positive sides and 3*H*W*4 bytes below 2 GiB.
-bool color_shape_ok(int H, int W) {
-  if (H <= 0 || W <= 0) return false;
-  return 3ull * (unsigned long long)H * (unsigned long long)W * 4ull < (1ull << 31);
-}
 // the byte ranges [a, a + bytes) and [b, b + bytes) share a byte
 bool ranges_overlap(const void* a, const void* b, size_t bytes) {
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;

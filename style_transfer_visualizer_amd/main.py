@@ -22,6 +22,11 @@ list is handed to the model, which blends the Gram targets.  With no extra style
 counterpart in the reference): the two masks are read and checked before the first launch, their label maps follow the images
 through the resize stage and through every level of a coarse-to-fine run, and the model is a guided one.  Without masks nothing
 here changes.
+
+``optimization.auto_mask`` / ``auto_mask_cell`` (``segment.py``, no counterpart in the reference): the two label maps come from a
+joint colour segmentation of the two images as the run sees them - behind the resize stage and the colour match, in front of
+the model - and are then handled as maps read from files are; a pair of images that does not split runs unguided.
+``output.save_masks`` writes the label maps of a guided run next to the result.  With the options off nothing here changes.
 """
 from __future__ import annotations
 
@@ -30,7 +35,7 @@ from pathlib import Path
 
 import torch
 
-from . import color, core_model, guidance, image_io, ops, optimization, pyramid, runtime, style_mix
+from . import color, core_model, guidance, image_io, ops, optimization, pyramid, runtime, segment, style_mix
 from . import resize as resize_rules
 from .logging_utils import logger
 from .type_defs import InputPaths, SaveOptions
@@ -93,6 +98,18 @@ def _load_masks(paths: InputPaths, oc) -> tuple[torch.Tensor, torch.Tensor] | No
     return maps[0], maps[1]
 
 
+def _check_save_masks(paths: InputPaths, guided: bool) -> None:
+    """``output.save_masks`` needs a guided run and two different file names."""
+    if not guided:
+        msg = "--save-masks without masks: give --content-mask and --style-mask, or --auto-mask"
+        raise ValueError(msg)
+    content_stem, style_stem = Path(paths.content_path).stem, Path(paths.style_path).stem
+    if content_stem == style_stem:
+        msg = (f"--save-masks: content image {paths.content_path!r} and style image {paths.style_path!r} share the stem "
+               f"{content_stem!r}, so both label maps would be written to {content_stem}_mask.png")
+        raise ValueError(msg)
+
+
 def _style_stem(paths: InputPaths) -> str:
     """The style part of the output names: the stems of the style images joined by ``+``."""
     return "+".join(Path(p).stem for p in (paths.style_path, *getattr(paths, "extra_style_paths", ())))
@@ -116,7 +133,11 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     if layer_weights is not None:
         style_mix.check_layer_weights(layer_weights, config.optimization.style_layers)
 
+    auto_mask = segment.check_options(paths, config.optimization)      # (refusals before the first launch)
     labels = _load_masks(paths, config.optimization)      # (refusals before the first launch)
+    save_masks = bool(getattr(config.output, "save_masks", False))
+    if save_masks:
+        _check_save_masks(paths, auto_mask or labels is not None)
 
     if config.video.final_only:                 # reference main.py:30-33
         config.video.create_video = False
@@ -145,6 +166,8 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     if preserve_color == "match":               # once per run, on the full-size images: a coarse-to-fine run halves the matched style
         style_img = color.match_style_to_content(style_img, content_img)
         extra_styles = [color.match_style_to_content(img, content_img) for img in extra_styles]
+    if auto_mask:                               # the images the run sees; None: no split that holds, the run is unguided
+        labels = segment.auto_guidance(content_img, style_img, oc, oc.pyramid_levels)
     if extra_styles:                            # (one style: the tensor itself, as always)
         style_img = [style_img, *extra_styles]
     label_kw = {"content_labels": labels[0], "style_labels": labels[1]} if labels is not None else {}
@@ -160,6 +183,11 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     if output_tag and config.output.log_loss:
         log_path = Path(config.output.log_loss)
         config.output.log_loss = str(log_path.with_name(log_path.stem + output_tag + log_path.suffix))
+
+    if save_masks and labels is not None:
+        for stem, lab in ((content_name, labels[0]), (Path(paths.style_path).stem, labels[1])):
+            segment.save_label_png(lab, oc.mask_regions, output_path / f"{stem}_mask.png")
+            logger.info("Label map saved to: %s", output_path / f"{stem}_mask.png")
 
     if coarse_to_fine:                          # (refuses frame sinks: frames would change size between levels)
         input_img, loss_metrics, elapsed = pyramid.run_pyramid(

@@ -599,6 +599,34 @@ def luma_transfer(result: torch.Tensor, content: torch.Tensor, *, mean: tuple | 
     return out
 
 
+# ---- automatic masks (--auto-mask) -------------------------------------------------
+
+def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor, labels: torch.Tensor, parts: torch.Tensor | None = None) -> torch.Tensor:
+    """One assignment pass of the colour k-means (``stv_kmeans_assign``) over a contiguous fp32 image ``[3, H, W]`` or
+    ``[1, 3, H, W]``: ``labels`` (uint8 ``[H, W]``, in place: the previous labels in, the new ones out) receive the index of
+    the nearest of the ``K`` <= ``KMEANS_MAX_K`` ``centroids`` (fp32 ``[K, 3]`` on the device; squared distance in fp32, the
+    lowest index wins a tie).  Returns ``parts``, float64 ``[KMEANS_PARTS, KMEANS_PART_DOUBLES]`` on the device (a new tensor
+    by default), one row per workgroup: per cluster the sums of the three channels and the count, then the number of labels
+    that changed; every entry is written.  The caller adds the rows."""
+    lib = _lib.load()
+    H, W = _color_image(x, "kmeans_assign")
+    if centroids.dtype != torch.float32 or centroids.dim() != 2 or centroids.shape[1] != 3 or not centroids.is_contiguous():   # noqa: PLR2004
+        msg = f"kmeans_assign: centroids are {tuple(centroids.shape)} {centroids.dtype}, expected a contiguous fp32 [K, 3]"
+        raise RuntimeError(msg)
+    if labels.dtype != torch.uint8 or tuple(labels.shape) != (H, W) or not labels.is_contiguous():
+        msg = f"kmeans_assign: labels are {tuple(labels.shape)} {labels.dtype}, expected a contiguous uint8 {(H, W)}"
+        raise RuntimeError(msg)
+    shape = (_lib.KMEANS_PARTS, _lib.KMEANS_PART_DOUBLES)
+    if parts is None:
+        parts = torch.empty(shape, dtype=torch.float64, device=x.device)
+    elif tuple(parts.shape) != shape or parts.dtype != torch.float64 or not parts.is_contiguous():
+        msg = f"kmeans_assign: parts is {tuple(parts.shape)} {parts.dtype}, expected a contiguous {shape} torch.float64"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_kmeans_assign(_ptr(x), _ptr(centroids), _ptr(labels), _ptr(parts), H, W, int(centroids.shape[0]), _stream()),
+               "stv_kmeans_assign")
+    return parts
+
+
 # ---- blended Gram targets (several style images) ------------------------------------
 
 def gram_blend(stack: torch.Tensor, weights, out: torch.Tensor | None = None) -> torch.Tensor:

@@ -101,6 +101,19 @@ def _halvings(img: torch.Tensor, levels: int) -> list[torch.Tensor]:
     return chain[::-1]
 
 
+def label_halvings(content_labels: torch.Tensor, style_labels: torch.Tensor, style_hw: tuple[int, int], levels: int) -> list:
+    """The two label maps at every level, FINEST first: the style's map cropped to ``style_hw`` (the slice the style image is
+    cropped by), then each level resampled (``guidance.resample_labels``) from the next finer one."""
+    from . import guidance  # noqa: PLC0415
+    Hs, Ws = style_hw
+    chain = [(content_labels, style_labels[:Hs, :Ws].contiguous())]
+    for _ in range(levels - 1):
+        c, s = chain[-1]
+        chain.append((guidance.resample_labels(c, c.shape[0] // 2, c.shape[1] // 2),
+                      guidance.resample_labels(s, s.shape[0] // 2, s.shape[1] // 2)))
+    return chain
+
+
 def level_labels(content_labels, style_labels, style_hw: tuple[int, int], levels: int, n_styles: int, oc) -> list | None:
     """Per level, coarsest first, the keyword arguments of a guided level: (those of the model, those of ``set_targets``);
     ``None`` without label maps.  The style's map is cropped by the slice the style image was cropped by; a level's maps
@@ -116,12 +129,7 @@ def level_labels(content_labels, style_labels, style_hw: tuple[int, int], levels
     from . import guidance  # noqa: PLC0415
     model_kw = {"guide_regions": guidance.check_regions(getattr(oc, "mask_regions", 2), minimum=2, what="mask_regions"),
                 "region_weights": getattr(oc, "region_weights", None)}
-    Hs, Ws = style_hw
-    chain = [(content_labels, style_labels[:Hs, :Ws].contiguous())]
-    for _ in range(levels - 1):
-        c, s = chain[-1]
-        chain.append((guidance.resample_labels(c, c.shape[0] // 2, c.shape[1] // 2),
-                      guidance.resample_labels(s, s.shape[0] // 2, s.shape[1] // 2)))
+    chain = label_halvings(content_labels, style_labels, style_hw, levels)
     from . import synthetic  # noqa: PLC0415
     for c, s in chain[::-1]:            # an active region that vanishes at a tap of some level: refused before the first launch
         guidance.check_maps(guidance.make_guide(model_kw["guide_regions"], model_kw["region_weights"], c, s),
