@@ -483,6 +483,40 @@ int stv_mask_split(const void* F, const uint8_t* labels, void* out, size_t n_pix
 int stv_image_to_u8(const float* x_nchw, uint8_t* out_hwc, int H, int W, const float* mean3,
                     const float* std3, int round, void* stream);
 
+/* ---- Timelapse GIF output (--gif; the reference encodes its timelapse on the host): the two device passes over the
+ *      captured frames, HWC uint8 [H][W][3] as stv_image_to_u8 (round = 0) writes them.  Since version 115.  One
+ *      stv_frame_hist launch per saved frame, behind its capture; one stv_gif_map launch per frame when the file is
+ *      written; none inside the step.  All arithmetic is integer and fixed to the bit.
+ *   stv_frame_hist:   hist[(r>>3)<<10 | (g>>3)<<5 | (b>>3)] += 1            for every pixel (r, g, b) of the frame
+ *   stv_gif_map, per pixel (y, x):
+ *     t      = B8[y & 7][x & 7]                     the 8x8 Bayer matrix, a permutation of 0..63:
+ *              B8[y][x] = OR over b = 0..2 of  (((x>>b)&1) ^ ((y>>b)&1)) << (2*(2-b)+1)  and  ((y>>b)&1) << (2*(2-b))
+ *              (row 0 starts 0, 32, 8, 40; row 1 starts 48, 16, 56, 24)
+ *     off    = ((2*t - 63) * spread) >> 7           arithmetic shift (floor); spread 0 = no dither, spread 16 gives -8..7
+ *     v[c]   = clamp(frame[y][x][c] + off, 0, 255)  the same offset for the three channels
+ *     index  = argmin_k  sum_c (v[c] - palette[k][c])^2     over k < n_colors, in int32; the lowest k wins a tie
+ *      The search is exact and brute force (no lookup table). ------------------------------------------------------- */
+/* launch constants: a frame is walked as a flat run of pixels, a work item is four consecutive pixels (12 bytes in, the
+ * map: 4 bytes out), a pass of the capped grid covers STV_GIF_MAX_BLOCKS * STV_GIF_THREADS items.  Vector path (three
+ * 32-bit loads, the map: one 32-bit store): a 4-byte aligned frame - and, for the map, a 4-byte aligned index plane -, for
+ * every item with four pixels; otherwise, and for the last n % 4 pixels, the same items with byte accesses and the same
+ * results.  Frame i of a packed store starts at byte i*H*W*3 and its index plane at byte i*H*W: aligned or not. */
+#define STV_GIF_THREADS 256
+#define STV_GIF_MAX_BLOCKS 2048
+#define STV_GIF_HIST_BINS 32768
+/* hist: uint32 [STV_GIF_HIST_BINS] on the device.  The kernel ACCUMULATES: the caller zeroes hist once and adds any number
+ * of frames.  No-return global atomic adds: integer adds commute, so - unlike the floating-point statistics kernels -
+ * the result depends neither on their order nor on how pixels are grouped into one add (a run of equal bins inside a work
+ * item, and a wave whose 256 pixels share one bin, are added at once: a constant frame does not queue on one counter).
+ * STV_ERR_ARG, before any HIP call: a null pointer, n_pixels == 0, n_pixels*3 >= 2 GiB. */
+int stv_frame_hist(const uint8_t* frame_hwc, size_t n_pixels, uint32_t* hist, void* stream);
+/* index_hw: uint8 [H][W] on the device, every byte written, sharing no byte with the frame.  palette: uint8 [n_colors][3]
+ * on the device, staged once per workgroup in LDS.
+ * STV_ERR_ARG, before any HIP call: a null pointer, H or W <= 0, n_colors outside 1..256, spread outside 0..64,
+ * H*W*3 >= 2 GiB. */
+int stv_gif_map(const uint8_t* frame_hwc, uint8_t* index_hw, int H, int W, const uint8_t* palette, int n_colors, int spread,
+                void* stream);
+
 /* ---- Score combine: torch.stack(losses).sum() and
  *      loss = style_w*style + content_w*content (optimization.py:298-312).
  *  table: int32 [n_terms][3] = {offset into parts, count, kind(0 style,1 content,2 extra)}

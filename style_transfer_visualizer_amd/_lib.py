@@ -58,6 +58,10 @@ KMEANS_THREADS, KMEANS_PARTS, KMEANS_PART_DOUBLES, KMEANS_MAX_K = 256, 256, 17, 
 # launch constants of stv_gram_blend (stv.h STV_BLEND_*; csrc/blend.hip): at most BLEND_MAX_TABLES tables per launch, a work
 # item is BLEND_VEC consecutive elements, a pass of the capped grid covers BLEND_MAX_BLOCKS * BLEND_THREADS items
 BLEND_MAX_TABLES, BLEND_VEC, BLEND_THREADS, BLEND_MAX_BLOCKS = 8, 4, 256, 128
+# launch constants of stv_frame_hist / stv_gif_map (stv.h STV_GIF_*; csrc/gif.hip): a work item is GIF_VEC consecutive pixels
+# of the flat frame, a pass of the capped grid covers GIF_MAX_BLOCKS * GIF_THREADS items; the histogram has GIF_HIST_BINS
+# 32-bit counters (five bits per channel)
+GIF_THREADS, GIF_MAX_BLOCKS, GIF_VEC, GIF_HIST_BINS = 256, 2048, 4, 32768
 
 _ERRORS = {1: "STV_ERR_ARG (unsupported shape / null pointer / dtype)",
            2: "STV_ERR_LAUNCH (HIP launch failed)", 3: "STV_ERR_ALLOC", 4: "STV_ERR_GRAPH"}
@@ -145,6 +149,8 @@ SIGNATURES = {
     "stv_kmeans_assign": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "stv_gram_blend": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int64, c_void_p]),
     "stv_image_to_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_void_p]),
+    "stv_frame_hist": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "stv_gif_map": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "stv_loss_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "stv_loss_combine_log": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                      c_int, c_void_p, c_void_p, c_void_p]),

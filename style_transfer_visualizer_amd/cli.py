@@ -112,6 +112,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     vid.add_argument("--no-gif", dest="create_gif", action="store_false", default=S)
     vid.add_argument("--gif-include-intro", dest="gif_include_intro", action="store_true", default=S)
     vid.add_argument("--gif-include-outro", dest="gif_include_outro", action="store_true", default=S)
+    vid.add_argument("--gif-colors", type=int, default=S,
+                     help="Entries of the timelapse GIF's one palette, 2 to 256 (default: 256)")
+    vid.add_argument("--gif-dither", choices=["none", "ordered"], default=S,
+                     help="Dither of the timelapse GIF: ordered (8x8 Bayer, the default) or none")
     vid.add_argument("--video-mode", choices=["realtime", "postprocess"], default=S)
 
     hw = p.add_argument_group("hardware")
@@ -192,6 +196,9 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
     if o.auto_mask:
         at = next(i for i, (label, _) in enumerate(rows) if label == "Style image loaded") + 1
         rows[at:at] = [("Automatic Masks", "Enabled"), ("Mask Regions", o.mask_regions), ("Automatic Mask Cell", o.auto_mask_cell)]
+    if v.create_gif:
+        at = next(i for i, (label, _) in enumerate(rows) if label == "GIF Outro Included") + 1
+        rows[at:at] = [("GIF Colors", v.gif_colors), ("GIF Dither", v.gif_dither)]
     if cfg.output.save_masks:
         rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Output Directory") + 1, ("Save Masks", "Yes"))
     for label, value in rows:

@@ -46,6 +46,8 @@ DEFAULT_VIDEO_MODE = "realtime"
 DEFAULT_CREATE_GIF = False
 DEFAULT_GIF_INCLUDE_INTRO = False
 DEFAULT_GIF_INCLUDE_OUTRO = False
+DEFAULT_GIF_COLORS = 256       # build-specific: entries of the timelapse GIF's one palette (2..256)
+DEFAULT_GIF_DITHER = "ordered" # build-specific: "ordered" (8x8 Bayer) or "none"
 
 # hardware
 DEFAULT_DEVICE = "cuda"

@@ -1,9 +1,16 @@
 """Top-level orchestration: the production caller of the hot path (reference main.py:20-167).
 
 validate -> seed -> device -> load images -> model/targets/optimizer -> run -> save PNG ->
-``input_img.detach().clamp(0, 1)``.  Timelapse video / GIF encoding is presentation and is not
+``input_img.detach().clamp(0, 1)``.  Timelapse video (MP4) encoding is presentation and is not
 part of this build: any ``FrameSink`` may be injected, otherwise video requests are downgraded
 with a warning and the run proceeds like ``--no-video``.
+
+``video.create_gif`` (``gif.py``): a GIF timelapse is built in.  On a GPU, without an injected ``gif_collector`` and outside a
+coarse-to-fine run, a ``gif.DeviceGifCollector`` captures the frames on the device and writes ``timelapse_{content}_x_{style}.gif``
+(the reference's name) with one global palette when the run is over; its budget refusal comes before the run's first kernel.
+The intro and outro segments of the reference's GIF need its gallery renderer, which is not built: the two flags are ignored
+with a warning.  An injected collector wins; on a CPU device and in a coarse-to-fine run the request is downgraded as a video
+request is.  With ``create_gif`` off nothing here changes.
 
 ``optimization.preserve_color`` (``color.py``, no counterpart in the reference) adds one stage at either end: "match"
 re-colours the style image right behind the loads, "luma" restores the content image's chrominance in the result right
@@ -36,6 +43,7 @@ from pathlib import Path
 import torch
 
 from . import color, core_model, guidance, image_io, ops, optimization, pyramid, runtime, segment, style_mix
+from . import gif as gif_output
 from . import resize as resize_rules
 from .logging_utils import logger
 from .type_defs import InputPaths, SaveOptions
@@ -143,18 +151,34 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
         config.video.create_video = False
         config.video.create_gif = False
         config.video.save_every = config.optimization.steps + 1
-    if (config.video.create_video and video_writer is None) or (config.video.create_gif and gif_collector is None):
+    device = runtime.setup_device(config.hardware.device)
+    # the built-in GIF collector keeps its frames on the device and needs one frame size: a GPU run at one level
+    builtin_gif = (config.video.create_gif and gif_collector is None and device.type == "cuda"
+                   and config.optimization.pyramid_levels == 1)
+    if (config.video.create_video and video_writer is None) or (config.video.create_gif and gif_collector is None and not builtin_gif):
         logger.warning("Timelapse encoding is not part of the MI355X build; continuing without video/GIF "
                        "(pass --no-video to silence this, or inject a frame sink).")
         config.video.create_video = video_writer is not None
-        config.video.create_gif = gif_collector is not None
+        config.video.create_gif = gif_collector is not None or builtin_gif
+    if builtin_gif:                             # refusals before the first launch: the palette size, the dither
+        gif_colors = gif_output.check_colors(getattr(config.video, "gif_colors", gif_output.MAX_COLORS))
+        gif_dither = getattr(config.video, "gif_dither", "ordered")
+        gif_output.dither_spread(gif_dither)
+        if config.video.gif_include_intro or config.video.gif_include_outro:
+            logger.warning("gif_include_intro / gif_include_outro are ignored: the intro and outro segments of the GIF timelapse "
+                           "are not built; the file holds the frames of the run.")
 
-    device = runtime.setup_device(config.hardware.device)
     normalize = config.optimization.normalize
     content_img = image_io.load_image_to_tensor(paths.content_path, device, normalize=normalize)
     style_img = image_io.load_image_to_tensor(paths.style_path, device, normalize=normalize)
     extra_styles = [image_io.load_image_to_tensor(path, device, normalize=normalize) for path in extra_paths]
     oc = config.optimization
+    gif_frames = oc.steps // config.video.save_every if builtin_gif else 0
+    if builtin_gif:                             # the run has the content's size: refuse a store over the budget before any kernel
+        run_hw = tuple(int(v) for v in content_img.shape[-2:])
+        if oc.content_size > 0 or oc.style_size > 0 or oc.style_scale > 0:
+            run_hw = resize_rules.plan_sizes(oc, run_hw, style_img.shape[-2:])[0] or run_hw
+        gif_output.check_budget(gif_frames, *run_hw)
     if oc.content_size > 0 or oc.style_size > 0 or oc.style_scale > 0:
         loaded_hw = tuple(int(v) for v in content_img.shape[-2:])
         content_img, style_img = _resize_inputs(content_img, style_img, oc)
@@ -189,6 +213,13 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
             segment.save_label_png(lab, oc.mask_regions, output_path / f"{stem}_mask.png")
             logger.info("Label map saved to: %s", output_path / f"{stem}_mask.png")
 
+    gif_name = None
+    if builtin_gif:
+        gif_name = f"timelapse_{content_name}_x_{_style_stem(paths)}{output_tag}.gif"
+        gif_collector = gif_output.DeviceGifCollector(
+            output_path / gif_name, config.video.fps, int(input_img.shape[-2]), int(input_img.shape[-1]), gif_frames,
+            colors=gif_colors, dither=gif_dither, device=device)
+
     if coarse_to_fine:                          # (refuses frame sinks: frames would change size between levels)
         input_img, loss_metrics, elapsed = pyramid.run_pyramid(
             content_img, style_img, device, config, video_writer=video_writer, gif_collector=gif_collector,
@@ -205,7 +236,7 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
 
     runtime.save_outputs(input_img, loss_metrics, output_path, elapsed, SaveOptions(
         content_name=content_name, style_name=style_name, normalize=normalize,
-        video_created=video_writer is not None, gif_created=gif_collector is not None,
+        video_created=video_writer is not None, gif_name=gif_name, gif_created=gif_collector is not None,
         plot_losses=config.output.plot_losses),
         **({"plot_name": f"loss_plot{output_tag}.png"} if output_tag else {}))      # (untagged: the reference's call, runtime/output.py:55)
     return input_img.detach().clamp(0, 1)

@@ -779,11 +779,58 @@ def image_to_u8(x: torch.Tensor, *, mean: tuple | list | None, std: tuple | list
     _, H, W = img.shape
     if out is None:
         out = torch.empty(H, W, 3, device=img.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous():      # (a slot of a frame store)
+        msg = f"image_to_u8: out is {tuple(out.shape)} {out.dtype}, expected a contiguous uint8 {(H, W, 3)}"
+        raise RuntimeError(msg)
     m3 = (ctypes.c_float * 3)(*mean) if mean is not None else None
     s3 = (ctypes.c_float * 3)(*std) if std is not None else None
     lib = _lib.load()
     _lib.check(lib.stv_image_to_u8(_ptr(img), _ptr(out), H, W, m3, s3, 1 if rounding else 0, _stream()),
                "stv_image_to_u8")
+    return out
+
+
+# ---- timelapse GIF (--gif) --------------------------------------------------------
+
+def _gif_frame(frame: torch.Tensor, what: str) -> tuple[int, int]:
+    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or not frame.is_contiguous():   # noqa: PLR2004
+        msg = f"{what} expects a contiguous uint8 frame [H, W, 3], got {tuple(frame.shape)} {frame.dtype}"
+        raise RuntimeError(msg)
+    return int(frame.shape[0]), int(frame.shape[1])
+
+
+def frame_hist(frame: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:
+    """Add the pixels of a contiguous uint8 frame ``[H, W, 3]`` to the colour histogram ``hist`` (``stv_frame_hist``): bin
+    ``(r>>3)<<10 | (g>>3)<<5 | (b>>3)`` counts one more per pixel.  ``hist``: ``GIF_HIST_BINS`` 32-bit counters on the
+    device, ``torch.int32`` holding the bits of unsigned counts; it is accumulated into, so the caller zeroes it once.
+    The frame may start at any byte (a slot of a packed store).  Returns ``hist``."""
+    lib = _lib.load()
+    H, W = _gif_frame(frame, "frame_hist")
+    if hist.dtype != torch.int32 or tuple(hist.shape) != (_lib.GIF_HIST_BINS,) or not hist.is_contiguous():
+        msg = f"frame_hist: hist is {tuple(hist.shape)} {hist.dtype}, expected a contiguous {(_lib.GIF_HIST_BINS,)} torch.int32"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_frame_hist(_ptr(frame), H * W, _ptr(hist), _stream()), "stv_frame_hist")
+    return hist
+
+
+def gif_map(frame: torch.Tensor, palette: torch.Tensor, spread: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Palette indices of a contiguous uint8 frame ``[H, W, 3]`` (``stv_gif_map``): per pixel the 8x8 Bayer offset
+    ``((2*B8[y&7][x&7] - 63) * spread) >> 7`` is added to the three channels, the sums are clamped to 0..255, and the index
+    of the nearest entry of ``palette`` (uint8 ``[n, 3]`` on the device, ``n`` <= 256; squared distance in integers, the
+    lowest index wins a tie) is written to ``out``, uint8 ``[H, W]`` (a new tensor by default).  ``spread`` 0..64, 0 = no
+    dither.  Frame and ``out`` may start at any byte.  Returns ``out``."""
+    lib = _lib.load()
+    H, W = _gif_frame(frame, "gif_map")
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 or not palette.is_contiguous():   # noqa: PLR2004
+        msg = f"gif_map: palette is {tuple(palette.shape)} {palette.dtype}, expected a contiguous uint8 [n, 3]"
+        raise RuntimeError(msg)
+    if out is None:
+        out = torch.empty(H, W, dtype=torch.uint8, device=frame.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or not out.is_contiguous():
+        msg = f"gif_map: out is {tuple(out.shape)} {out.dtype}, expected a contiguous uint8 {(H, W)}"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_gif_map(_ptr(frame), _ptr(out), H, W, _ptr(palette), int(palette.shape[0]), int(spread), _stream()),
+               "stv_gif_map")
     return out
 
 

@@ -402,6 +402,15 @@ class OptimizationRunner:
         if (not vc.save_every or step_idx % vc.save_every != 0
                 or (self.video_writer is None and self.gif_collector is None)):
             return
+        # a GIF sink that captures on the device (gif.DeviceGifCollector) takes the image itself: two launches, no host
+        # frame.  The host frame - one kernel and a blocking copy - is formed only for whoever else wants one.
+        device_gif = self.gif_collector is not None and callable(getattr(self.gif_collector, "append_device", None))
+        if device_gif:
+            with torch.no_grad():
+                self.gif_collector.append_device(self.input_img, normalize=self.config.optimization.normalize)
+            if self.video_writer is None and self.callbacks.on_video_frame is None:
+                self._update_progress_postfix(metrics)
+                return
         with torch.no_grad():
             frame = image_io.frame_uint8(self.input_img, normalize=self.config.optimization.normalize)
             if frame is None:
@@ -409,11 +418,11 @@ class OptimizationRunner:
         if self.intro_last_frame is not None and not self.intro_transition_done:
             if self.video_writer is not None and vc.intro_enabled:
                 append_crossfade(self.video_writer, self.intro_last_frame, frame, self.intro_crossfade_frames)
-            if self.gif_collector is not None and vc.gif_include_intro:
+            if self.gif_collector is not None and vc.gif_include_intro and not device_gif:
                 append_crossfade(self.gif_collector, self.intro_last_frame, frame, self.intro_crossfade_frames)
             self.intro_transition_done = True
             self.intro_last_frame = None
-        for sink in (self.video_writer, self.gif_collector):
+        for sink in (self.video_writer, None if device_gif else self.gif_collector):
             if sink is not None:
                 sink.append_data(frame)
         self._update_progress_postfix(metrics)

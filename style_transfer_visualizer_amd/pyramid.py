@@ -10,8 +10,8 @@ single-level run takes, and the image never visits the host between levels.
 Several style images (``style_mix.py``): ``style_img`` may be a list; each image is cropped and halved on its own, and each
 level's targets are blended from that level's images.
 
-Not built: frames (video / GIF) during such a run - their size would change between levels -, ratios other than two
-between levels, and row strips (``spatial.py``).
+Not built: frames (video / GIF) during such a run - their size would change between levels, so the built-in GIF collector
+(``gif.py``) is not created for one either -, ratios other than two between levels, and row strips (``spatial.py``).
 """
 from __future__ import annotations
 

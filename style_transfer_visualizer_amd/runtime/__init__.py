@@ -91,6 +91,10 @@ def save_outputs(input_img: torch.Tensor, loss_metrics: LossHistory, output_dir:
     image_io.save_image(input_img, final_path, normalize=opts.normalize)
     if opts.video_created and opts.video_name:
         logger.info("Video saved to: %s", output_dir / opts.video_name)
+    if opts.gif_created and opts.gif_name:
+        gif_path = output_dir / opts.gif_name
+        if gif_path.exists():
+            logger.info("GIF saved to: %s", gif_path)
     if opts.plot_losses and loss_metrics:
         try:
             import matplotlib
