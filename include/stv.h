@@ -517,6 +517,74 @@ int stv_frame_hist(const uint8_t* frame_hwc, size_t n_pixels, uint32_t* hist, vo
 int stv_gif_map(const uint8_t* frame_hwc, uint8_t* index_hw, int H, int W, const uint8_t* palette, int n_colors, int spread,
                 void* stream);
 
+/* ---- Motion-JPEG timelapse (--video-format mjpeg; the reference encodes H.264 through ffmpeg on the host): every saved
+ *      frame becomes one baseline JPEG, 4:2:0, Annex K Huffman tables (ITU T.81).  Since version 116.  One stv_jpeg_dct
+ *      launch per saved frame, behind its capture; stv_jpeg_block_bits, stv_jpeg_scan and stv_jpeg_emit run over all frames
+ *      when the file is written; none inside the step.  All arithmetic is integer and fixed to the bit.
+ *   MCU and edges: an MCU is 16x16 pixels, MCUs are row-major, mcu_w = (W+15)/16, mcu_h = (H+15)/16; the blocks of an MCU
+ *     are Y00 Y01 Y10 Y11 Cb Cr (Yrc: row r, column c of the 2x2 luminance blocks).  A pixel past the right or the bottom
+ *     edge is the last pixel of its row / the last row (coordinates clamped to W-1, H-1).
+ *   Colour, int32 per pixel (r, g, b):
+ *     Y  = ( 19595*r + 38470*g +  7471*b + 32768) >> 16
+ *     Cb = (-11059*r - 21709*g + 32768*b + 8388608 + 32767) >> 16
+ *     Cr = ( 32768*r - 27439*g -  5329*b + 8388608 + 32767) >> 16           all three in 0..255
+ *   Chroma sample (cy, cx) of an MCU: the Cb (Cr) values of pixels (2cy..2cy+1, 2cx..2cx+1), (sum + 2) >> 2.
+ *   Level shift: s = sample - 128.
+ *   DCT table: T[u][x] = rint(8192 * c(u)/2 * cos((2x+1) u pi / 16)), c(0) = 1/sqrt(2), c(u) = 1: STV_JPEG_DCT_TABLE.
+ *   Rows:    a[y][u] = sum_x T[u][x] * s[y][x];   a1 = (a + 128) >> 8        (arithmetic shift)
+ *   Columns: b[v][u] = sum_y T[v][y] * a1[y][u]                              (the coefficient times 2^18)
+ *     |a| <= 2965504, |a1| <= 11584, |b| <= 268378112: int32 throughout.
+ *   Quantisation with q = qtab[v*8 + u] (table 0 for Y, table 1 for Cb and Cr; row-major, v the vertical frequency):
+ *     d = q << 18;  c = sign(b) * ((|b| + (d >> 1)) / d)                     (round half away from zero)
+ *     c is clamped to -1023..1023, the DC (v = u = 0) to -1024..1023, and stored as int16 at the zigzag position of (v, u).
+ *   Entropy code of a block (baseline Huffman, class 0 tables for Y, class 1 for Cb and Cr): the DC difference against
+ *     the previous block of the same component in scan order (0 in front of a frame's first): the code of its category
+ *     (bit length of its magnitude, 0..11), then that many value bits (v for v > 0, the low bits of v - 1 for v < 0);
+ *     every non-zero AC coefficient as the code of (run << 4 | category) and its value bits, a run of 16 or more zeros in
+ *     front of it as one ZRL (0xF0) per 16; an EOB (0x00) unless coefficient 63 is non-zero.  Bits are MSB first.  The
+ *     last block of a frame pads the stream to a byte with 1-bits.  0xFF stuffing is left to the host. ------------------ */
+#define STV_JPEG_DCT_TABLE                                        \
+  {{2896, 2896, 2896, 2896, 2896, 2896, 2896, 2896},              \
+   {4017, 3406, 2276, 799, -799, -2276, -3406, -4017},            \
+   {3784, 1567, -1567, -3784, -3784, -1567, 1567, 3784},          \
+   {3406, -799, -4017, -2276, 2276, 4017, 799, -3406},            \
+   {2896, -2896, -2896, 2896, 2896, -2896, -2896, 2896},          \
+   {2276, -4017, 799, 3406, -3406, -799, 4017, -2276},            \
+   {1567, -3784, 3784, -1567, -1567, 3784, -3784, 1567},          \
+   {799, -2276, 3406, -4017, 4017, -3406, 2276, -799}}
+/* launch constants: stv_jpeg_dct runs workgroups of STV_JPEG_DCT_THREADS, 8 lanes per 8x8 block (a lane is one row of the
+ * block in the row pass and one column in the column pass, LDS in between), one workgroup per 32 blocks; the three entropy
+ * kernels run workgroups of STV_JPEG_THREADS, a work item one block (stv_jpeg_scan: one workgroup per frame).  A block's
+ * code is at most STV_JPEG_MAX_BLOCK_BITS long (DC 11 + 11, 63 AC of 16 + 10, rounded up to 32), and bit offsets are 32
+ * bits wide: a frame has fewer than 2^32 / STV_JPEG_MAX_BLOCK_BITS blocks. */
+#define STV_JPEG_DCT_THREADS 256
+#define STV_JPEG_THREADS 256
+#define STV_JPEG_MAX_BLOCK_BITS 1664
+#define STV_JPEG_MAX_DIM 65535
+/* frame_hwc: uint8 [H][W][3] on the device, at any byte address (32-bit loads where a row of a block is 4-byte aligned and
+ * inside the frame, byte loads elsewhere: the same results).  qtabs: HOST array of 128 ints, table 0 then table 1, row-major,
+ * passed by value into the launch.  coef: int16 [mcu_h*mcu_w*6][64] on the device, 16-byte aligned, every element written
+ * (16-byte stores).  STV_ERR_ARG, before any HIP call: a null pointer, H or W outside 1..STV_JPEG_MAX_DIM, a table entry
+ * outside 1..255, a misaligned coef. */
+int stv_jpeg_dct(const uint8_t* frame_hwc, const int* qtabs, int H, int W, int16_t* coef, void* stream);
+/* coef: int16 [n_frames][blocks_per_frame][64], 16-byte aligned; bits: uint32 [n_frames][blocks_per_frame], the length of
+ * each block's code in bits (without the padding of a frame's last block).  blocks_per_frame: a multiple of 6.
+ * STV_ERR_ARG, before any HIP call: a null pointer, n_frames or blocks_per_frame <= 0, blocks_per_frame no multiple of 6 or
+ * >= 2^32 / STV_JPEG_MAX_BLOCK_BITS, n_frames * blocks_per_frame >= 2^31, a misaligned coef. */
+int stv_jpeg_block_bits(const int16_t* coef, int n_frames, int blocks_per_frame, uint32_t* bits, void* stream);
+/* offsets[f][b] = bits[f][0] + ... + bits[f][b-1] (an exclusive prefix sum per frame), totals[f] = the sum of frame f.
+ * One workgroup per frame; integer sums, so the result does not depend on how the sum is split.  STV_ERR_ARG as above. */
+int stv_jpeg_scan(const uint32_t* bits, int n_frames, int blocks_per_frame, uint32_t* offsets, uint32_t* totals, void* stream);
+/* Writes the code of every block at bit offsets[f][b] of frame f's stream, which starts at byte base[f] of `stream_bytes`
+ * (base: uint32 [n_frames] on the device, multiples of 4).  `stream_bytes`: capacity bytes on the device, 4-byte aligned,
+ * capacity a multiple of 4, ZEROED by the caller; frame f occupies ((totals[f] + 7) / 8) bytes from base[f], and the caller
+ * leaves at least that, rounded up to 4, between two bases.  The stream is written as big-endian 32-bit words: a word a
+ * block shares with a neighbour (its first and its last) is combined with a vector atomic OR, a word it owns is stored.
+ * Integer OR commutes, so the bytes do not depend on any order.  No word at or past `capacity` is touched.
+ * STV_ERR_ARG, before any HIP call: as stv_jpeg_block_bits, and capacity == 0, capacity % 4 != 0 or capacity >= 2^32, a misaligned stream. */
+int stv_jpeg_emit(const int16_t* coef, const uint32_t* offsets, const uint32_t* base, int n_frames, int blocks_per_frame,
+                  uint8_t* stream_bytes, size_t capacity, void* stream);
+
 /* ---- Score combine: torch.stack(losses).sum() and
  *      loss = style_w*style + content_w*content (optimization.py:298-312).
  *  table: int32 [n_terms][3] = {offset into parts, count, kind(0 style,1 content,2 extra)}

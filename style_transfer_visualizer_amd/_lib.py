@@ -62,6 +62,21 @@ BLEND_MAX_TABLES, BLEND_VEC, BLEND_THREADS, BLEND_MAX_BLOCKS = 8, 4, 256, 128
 # of the flat frame, a pass of the capped grid covers GIF_MAX_BLOCKS * GIF_THREADS items; the histogram has GIF_HIST_BINS
 # 32-bit counters (five bits per channel)
 GIF_THREADS, GIF_MAX_BLOCKS, GIF_VEC, GIF_HIST_BINS = 256, 2048, 4, 32768
+# constants of the four JPEG kernels (stv.h STV_JPEG_*; csrc/jpeg.hip): stv_jpeg_dct runs workgroups of JPEG_DCT_THREADS, eight
+# lanes per 8x8 block; the entropy kernels workgroups of JPEG_THREADS, a work item one block; a block's code has at most
+# JPEG_MAX_BLOCK_BITS bits and bit offsets are 32 bits wide; a frame side is at most JPEG_MAX_DIM; JPEG_DCT_TABLE is
+# T[u][x] = rint(8192 * c(u)/2 * cos((2x+1) u pi / 16)) as the header spells it
+JPEG_DCT_THREADS, JPEG_THREADS, JPEG_MAX_BLOCK_BITS, JPEG_MAX_DIM = 256, 256, 1664, 65535
+JPEG_DCT_TABLE = (
+    (2896, 2896, 2896, 2896, 2896, 2896, 2896, 2896),
+    (4017, 3406, 2276, 799, -799, -2276, -3406, -4017),
+    (3784, 1567, -1567, -3784, -3784, -1567, 1567, 3784),
+    (3406, -799, -4017, -2276, 2276, 4017, 799, -3406),
+    (2896, -2896, -2896, 2896, 2896, -2896, -2896, 2896),
+    (2276, -4017, 799, 3406, -3406, -799, 4017, -2276),
+    (1567, -3784, 3784, -1567, -1567, 3784, -3784, 1567),
+    (799, -2276, 3406, -4017, 4017, -3406, 2276, -799),
+)
 
 _ERRORS = {1: "STV_ERR_ARG (unsupported shape / null pointer / dtype)",
            2: "STV_ERR_LAUNCH (HIP launch failed)", 3: "STV_ERR_ALLOC", 4: "STV_ERR_GRAPH"}
@@ -151,6 +166,10 @@ SIGNATURES = {
     "stv_image_to_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_void_p]),
     "stv_frame_hist": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
     "stv_gif_map": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "stv_jpeg_dct": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_void_p]),
+    "stv_jpeg_block_bits": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "stv_jpeg_scan": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "stv_jpeg_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "stv_loss_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "stv_loss_combine_log": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                      c_int, c_void_p, c_void_p, c_void_p]),

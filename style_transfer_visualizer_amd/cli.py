@@ -117,6 +117,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
     vid.add_argument("--gif-dither", choices=["none", "ordered"], default=S,
                      help="Dither of the timelapse GIF: ordered (8x8 Bayer, the default) or none")
     vid.add_argument("--video-mode", choices=["realtime", "postprocess"], default=S)
+    vid.add_argument("--video-format", choices=["mp4", "mjpeg"], default=S,
+                     help="Timelapse video: mp4 (the default; not encoded by this build) or mjpeg (Motion-JPEG in an AVI file, built in)")
 
     hw = p.add_argument_group("hardware")
     hw.add_argument("--device", type=str, default=S, help="Device to run on (cuda = MI355X under ROCm)")
@@ -199,6 +201,8 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
     if v.create_gif:
         at = next(i for i, (label, _) in enumerate(rows) if label == "GIF Outro Included") + 1
         rows[at:at] = [("GIF Colors", v.gif_colors), ("GIF Dither", v.gif_dither)]
+    if v.format != "mp4":
+        rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Video Creation") + 1, ("Video Format", v.format))
     if cfg.output.save_masks:
         rows.insert(next(i for i, (label, _) in enumerate(rows) if label == "Output Directory") + 1, ("Save Masks", "Yes"))
     for label, value in rows:

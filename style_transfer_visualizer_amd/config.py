@@ -14,7 +14,8 @@ several style images, a weight per style layer, ``style_mix.py``; ``None`` = not
 ``optimization.pooling`` ("max" | "avg": the pooling layers of the feature stack, "max" = VGG as trained) and
 ``optimization.auto_mask`` / ``auto_mask_cell`` (the two label maps from a joint colour segmentation of the two images instead
 of mask files, and its cell size, ``segment.py``) and ``output.save_masks`` (write the label maps of a guided run as PNGs) and ``video.gif_colors`` /
-``gif_dither`` (entries of the timelapse GIF's one palette, 2..256, and its dither, "ordered" | "none", ``gif.py``).
+``gif_dither`` (entries of the timelapse GIF's one palette, 2..256, and its dither, "ordered" | "none", ``gif.py``) and
+``video.format`` ("mp4" | "mjpeg": the timelapse video's container; only "mjpeg" has an encoder in this build, ``mjpeg.py``).
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ from pydantic import BaseModel, Field, field_validator
 from . import config_defaults as d
 from .constants import VIDEO_QUALITY_MAX, VIDEO_QUALITY_MIN
 from .logging_utils import logger
-from .type_defs import GifDither, InitMethod, Pooling, Precision, PreserveColor, ResizeFilter, VideoMode
+from .type_defs import GifDither, InitMethod, Pooling, Precision, PreserveColor, ResizeFilter, VideoFormat, VideoMode
 
 
 class OptimizationConfig(BaseModel):
@@ -101,6 +102,7 @@ class VideoConfig(BaseModel):
     gif_include_outro: bool = d.DEFAULT_GIF_INCLUDE_OUTRO
     gif_colors: int = Field(d.DEFAULT_GIF_COLORS, ge=2, le=256)
     gif_dither: GifDither = Field(d.DEFAULT_GIF_DITHER)
+    format: VideoFormat = Field(d.DEFAULT_VIDEO_FORMAT)
     mode_override: bool = Field(default=False, exclude=True, repr=False)
 
 
@@ -186,7 +188,7 @@ _DIRECT = {
     "metadata_title": ("video", "metadata_title"), "metadata_artist": ("video", "metadata_artist"),
     "create_gif": ("video", "create_gif"), "gif_include_intro": ("video", "gif_include_intro"),
     "gif_include_outro": ("video", "gif_include_outro"),
-    "gif_colors": ("video", "gif_colors"), "gif_dither": ("video", "gif_dither"),
+    "gif_colors": ("video", "gif_colors"), "gif_dither": ("video", "gif_dither"), "video_format": ("video", "format"),
     "final_frame_compare": ("video", "final_frame_compare"),
     "device": ("hardware", "device"), "precision": ("hardware", "precision"),
 }
@@ -259,6 +261,8 @@ def _apply_video_overrides(cfg: StyleTransferConfig, args: Mapping[str, Any]) ->
     _apply_section(cfg, args, "video")
     if "gif_colors" in args or "gif_dither" in args:            # (assignments are not validated: the field rules again)
         VideoConfig.model_validate({"gif_colors": cfg.video.gif_colors, "gif_dither": cfg.video.gif_dither})
+    if "video_format" in args:
+        VideoConfig.model_validate({"format": cfg.video.format})
     for key, attr in (("intro_duration", "intro_duration_seconds"), ("outro_duration", "outro_duration_seconds")):
         if key in args:
             setattr(cfg.video, attr, max(args[key], 0.0))       # negative durations mean "none"

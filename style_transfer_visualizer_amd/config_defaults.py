@@ -47,6 +47,7 @@ DEFAULT_CREATE_GIF = False
 DEFAULT_GIF_INCLUDE_INTRO = False
 DEFAULT_GIF_INCLUDE_OUTRO = False
 DEFAULT_GIF_COLORS = 256       # build-specific: entries of the timelapse GIF's one palette (2..256)
+DEFAULT_VIDEO_FORMAT = "mp4"   # build-specific: "mp4" (the reference's container; no encoder in this build) or "mjpeg" (built in)
 DEFAULT_GIF_DITHER = "ordered" # build-specific: "ordered" (8x8 Bayer) or "none"
 
 # hardware

@@ -12,6 +12,12 @@ The intro and outro segments of the reference's GIF need its gallery renderer, w
 with a warning.  An injected collector wins; on a CPU device and in a coarse-to-fine run the request is downgraded as a video
 request is.  With ``create_gif`` off nothing here changes.
 
+``video.format = "mjpeg"`` (``mjpeg.py``): a Motion-JPEG timelapse video is built in under the same conditions - ``create_video``
+on, a GPU, no injected ``video_writer``, one level -: a ``mjpeg.DeviceMjpegWriter`` keeps the frames' DCT coefficients on the
+device and writes ``timelapse_{content}_x_{style}.avi`` when the run is over; its refusals (frame size, budget) come before the
+run's first kernel.  The intro and outro segments need the gallery renderer: ``intro_enabled`` and ``final_frame_compare`` are
+ignored with a warning.  With ``format = "mp4"`` (the default) nothing here changes: the request is downgraded as before.
+
 ``optimization.preserve_color`` (``color.py``, no counterpart in the reference) adds one stage at either end: "match"
 re-colours the style image right behind the loads, "luma" restores the content image's chrominance in the result right
 in front of the save; "off" adds nothing.
@@ -44,6 +50,7 @@ import torch
 
 from . import color, core_model, guidance, image_io, ops, optimization, pyramid, runtime, segment, style_mix
 from . import gif as gif_output
+from . import mjpeg as mjpeg_output
 from . import resize as resize_rules
 from .logging_utils import logger
 from .type_defs import InputPaths, SaveOptions
@@ -155,10 +162,14 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
     # the built-in GIF collector keeps its frames on the device and needs one frame size: a GPU run at one level
     builtin_gif = (config.video.create_gif and gif_collector is None and device.type == "cuda"
                    and config.optimization.pyramid_levels == 1)
-    if (config.video.create_video and video_writer is None) or (config.video.create_gif and gif_collector is None and not builtin_gif):
+    # the built-in Motion-JPEG writer (video.format = "mjpeg") keeps coefficients on the device: the same conditions
+    builtin_mjpeg = (config.video.create_video and video_writer is None and getattr(config.video, "format", "mp4") == "mjpeg"
+                     and device.type == "cuda" and config.optimization.pyramid_levels == 1)
+    if ((config.video.create_video and video_writer is None and not builtin_mjpeg)
+            or (config.video.create_gif and gif_collector is None and not builtin_gif)):
         logger.warning("Timelapse encoding is not part of the MI355X build; continuing without video/GIF "
                        "(pass --no-video to silence this, or inject a frame sink).")
-        config.video.create_video = video_writer is not None
+        config.video.create_video = video_writer is not None or builtin_mjpeg
         config.video.create_gif = gif_collector is not None or builtin_gif
     if builtin_gif:                             # refusals before the first launch: the palette size, the dither
         gif_colors = gif_output.check_colors(getattr(config.video, "gif_colors", gif_output.MAX_COLORS))
@@ -168,17 +179,27 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
             logger.warning("gif_include_intro / gif_include_outro are ignored: the intro and outro segments of the GIF timelapse "
                            "are not built; the file holds the frames of the run.")
 
+    if builtin_mjpeg:                           # (the quality was validated above)
+        if config.video.intro_enabled or config.video.final_frame_compare:
+            logger.warning("intro_enabled / final_frame_compare are ignored: the intro and outro segments of the MJPEG timelapse "
+                           "are not built; the file holds the frames of the run (--no-intro --no-final-frame-compare silence this).")
+
     normalize = config.optimization.normalize
     content_img = image_io.load_image_to_tensor(paths.content_path, device, normalize=normalize)
     style_img = image_io.load_image_to_tensor(paths.style_path, device, normalize=normalize)
     extra_styles = [image_io.load_image_to_tensor(path, device, normalize=normalize) for path in extra_paths]
     oc = config.optimization
     gif_frames = oc.steps // config.video.save_every if builtin_gif else 0
-    if builtin_gif:                             # the run has the content's size: refuse a store over the budget before any kernel
+    video_frames = oc.steps // config.video.save_every if builtin_mjpeg else 0
+    if builtin_gif or builtin_mjpeg:            # the run has the content's size: refuse a store over the budget before any kernel
         run_hw = tuple(int(v) for v in content_img.shape[-2:])
         if oc.content_size > 0 or oc.style_size > 0 or oc.style_scale > 0:
             run_hw = resize_rules.plan_sizes(oc, run_hw, style_img.shape[-2:])[0] or run_hw
-        gif_output.check_budget(gif_frames, *run_hw)
+        if builtin_gif:
+            gif_output.check_budget(gif_frames, *run_hw)
+        if builtin_mjpeg:
+            mjpeg_output.check_frame_size(*run_hw)
+            mjpeg_output.check_budget(video_frames, *run_hw)
     if oc.content_size > 0 or oc.style_size > 0 or oc.style_scale > 0:
         loaded_hw = tuple(int(v) for v in content_img.shape[-2:])
         content_img, style_img = _resize_inputs(content_img, style_img, oc)
@@ -220,6 +241,14 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
             output_path / gif_name, config.video.fps, int(input_img.shape[-2]), int(input_img.shape[-1]), gif_frames,
             colors=gif_colors, dither=gif_dither, device=device)
 
+    video_name = None
+    if builtin_mjpeg:
+        video_name = f"timelapse_{content_name}_x_{_style_stem(paths)}{output_tag}.avi"
+        video_writer = mjpeg_output.DeviceMjpegWriter(
+            output_path / video_name, config.video.fps, int(input_img.shape[-2]), int(input_img.shape[-1]), video_frames,
+            quality=config.video.quality, device=device,
+            info=mjpeg_output.video_info(config.video.metadata_title, config.video.metadata_artist))
+
     if coarse_to_fine:                          # (refuses frame sinks: frames would change size between levels)
         input_img, loss_metrics, elapsed = pyramid.run_pyramid(
             content_img, style_img, device, config, video_writer=video_writer, gif_collector=gif_collector,
@@ -236,7 +265,7 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
 
     runtime.save_outputs(input_img, loss_metrics, output_path, elapsed, SaveOptions(
         content_name=content_name, style_name=style_name, normalize=normalize,
-        video_created=video_writer is not None, gif_name=gif_name, gif_created=gif_collector is not None,
+        video_name=video_name, video_created=video_writer is not None, gif_name=gif_name, gif_created=gif_collector is not None,
         plot_losses=config.output.plot_losses),
         **({"plot_name": f"loss_plot{output_tag}.png"} if output_tag else {}))      # (untagged: the reference's call, runtime/output.py:55)
     return input_img.detach().clamp(0, 1)

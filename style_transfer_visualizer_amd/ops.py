@@ -834,6 +834,96 @@ def gif_map(frame: torch.Tensor, palette: torch.Tensor, spread: int, out: torch.
     return out
 
 
+# ---- Motion-JPEG timelapse (--video-format mjpeg) -----------------------------------
+
+def jpeg_blocks(H: int, W: int) -> int:
+    """8x8 blocks of a 4:2:0 frame of ``H x W`` pixels: six per 16x16 MCU, edges padded."""
+    return ((int(H) + 15) // 16) * ((int(W) + 15) // 16) * 6
+
+
+def _jpeg_coef(coef: torch.Tensor, what: str) -> tuple[int, int]:
+    if coef.dtype != torch.int16 or coef.dim() != 3 or coef.shape[2] != 64 or not coef.is_contiguous():   # noqa: PLR2004
+        msg = f"{what} expects contiguous int16 coefficients [frames, blocks, 64], got {tuple(coef.shape)} {coef.dtype}"
+        raise RuntimeError(msg)
+    return int(coef.shape[0]), int(coef.shape[1])
+
+
+def _jpeg_u32(t: torch.Tensor, shape: tuple[int, ...], what: str) -> None:
+    if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+        msg = f"{what} is {tuple(t.shape)} {t.dtype}, expected a contiguous {shape} torch.int32"
+        raise RuntimeError(msg)
+
+
+def jpeg_dct(frame: torch.Tensor, qtabs, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Quantised DCT coefficients of a contiguous uint8 frame ``[H, W, 3]`` (``stv_jpeg_dct``): colour conversion, 4:2:0
+    chroma, level shift, fixed-point 8x8 DCT, quantisation by ``qtabs`` (128 host integers in 1..255: the luminance table,
+    then the chrominance table, row-major), int16 in zigzag order, ``[jpeg_blocks(H, W), 64]`` (a new tensor by default;
+    ``out`` may be one frame of a store).  The frame may start at any byte.  Returns ``out``."""
+    lib = _lib.load()
+    H, W = _gif_frame(frame, "jpeg_dct")
+    q = [int(v) for v in np.asarray(qtabs).reshape(-1)]
+    if len(q) != 128:   # noqa: PLR2004
+        msg = f"jpeg_dct: qtabs holds {len(q)} entries, expected 2 tables of 64"
+        raise RuntimeError(msg)
+    n = jpeg_blocks(H, W)
+    if out is None:
+        out = torch.empty(n, 64, dtype=torch.int16, device=frame.device)
+    elif out.dtype != torch.int16 or tuple(out.shape) != (n, 64) or not out.is_contiguous():
+        msg = f"jpeg_dct: out is {tuple(out.shape)} {out.dtype}, expected a contiguous int16 {(n, 64)}"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_jpeg_dct(_ptr(frame), (ctypes.c_int * 128)(*q), H, W, _ptr(out), _stream()), "stv_jpeg_dct")
+    return out
+
+
+def jpeg_block_bits(coef: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The length in bits of every block's Huffman code (``stv_jpeg_block_bits``): ``coef`` int16 ``[frames, blocks, 64]`` in
+    zigzag order, the result ``torch.int32 [frames, blocks]`` holding unsigned counts.  The DC of a block is coded against
+    the previous block of its component inside its frame."""
+    lib = _lib.load()
+    F, B = _jpeg_coef(coef, "jpeg_block_bits")
+    if out is None:
+        out = torch.empty(F, B, dtype=torch.int32, device=coef.device)
+    _jpeg_u32(out, (F, B), "jpeg_block_bits: out")
+    _lib.check(lib.stv_jpeg_block_bits(_ptr(coef), F, B, _ptr(out), _stream()), "stv_jpeg_block_bits")
+    return out
+
+
+def jpeg_scan(bits: torch.Tensor, offsets: torch.Tensor | None = None,
+              totals: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Per frame the exclusive prefix sum of ``bits`` (``torch.int32 [frames, blocks]``) and its total (``stv_jpeg_scan``):
+    returns ``(offsets [frames, blocks], totals [frames])``."""
+    lib = _lib.load()
+    if bits.dim() != 2:   # noqa: PLR2004
+        msg = f"jpeg_scan expects bits [frames, blocks], got {tuple(bits.shape)}"
+        raise RuntimeError(msg)
+    F, B = int(bits.shape[0]), int(bits.shape[1])
+    _jpeg_u32(bits, (F, B), "jpeg_scan: bits")
+    if offsets is None:
+        offsets = torch.empty(F, B, dtype=torch.int32, device=bits.device)
+    if totals is None:
+        totals = torch.empty(F, dtype=torch.int32, device=bits.device)
+    _jpeg_u32(offsets, (F, B), "jpeg_scan: offsets")
+    _jpeg_u32(totals, (F,), "jpeg_scan: totals")
+    _lib.check(lib.stv_jpeg_scan(_ptr(bits), F, B, _ptr(offsets), _ptr(totals), _stream()), "stv_jpeg_scan")
+    return offsets, totals
+
+
+def jpeg_emit(coef: torch.Tensor, offsets: torch.Tensor, base: torch.Tensor, stream: torch.Tensor) -> torch.Tensor:
+    """Write the Huffman code of every block into ``stream`` (``stv_jpeg_emit``): a ZEROED contiguous uint8 buffer whose size is
+    a multiple of 4; frame ``f`` starts at byte ``base[f]`` (``torch.int32 [frames]``, multiples of 4) and block ``b`` at bit
+    ``offsets[f, b]`` behind it, MSB first, the frame padded to a byte with 1-bits.  Returns ``stream``."""
+    lib = _lib.load()
+    F, B = _jpeg_coef(coef, "jpeg_emit")
+    _jpeg_u32(offsets, (F, B), "jpeg_emit: offsets")
+    _jpeg_u32(base, (F,), "jpeg_emit: base")
+    if stream.dtype != torch.uint8 or stream.dim() != 1 or not stream.is_contiguous():
+        msg = f"jpeg_emit: stream is {tuple(stream.shape)} {stream.dtype}, expected a contiguous uint8 vector"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_jpeg_emit(_ptr(coef), _ptr(offsets), _ptr(base), F, B, _ptr(stream), int(stream.numel()), _stream()),
+               "stv_jpeg_emit")
+    return stream
+
+
 # ---- optimizers ---------------------------------------------------------------
 
 def lbfgs_alloc(n: int, history: int, device: torch.device, *, compact: bool = False,

@@ -404,11 +404,17 @@ class OptimizationRunner:
             return
         # a GIF sink that captures on the device (gif.DeviceGifCollector) takes the image itself: two launches, no host
         # frame.  The host frame - one kernel and a blocking copy - is formed only for whoever else wants one.
+        # A video writer that captures on the device (mjpeg.DeviceMjpegWriter) is treated the same way.
         device_gif = self.gif_collector is not None and callable(getattr(self.gif_collector, "append_device", None))
-        if device_gif:
+        device_video = self.video_writer is not None and callable(getattr(self.video_writer, "append_device", None))
+        if device_gif or device_video:
             with torch.no_grad():
-                self.gif_collector.append_device(self.input_img, normalize=self.config.optimization.normalize)
-            if self.video_writer is None and self.callbacks.on_video_frame is None:
+                for sink, on_device in ((self.video_writer, device_video), (self.gif_collector, device_gif)):
+                    if on_device:
+                        sink.append_device(self.input_img, normalize=self.config.optimization.normalize)
+            host_sinks = [s for s, on_device in ((self.video_writer, device_video), (self.gif_collector, device_gif))
+                          if s is not None and not on_device]
+            if not host_sinks and self.callbacks.on_video_frame is None:
                 self._update_progress_postfix(metrics)
                 return
         with torch.no_grad():
@@ -416,13 +422,13 @@ class OptimizationRunner:
             if frame is None:
                 return
         if self.intro_last_frame is not None and not self.intro_transition_done:
-            if self.video_writer is not None and vc.intro_enabled:
+            if self.video_writer is not None and vc.intro_enabled and not device_video:
                 append_crossfade(self.video_writer, self.intro_last_frame, frame, self.intro_crossfade_frames)
             if self.gif_collector is not None and vc.gif_include_intro and not device_gif:
                 append_crossfade(self.gif_collector, self.intro_last_frame, frame, self.intro_crossfade_frames)
             self.intro_transition_done = True
             self.intro_last_frame = None
-        for sink in (self.video_writer, None if device_gif else self.gif_collector):
+        for sink in (None if device_video else self.video_writer, None if device_gif else self.gif_collector):
             if sink is not None:
                 sink.append_data(frame)
         self._update_progress_postfix(metrics)

@@ -13,6 +13,7 @@ PreserveColor = Literal["off", "match", "luma"]
 ResizeFilter = Literal["bilinear", "bicubic", "lanczos"]
 Pooling = Literal["max", "avg"]
 GifDither = Literal["none", "ordered"]
+VideoFormat = Literal["mp4", "mjpeg"]
 LossHistory = dict[str, list[float]]
 TensorList = list[torch.Tensor]
 
