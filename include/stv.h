@@ -641,6 +641,12 @@ int stv_lbfgsc_dots(const float* grad, void* state, void* workspace, size_t n, i
 int stv_lbfgsc_apply(float* x, const float* grad, void* state, void* workspace, size_t n, int history, float lr,
                      float tol_grad, float tol_change, void* stream);
 size_t stv_lbfgsc_dots_offset(size_t n, int history, int* count, int* max_index);
+/* Since version 117.  The launch geometry a step over n elements will use (host arithmetic: no launch, no device
+ * access), with the STV_LBFGS_TILE / STV_LBFGS_TILE_B / STV_LBFGS_PGROUPS overrides applied: *nn = n padded to the pitch
+ * (d, prev_g and every S / Y row are *nn floats, laid out d | prev_g | S[history+1] | Y[history+1]), sweep A's tile in
+ * floats, its tile count and the number of workgroups a tile's history pairs are dealt to, sweep B's tile in floats.
+ * Any out pointer may be NULL.  For tests and tools: which kernel instantiation a size reaches. */
+int stv_lbfgsc_geometry(size_t n, int history, size_t* nn, int* tile_a, int* ntiles, int* pgroups, int* tile_b);
 /* Since version 103.  torch.optim.LBFGS.step with max_iter > 1 (no line search), one call per iteration:
  * `iters_per_step` consecutive calls on one state block are ONE optimizer step, each behind the evaluation of the
  * image the previous call left.  iters_per_step = min(max_iter, max(1, max_eval - 1)) is known on the host; the step's

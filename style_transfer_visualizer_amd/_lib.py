@@ -184,6 +184,8 @@ SIGNATURES = {
     "stv_lbfgsc_dots": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "stv_lbfgsc_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_float, c_void_p]),
     "stv_lbfgsc_dots_offset": (c_size_t, [c_size_t, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "stv_lbfgsc_geometry": (c_int, [c_size_t, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                    ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "stv_lbfgsc_iter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_float, c_float, c_float,
                                 c_void_p]),
     "stv_lbfgsc_iter_reset": (c_int, [c_void_p, c_void_p]),

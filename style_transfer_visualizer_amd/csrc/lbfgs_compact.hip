@@ -699,7 +699,8 @@ inline int tile_floats_b(size_t n) {
   return 1024;
 }
 struct StepGeom { size_t nn; int tile, ntiles, nparts, pgroups; CWs w; };
-inline StepGeom step_geom(void* workspace, size_t n, int history) {
+// the launch shape alone (no workspace): what stv_lbfgsc_geometry reports is what step_geom launches
+inline StepGeom launch_geom(size_t n) {
   StepGeom g;
   g.nn = align_up(n, 4096);
   g.tile = tile_floats(n);
@@ -711,6 +712,11 @@ inline StepGeom step_geom(void* workspace, size_t n, int history) {
   g.pgroups = forced_pg > 0 ? forced_pg : (g.ntiles >= 256 ? 1 : (768 + g.ntiles - 1) / g.ntiles);
   if (g.pgroups > 4) g.pgroups = 4;
   if (g.pgroups < 1) g.pgroups = 1;
+  g.w = CWs{};
+  return g;
+}
+inline StepGeom step_geom(void* workspace, size_t n, int history) {
+  StepGeom g = launch_geom(n);
   g.w = carve(workspace, n, history, g.nparts);
   return g;
 }
@@ -782,6 +788,19 @@ extern "C" size_t stv_lbfgsc_dots_offset(size_t n, int history, int* count, int*
   if (count) *count = 5 * MAX_HIST + NSCAL;
   if (max_index) *max_index = 5 * MAX_HIST;
   return (nn * (2 + 2 * (size_t)S) + 2 * 2 * align_up((size_t)S * S, 64)) * sizeof(float);
+}
+
+// The launch geometry of a step over n elements, environment overrides included (host arithmetic only, no launch, no
+// device access): padded length, sweep A's tile in floats / tile count / pair groups, sweep B's tile in floats.
+extern "C" int stv_lbfgsc_geometry(size_t n, int history, size_t* nn, int* tile_a, int* ntiles, int* pgroups, int* tile_b) {
+  if (n == 0 || history < 1 || history > MAX_HIST) return STV_ERR_ARG;
+  const StepGeom g = launch_geom(n);
+  if (nn) *nn = g.nn;
+  if (tile_a) *tile_a = g.tile;
+  if (ntiles) *ntiles = g.ntiles;
+  if (pgroups) *pgroups = g.pgroups;
+  if (tile_b) *tile_b = tile_floats_b(n);
+  return STV_OK;
 }
 
 extern "C" int stv_lbfgsc_step(float* x, const float* grad, void* state, void* workspace, size_t n, int history,

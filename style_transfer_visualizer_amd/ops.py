@@ -985,6 +985,26 @@ def lbfgs_dots_view(work: torch.Tensor, n: int, history: int) -> tuple[torch.Ten
     return work[off // 4: off // 4 + 2 * count.value].view(torch.float64), imax.value
 
 
+def lbfgs_geometry(n: int, history: int) -> dict:
+    """What a compact L-BFGS step over ``n`` elements launches (stv_lbfgsc_geometry; host only): ``nn`` (padded
+    length), ``tile_a`` / ``ntiles`` / ``pgroups`` of sweep A, ``tile_b`` of sweep B."""
+    nn = ctypes.c_size_t()
+    tile_a, ntiles, pgroups, tile_b = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().stv_lbfgsc_geometry(n, history, ctypes.byref(nn), ctypes.byref(tile_a), ctypes.byref(ntiles),
+                                               ctypes.byref(pgroups), ctypes.byref(tile_b)), "stv_lbfgsc_geometry")
+    return {"nn": int(nn.value), "tile_a": tile_a.value, "ntiles": ntiles.value, "pgroups": pgroups.value,
+            "tile_b": tile_b.value}
+
+
+def lbfgs_views(work: torch.Tensor, n: int, history: int) -> dict:
+    """fp32 views into a compact workspace: ``d`` and ``prev_g`` ``[nn]``, the rings ``S`` and ``Y``
+    ``[history + 1, nn]`` (by ring slot), with ``nn`` from ``lbfgs_geometry``."""
+    nn = lbfgs_geometry(n, history)["nn"]
+    rows = history + 1
+    ring = work[2 * nn: 2 * nn + 2 * rows * nn].view(2, rows, nn)
+    return {"d": work[:nn], "prev_g": work[nn: 2 * nn], "S": ring[0], "Y": ring[1]}
+
+
 def lbfgs_apply(x: torch.Tensor, grad: torch.Tensor, state: torch.Tensor, work: torch.Tensor, history: int, lr: float,
                 tol_grad: float = 1e-7, tol_change: float = 1e-9) -> None:
     """Second half (stv_lbfgsc_apply): scalar recursion from the (all-reduced) inner products, then the update."""

@@ -34,6 +34,9 @@ def test_version_and_sizing_helpers_run_without_gpu():
     assert lib.stv_lbfgs_workspace_bytes(3 * 64 * 64, 100) > 2 * 101 * 3 * 64 * 64 * 4
     assert lib.stv_lbfgsc_workspace_bytes(3 * 64 * 64, 100) > 2 * 101 * 3 * 64 * 64 * 4
     assert lib.stv_gram_loss_parts(64) * 128 >= 64 * 64   # one loss partial per 128 Gram elements
+    nn, tile_a = ctypes.c_size_t(), ctypes.c_int()
+    assert lib.stv_lbfgsc_geometry(3 * 64 * 64, 100, ctypes.byref(nn), ctypes.byref(tile_a), None, None, None) == 0
+    assert nn.value == 3 * 64 * 64 and tile_a.value in (1024, 2048, 4096)   # (the L-BFGS launch shape: host arithmetic)
 
 
 def test_op_struct_layout_matches_header():

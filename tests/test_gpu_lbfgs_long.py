@@ -183,6 +183,12 @@ def test_lbfgs_full_history_matches_oracle(history, compact):
     _run(f"lbfgs m={history} n=20000 {'compact' if compact else 'twoloop'}", 20000, history, compact)
 
 
+def test_lbfgs_twoloop_over_three_stride_trips():
+    """The operation-ordered form strides by 512 x 256 = 131072 elements: n = 262144 + 77 makes every vector loop take
+    three trips, the last one ragged (n = 20,000 never makes a second)."""
+    _run("lbfgs m=6 n=262144+77 twoloop", 262144 + 77, 6, False, extra_steps=8)
+
+
 def test_lbfgs_full_history_at_512_image_size():
     """n = 3 x 512 x 512 (the image of configs[1]): 4096-float tiles, 768 per-wave partial sums per dot."""
     _run("lbfgs m=100 n=3x512x512 compact", 3 * 512 * 512, 100, True, extra_steps=30)
