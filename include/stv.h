@@ -437,6 +437,58 @@ int stv_luma_transfer(const float* result, const float* content, float* out, int
 int stv_kmeans_assign(const float* x_nchw, const float* centroids, uint8_t* labels, double* parts, int H, int W, int K,
                       void* stream);
 
+/* ---- Automatic masks in VGG feature space (--auto-mask-space features; no counterpart in the reference): the joint
+ *      k-means over one VGG layer's activations of the content and of the style image.  Since version 118.  Two assignment
+ *      launches and one update launch per iteration while the run is set up, none inside the step.  A point is a pixel of
+ *      F, NHWC [n][C] of bf16 or fp32 (bf16 -> fp32 by the exact bit shift), C = 64, 128, 256 or 512 (the channel
+ *      counts of VGG; Q below must be a power of two: the lane maps and the pairwise sums halve it down to 1).  The channel axis
+ *      is cut into Q = C/8 octets of 8 consecutive channels; with o the octet and k the centroid:
+ *   p_k[o]   = (...((0 + e_0*e_0) + e_1*e_1) ...) + e_7*e_7,  e_j = x[8o+j] - c_k[8o+j]     ascending j
+ *   d_k      = the Q octet sums combined pairwise: for s = Q/2, Q/4, ..., 1:  p_k[o] = p_k[o] + p_k[o+s]  (o < s);  d_k = p_k[0]
+ *              every difference, product and sum rounded to fp32 on its own (no FMA contraction): an fp32 twin reproduces
+ *              every bit
+ *   label(p) = the first k, ascending, with d_k < the best so far, which starts at +inf (a strict `<`: the lowest index
+ *              wins a tie; a NaN distance never wins; a pixel whose every distance is NaN or +inf gets label 0)
+ *      Inputs are taken as finite. ---- */
+/* launch constants.  A pixel belongs to Q lanes of one wave (one octet each: a 16-byte load of bf16, two of fp32), so a wave
+ * holds G = 64/Q pixels at a time, a workgroup of STV_KMF_THREADS threads STV_KMF_WAVES * G, and the kernel always launches
+ * STV_KMF_PARTS workgroups (one row of `parts` each): a pass of the grid covers STV_KMF_PARTS * STV_KMF_WAVES * G pixels.
+ * Pixel p sits in
+ *   pass = p / (STV_KMF_PARTS * STV_KMF_WAVES * G),   r = p % (STV_KMF_PARTS * STV_KMF_WAVES * G),
+ *   workgroup = r / (STV_KMF_WAVES * G),   wave = (r / G) % STV_KMF_WAVES,   group = r % G,   lane = group * Q + octet
+ * so the 64 lanes of a wave read 64 * 8 consecutive elements.  Order of the double sums of one entry: a lane adds its pixels
+ * in pass order (a pixel of another label, and a pixel past n, adds +0.0); the G lanes of a wave that hold the same octet
+ * combine pairwise, for h = G/2, ..., 1: v[g] = v[g] + v[g+h] (g < h); the waves add into a zeroed entry in wave order. */
+#define STV_KMF_THREADS 256
+#define STV_KMF_WAVES 4
+#define STV_KMF_PARTS 256
+#define STV_KMF_MAX_K 4
+#define STV_KMF_MAX_C 512
+/* doubles in one row of `parts` for C channels: for k < 4 at k*(C+1) .. k*(C+1)+C-1 the channel sums of the workgroup's
+ * pixels with label k and at k*(C+1)+C their number; at 4*(C+1) the number of its pixels whose label changed */
+#define STV_KMF_ROW_DOUBLES(C) (4 * ((C) + 1) + 1)
+/* F: [n][C] on the device, 16-byte aligned, dtype STV_F32 or STV_BF16.  centroids: fp32 [K][C] on the device, uniform over
+ * the launch.  labels: uint8 [n]; in: the previous labels (any bytes before the first iteration), out: the new ones - the
+ * octet-0 lane of a pixel reads its byte before it writes it and no other lane touches it, so in place is the contract.
+ * keep_labels != 0: labels are read and not written, no distance is formed, the changed count is 0 and a pixel whose
+ * label is >= K is in no sum (the pass that gives the mean: all labels 0, K = 1).  parts: double [STV_KMF_PARTS]
+ * [STV_KMF_ROW_DOUBLES(C)]; no atomics; every entry is written on every launch, zeros for k >= K and for a workgroup
+ * without pixels.
+ * STV_ERR_ARG, before any HIP call: a null pointer, n < 1, C other than 64, 128, 256, 512 (192, 320, 384 and 448 included),
+ * K outside 1..4, a dtype other than the two, n*C of 2^31 elements or more, F not 16-byte aligned. */
+int stv_kmeans_feat_assign(const void* F, int dtype, const float* centroids, uint8_t* labels, double* parts, int n, int C,
+                           int K, int keep_labels, void* stream);
+/* The centroid update on the device, one work item per (k, c), k < K, c < C.  With i = content (parts_c, n_c) and style:
+ *   S_k^i[c], N_k^i, changed^i = the STV_KMF_PARTS rows of parts_i added in index order (from the first row's value)
+ *   w_k      = N_k^c/n_c + N_k^s/n_s
+ *   c_k[c]   = fp32((S_k^c[c]/n_c + S_k^s[c]/n_s) / w_k)     every operation a double operation of its own (no FMA
+ *              contraction), one rounding to fp32; where w_k == 0 (a cluster empty in both images) c_k is left as it is
+ * centroids: fp32 [K][C], updated in place.  result: double [9] on the device - [0..3] N_k^c, [4..7] N_k^s (zeros for
+ * k >= K), [8] changed^c + changed^s: all the host reads per iteration.
+ * STV_ERR_ARG, before any HIP call: a null pointer, n_c < 1, n_s < 1, C other than 64, 128, 256, 512, K outside 1..4. */
+int stv_kmeans_feat_update(const double* parts_c, const double* parts_s, float* centroids, double* result, int n_c, int n_s,
+                           int C, int K, void* stream);
+
 /* ---- Blended Gram targets (several style images with blend weights; no counterpart in the reference; jcjohnson's
  *      -style_blend_weights).  Since version 110.  One launch per style layer when targets are set, none inside the step.
  *   out[i] = (...((w[0]*G_0[i]) + w[1]*G_1[i]) + ...) + w[K-1]*G_{K-1}[i]      i < n

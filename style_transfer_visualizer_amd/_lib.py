@@ -55,6 +55,25 @@ COLOR_VEC, COLOR_THREADS, COLOR_STATS_PARTS, COLOR_MAX_BLOCKS = 4, 256, 256, 102
 # KMEANS_PARTS workgroups of KMEANS_THREADS threads, one row of KMEANS_PART_DOUBLES doubles each - for k < KMEANS_MAX_K at
 # 4k..4k+3 the sums of the three channels and the count of label k, at [16] the changed labels
 KMEANS_THREADS, KMEANS_PARTS, KMEANS_PART_DOUBLES, KMEANS_MAX_K = 256, 256, 17, 4
+# launch constants of stv_kmeans_feat_assign / stv_kmeans_feat_update (stv.h STV_KMF_*; csrc/kmeans_feat.hip): a pixel of C
+# channels belongs to C/8 lanes of one wave, a wave holds 64 / (C/8) pixels at a time, always KMF_PARTS workgroups of
+# KMF_THREADS threads (KMF_WAVES waves), one row of kmf_row_doubles(C) doubles each
+KMF_THREADS, KMF_WAVES, KMF_PARTS, KMF_MAX_K, KMF_MAX_C = 256, 4, 256, 4, 512
+KMF_CHANNELS = (64, 128, 256, 512)      # the channel counts the kernels take: C/8 lanes per pixel, a power of two
+
+
+def kmf_row_doubles(C: int) -> int:
+    """``STV_KMF_ROW_DOUBLES(C)``: per cluster ``k < 4`` the ``C`` channel sums and the count at ``k*(C+1)``, then the changed
+    count."""
+    return 4 * (C + 1) + 1
+
+
+def kmf_geometry(C: int) -> tuple[int, int, int]:
+    """``(Q, G, pixels per pass of the grid)`` for ``C`` channels: lanes per pixel, pixels per wave, ``KMF_PARTS * KMF_WAVES * G``."""
+    Q = C // 8
+    G = 64 // Q
+    return Q, G, KMF_PARTS * KMF_WAVES * G
+
 # launch constants of stv_gram_blend (stv.h STV_BLEND_*; csrc/blend.hip): at most BLEND_MAX_TABLES tables per launch, a work
 # item is BLEND_VEC consecutive elements, a pass of the capped grid covers BLEND_MAX_BLOCKS * BLEND_THREADS items
 BLEND_MAX_TABLES, BLEND_VEC, BLEND_THREADS, BLEND_MAX_BLOCKS = 8, 4, 256, 128
@@ -162,6 +181,8 @@ SIGNATURES = {
     "stv_color_affine": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int, c_void_p]),
     "stv_luma_transfer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),
     "stv_kmeans_assign": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "stv_kmeans_feat_assign": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "stv_kmeans_feat_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "stv_gram_blend": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_int, c_int64, c_void_p]),
     "stv_image_to_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_void_p]),
     "stv_frame_hist": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),

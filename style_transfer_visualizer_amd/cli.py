@@ -5,7 +5,7 @@ are accepted and reported as unavailable.  Additions: ``--precision {fp32,bf16,b
 ``--pyramid-levels`` / ``--pyramid-steps``, ``--preserve-color {off,match,luma}``, ``--content-size`` / ``--style-size`` /
 ``--style-scale`` / ``--resize-filter {bilinear,bicubic,lanczos}``, ``--style-also`` / ``--style-blend`` /
 ``--style-layer-weights``, ``--lap-w`` / ``--lap-pool``, ``--content-mask`` / ``--style-mask`` / ``--mask-regions`` /
-``--region-weights``, ``--auto-mask`` / ``--auto-mask-cell`` / ``--save-masks`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
+``--region-weights``, ``--auto-mask`` / ``--auto-mask-cell`` / ``--auto-mask-space`` / ``--auto-mask-layer`` / ``--save-masks`` (``--content`` and ``--style`` stay exact options: argparse prefers an exact match to a prefix).
 """
 from __future__ import annotations
 
@@ -87,6 +87,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
                      help="Spatial guidance without mask files: segment both images jointly into --mask-regions colour regions")
     opt.add_argument("--auto-mask-cell", type=int, choices=[1, 2, 4, 8, 16, 32], default=S,
                      help="Cell size of the --auto-mask segmentation in pixels (default: 8)")
+    opt.add_argument("--auto-mask-space", choices=["color", "features"], default=S,
+                     help="Where --auto-mask clusters: color (box means of the colours, the default) or features (one VGG layer)")
+    opt.add_argument("--auto-mask-layer", type=int, default=S,
+                     help="VGG layer index whose output --auto-mask-space features clusters (default: 10, conv3_1)")
     opt.add_argument("--pooling", choices=["max", "avg"], default=S,
                      help="Pooling layers of the feature stack: max (VGG as trained, the default) or avg (the mean of each 2x2 window)")
     opt.add_argument("--lr", type=float, default=S, help="Learning rate")
@@ -198,6 +202,8 @@ def log_parameters(paths: InputPaths, cfg: stv_config.StyleTransferConfig,
     if o.auto_mask:
         at = next(i for i, (label, _) in enumerate(rows) if label == "Style image loaded") + 1
         rows[at:at] = [("Automatic Masks", "Enabled"), ("Mask Regions", o.mask_regions), ("Automatic Mask Cell", o.auto_mask_cell)]
+        if getattr(o, "auto_mask_space", "color") == "features":      # (the cell size is unused there: the layer's grid is the grid)
+            rows[at + 2:at + 3] = [("Automatic Mask Space", o.auto_mask_space), ("Automatic Mask Layer", o.auto_mask_layer)]
     if v.create_gif:
         at = next(i for i, (label, _) in enumerate(rows) if label == "GIF Outro Included") + 1
         rows[at:at] = [("GIF Colors", v.gif_colors), ("GIF Dither", v.gif_dither)]

@@ -13,7 +13,8 @@ several style images, a weight per style layer, ``style_mix.py``; ``None`` = not
 / ``region_weights`` (regions of the two masks of a guided run and their weights, ``guidance.py``; read only with masks) and
 ``optimization.pooling`` ("max" | "avg": the pooling layers of the feature stack, "max" = VGG as trained) and
 ``optimization.auto_mask`` / ``auto_mask_cell`` (the two label maps from a joint colour segmentation of the two images instead
-of mask files, and its cell size, ``segment.py``) and ``output.save_masks`` (write the label maps of a guided run as PNGs) and ``video.gif_colors`` /
+of mask files, and its cell size, ``segment.py``) / ``auto_mask_space`` / ``auto_mask_layer`` ("color" | "features": cluster box
+means of the colours, or the activations of one VGG layer, index ``auto_mask_layer``) and ``output.save_masks`` (write the label maps of a guided run as PNGs) and ``video.gif_colors`` /
 ``gif_dither`` (entries of the timelapse GIF's one palette, 2..256, and its dither, "ordered" | "none", ``gif.py``) and
 ``video.format`` ("mp4" | "mjpeg": the timelapse video's container; only "mjpeg" has an encoder in this build, ``mjpeg.py``).
 """
@@ -28,7 +29,7 @@ from pydantic import BaseModel, Field, field_validator
 from . import config_defaults as d
 from .constants import VIDEO_QUALITY_MAX, VIDEO_QUALITY_MIN
 from .logging_utils import logger
-from .type_defs import GifDither, InitMethod, Pooling, Precision, PreserveColor, ResizeFilter, VideoFormat, VideoMode
+from .type_defs import AutoMaskSpace, GifDither, InitMethod, Pooling, Precision, PreserveColor, ResizeFilter, VideoFormat, VideoMode
 
 
 class OptimizationConfig(BaseModel):
@@ -53,6 +54,8 @@ class OptimizationConfig(BaseModel):
     region_weights: list[float] | None = d.DEFAULT_REGION_WEIGHTS
     auto_mask: bool = d.DEFAULT_AUTO_MASK
     auto_mask_cell: int = Field(d.DEFAULT_AUTO_MASK_CELL)
+    auto_mask_space: AutoMaskSpace = Field(d.DEFAULT_AUTO_MASK_SPACE)
+    auto_mask_layer: int = Field(d.DEFAULT_AUTO_MASK_LAYER, ge=0)
     pooling: Pooling = Field(d.DEFAULT_POOLING)
     lr: float = Field(d.DEFAULT_LEARNING_RATE, gt=0)
     init_method: InitMethod = Field(d.DEFAULT_INIT_METHOD)
@@ -178,6 +181,7 @@ _DIRECT = {
     "steps": ("optimization", "steps"), "style_w": ("optimization", "style_w"),
     "content_w": ("optimization", "content_w"), "tv_w": ("optimization", "tv_w"), "lap_w": ("optimization", "lap_w"),
     "mask_regions": ("optimization", "mask_regions"), "auto_mask_cell": ("optimization", "auto_mask_cell"),
+    "auto_mask_space": ("optimization", "auto_mask_space"), "auto_mask_layer": ("optimization", "auto_mask_layer"),
     "pooling": ("optimization", "pooling"),
     "lr": ("optimization", "lr"),
     "pyramid_levels": ("optimization", "pyramid_levels"), "preserve_color": ("optimization", "preserve_color"),

@@ -21,6 +21,8 @@ DEFAULT_MASK_REGIONS = 2     # build-specific: regions of --content-mask / --sty
 DEFAULT_REGION_WEIGHTS = None  # build-specific: one weight per region (None = every region counts 1; 0 = left unstyled)
 DEFAULT_AUTO_MASK = False    # build-specific: segment the two images into mask_regions colour regions instead of reading masks
 DEFAULT_AUTO_MASK_CELL = 8   # build-specific: cell size of that segmentation in pixels (1, 2, 4, 8, 16 or 32)
+DEFAULT_AUTO_MASK_SPACE = "color"  # build-specific: where that segmentation clusters, "color" (box means) or "features" (one VGG layer)
+DEFAULT_AUTO_MASK_LAYER = 10       # build-specific: the VGG index whose output is clustered in "features" space (conv3_1)
 DEFAULT_POOLING = "max"      # build-specific: pooling layers of the feature stack, "max" (VGG as trained) or "avg" (the mean)
 DEFAULT_LEARNING_RATE = 1.0
 DEFAULT_INIT_METHOD = "random"

@@ -212,7 +212,8 @@ def style_transfer(paths: InputPaths, config, *, video_writer=None, gif_collecto
         style_img = color.match_style_to_content(style_img, content_img)
         extra_styles = [color.match_style_to_content(img, content_img) for img in extra_styles]
     if auto_mask:                               # the images the run sees; None: no split that holds, the run is unguided
-        labels = segment.auto_guidance(content_img, style_img, oc, oc.pyramid_levels)
+        space_kw = ({"precision": config.hardware.precision} if getattr(oc, "auto_mask_space", "color") == "features" else {})
+        labels = segment.auto_guidance(content_img, style_img, oc, oc.pyramid_levels, **space_kw)
     if extra_styles:                            # (one style: the tensor itself, as always)
         style_img = [style_img, *extra_styles]
     label_kw = {"content_labels": labels[0], "style_labels": labels[1]} if labels is not None else {}

@@ -627,6 +627,84 @@ def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor, labels: torch.Tensor
     return parts
 
 
+# ---- automatic masks in VGG feature space (--auto-mask-space features) ----------------
+
+def _kmf_shape(C: int, K: int, what: str) -> None:
+    if C not in _lib.KMF_CHANNELS:
+        msg = f"{what}: {C} channels; the feature k-means takes one of {list(_lib.KMF_CHANNELS)} (C/8 lanes per pixel, a power of two)"
+        raise RuntimeError(msg)
+    if not 1 <= K <= _lib.KMF_MAX_K:
+        msg = f"{what}: {K} centroids; the feature k-means takes 1 to {_lib.KMF_MAX_K}"
+        raise RuntimeError(msg)
+
+
+def _kmf_centroids(centroids: torch.Tensor, what: str) -> tuple[int, int]:
+    if centroids.dtype != torch.float32 or centroids.dim() != 2 or not centroids.is_contiguous():      # noqa: PLR2004
+        msg = f"{what}: centroids are {tuple(centroids.shape)} {centroids.dtype}, expected a contiguous fp32 [K, C]"
+        raise RuntimeError(msg)
+    K, C = (int(v) for v in centroids.shape)
+    _kmf_shape(C, K, what)
+    return K, C
+
+
+def _kmf_parts(parts: torch.Tensor | None, C: int, device, what: str) -> torch.Tensor:
+    shape = (_lib.KMF_PARTS, _lib.kmf_row_doubles(C))
+    if parts is None:
+        return torch.empty(shape, dtype=torch.float64, device=device)
+    if tuple(parts.shape) != shape or parts.dtype != torch.float64 or not parts.is_contiguous():
+        msg = f"{what}: parts is {tuple(parts.shape)} {parts.dtype}, expected a contiguous {shape} torch.float64"
+        raise RuntimeError(msg)
+    return parts
+
+
+def kmeans_feat_assign(F: torch.Tensor, centroids: torch.Tensor, labels: torch.Tensor, parts: torch.Tensor | None = None, *,
+                       keep_labels: bool = False) -> torch.Tensor:
+    """One assignment pass of the feature-space k-means (``stv_kmeans_feat_assign``) over contiguous NHWC features
+    ``[..., C]`` of fp32 or bf16 storage: ``labels`` (uint8, one per pixel, in place) receive the index of the nearest of the
+    ``K`` ``centroids`` (fp32 ``[K, C]`` on the device; the distance in the order stv.h fixes, the lowest index wins a tie).
+    ``keep_labels``: the labels are read and not written (the sums and counts of the labels as they are).  Returns ``parts``,
+    float64 ``[KMF_PARTS, kmf_row_doubles(C)]`` on the device (a new tensor by default), one row per workgroup."""
+    lib = _lib.load()
+    what = "kmeans_feat_assign"
+    K, C = _kmf_centroids(centroids, what)
+    if F.dtype not in (torch.float32, torch.bfloat16):
+        msg = f"{what}: features are {F.dtype}; the two storage types are torch.float32 and torch.bfloat16"
+        raise RuntimeError(msg)
+    if F.dim() < 2 or int(F.shape[-1]) != C or not F.is_contiguous() or F.numel() == 0:      # noqa: PLR2004
+        msg = f"{what}: features are {tuple(F.shape)}, expected a contiguous [..., {C}] (the centroids' channels last)"
+        raise RuntimeError(msg)
+    n = F.numel() // C
+    if labels.dtype != torch.uint8 or labels.numel() != n or not labels.is_contiguous():
+        msg = f"{what}: labels are {tuple(labels.shape)} {labels.dtype}, expected {n} contiguous uint8 (one per pixel)"
+        raise RuntimeError(msg)
+    parts = _kmf_parts(parts, C, F.device, what)
+    _lib.check(lib.stv_kmeans_feat_assign(_ptr(F), dtype_code(F.dtype), _ptr(centroids), _ptr(labels), _ptr(parts), n, C, K,
+                                          int(bool(keep_labels)), _stream()), "stv_kmeans_feat_assign")
+    return parts
+
+
+def kmeans_feat_update(parts_c: torch.Tensor, parts_s: torch.Tensor, centroids: torch.Tensor, n_c: int, n_s: int,
+                       result: torch.Tensor | None = None) -> torch.Tensor:
+    """The centroid update of the feature-space k-means on the device (``stv_kmeans_feat_update``): ``centroids`` (fp32
+    ``[K, C]``) in place from the two images' ``parts`` and pixel numbers.  Returns ``result``, float64 ``[9]`` on the device:
+    the four counts of the content image, the four of the style image, the changed total."""
+    lib = _lib.load()
+    what = "kmeans_feat_update"
+    K, C = _kmf_centroids(centroids, what)
+    parts_c, parts_s = _kmf_parts(parts_c, C, centroids.device, what), _kmf_parts(parts_s, C, centroids.device, what)
+    if int(n_c) < 1 or int(n_s) < 1:
+        msg = f"{what}: {n_c} and {n_s} pixels; both images hold at least one"
+        raise RuntimeError(msg)
+    if result is None:
+        result = torch.empty(9, dtype=torch.float64, device=centroids.device)
+    elif tuple(result.shape) != (9,) or result.dtype != torch.float64 or not result.is_contiguous():
+        msg = f"{what}: result is {tuple(result.shape)} {result.dtype}, expected a contiguous (9,) torch.float64"
+        raise RuntimeError(msg)
+    _lib.check(lib.stv_kmeans_feat_update(_ptr(parts_c), _ptr(parts_s), _ptr(centroids), _ptr(result), int(n_c), int(n_s), C, K,
+                                          _stream()), "stv_kmeans_feat_update")
+    return result
+
+
 # ---- blended Gram targets (several style images) ------------------------------------
 
 def gram_blend(stack: torch.Tensor, weights, out: torch.Tensor | None = None) -> torch.Tensor:

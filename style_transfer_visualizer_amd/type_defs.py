@@ -12,6 +12,7 @@ Precision = Literal["fp32", "bf16", "bf16x3"]
 PreserveColor = Literal["off", "match", "luma"]
 ResizeFilter = Literal["bilinear", "bicubic", "lanczos"]
 Pooling = Literal["max", "avg"]
+AutoMaskSpace = Literal["color", "features"]
 GifDither = Literal["none", "ordered"]
 VideoFormat = Literal["mp4", "mjpeg"]
 LossHistory = dict[str, list[float]]
