@@ -36,7 +36,7 @@ extern "C" {
  * stv_conv_config, stv_conv_tune, stv_conv_uses_ws (always 0), stv_gram_partial and stv_gram_multi; every other
  * entry point returns STV_ERR_ARG for it.  K-blocked conv weights (STV_W_BLOCKED) are pre-split: each 16-byte group of
  * four fp32 weights holds their four bf16 hi parts, then their four bf16 lo parts (same byte count); plain-layout
- * weights are fp32 and split in the kernel: a 3x3 takes K-blocked weights only, a 1x1 plain weights only.  Size guards count bytes: every tensor stays below 2 GiB. */
+ * weights are fp32 and split in the kernel: a 3x3 takes K-blocked weights only, a 1x1 plain weights only.  Size guards count bytes (stv_conv_fits). */
 enum { STV_F32 = 0, STV_BF16 = 1, STV_BF16X3 = 2 };
 
 enum {
@@ -183,10 +183,28 @@ int stv_conv_igemm_dual(const void* x, const void* w, const void* x2, const void
 int stv_conv_igemm_route(const void* x, const void* w, const void* pool_idx, void* y_full, int H, int W, int cin,
                          int cout, int flags, int dtype, void* stream);
 
+/* The size guard of the conv entry points, as a query (host arithmetic, no device work; since version 119).  The
+ * kernels address every tensor with 32-bit byte offsets and use offset 2^31 for "nothing here", so every tensor of a
+ * launch may hold AT MOST 2^31 bytes (exactly 2 GiB is accepted, 16 bytes more are not).  Counted in bytes of the
+ * storage type (bf16 2, fp32 and bf16x3 4), per form:
+ *   every form        x [H][W][cin], y [H][W][cout] (also `ref` and the STV_ACCUM read-back, and also under
+ *                     STV_POOL_ONLY), w [taps][cout][cin], bias
+ *   STV_CONV_POOL     + y_pool [H/2][W/2][cout] and the byte map (both below y: they never decide)
+ *   STV_CONV_DUAL     + x2 [H][W][cin2], w2 [cout][cin2]   (cin2 > 0; every other form takes cin2 = 0)
+ *   STV_CONV_ROUTE    + y_full [2H][2W][cout] = 4 x y, and the byte map [H][W][cout]   (bf16 only)
+ * taps = 9, or 1 with STV_CONV_PLAIN.  STV_OK when stv_conv_igemm (PLAIN), _pool, _dual, _route would pass their size
+ * guard for this shape, else STV_ERR_ARG - the value those entry points return for such a shape before any HIP call.
+ * Says nothing about the other reasons an entry point refuses a shape (channel granularity, flags). */
+enum { STV_CONV_PLAIN = 0, STV_CONV_POOL = 1, STV_CONV_DUAL = 2, STV_CONV_ROUTE = 3 };
+int stv_conv_fits(int H, int W, int cin, int cout, int taps, int cin2, int form, int dtype);
+
 /* Which tile the dispatcher picks for a shape: -1 = scalar fallback (channel counts not a
  * multiple of the MFMA K-slice), else 0..3 = {8x128, 8x64, 4x128, 4x64} (rows x couts) and
  * 4 = 4x64 with K split over two wave groups, 5 = 8x64 and 6 = 4x64 with a two-deep LDS ring,
- * 7 = 2x64 and 8 = 1x64 (four waves) with the K split. */
+ * 7 = 2x64 and 8 = 1x64 (four waves) with the K split.
+ * -(100 + STV_ERR_ARG), like stv_conv_tune, for a shape the size guard refuses.  Both queries see neither a form nor
+ * cin2: with taps = 9 or 1 they answer for STV_CONV_PLAIN - which is also the answer for STV_CONV_POOL, whose extra
+ * tensors never decide - and with taps = STV_TUNE_ROUTE for STV_CONV_ROUTE; a dual launch asks stv_conv_fits. */
 int stv_conv_config(int H, int W, int cin, int cout, int taps, int dtype);
 
 /* 1 when stv_conv_igemm / _pool / _dual run this launch on the weight-stationary persistent kernel

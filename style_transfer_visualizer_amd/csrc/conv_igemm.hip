@@ -219,12 +219,10 @@ int launch_x3(const ConvArgs& a, hipStream_t st) {
 // step - plain fp32 weights that the kernel splits.
 bool x3_weights_ok(int taps, int flags) { return (taps == 9) == ((flags & STV_W_BLOCKED) != 0); }
 
-// The byte guard of the bf16x3 entry points: every tensor the kernel addresses through a 32-bit buffer descriptor
-// (input, output, reference map, weights, the second term's input and seed) must stay below 2 GiB in BYTES.
-bool x3_fits(int H, int W, int cin, int cout, int taps, int cin2 = 0) {
-  constexpr size_t kLimit = (size_t)1 << 31;
-  const size_t px = (size_t)H * W, cmax = (size_t)(cin > cout ? cin : cout) > (size_t)cin2 ? (size_t)(cin > cout ? cin : cout) : (size_t)cin2;
-  return px * cmax * 4 < kLimit && (size_t)taps * cin * cout * 4 < kLimit && (size_t)cin2 * cout * 4 < kLimit;
+// The size guard of every entry point below (conv_args.h: conv_fits - one byte count per descriptor and form).
+int elem_bytes(int dtype) { return dtype == STV_BF16 ? 2 : 4; }      // storage bytes (bf16x3: fp32 storage)
+bool fits(int H, int W, int cin, int cout, int taps, int dtype, int form = kFormPlain, int cin2 = 0) {
+  return conv_fits(H, W, cin, cout, taps, cin2, elem_bytes(dtype), form);
 }
 
 __global__ void tune_fill_kernel(uint32_t* p, size_t n_words, uint32_t seed) {
@@ -356,7 +354,15 @@ int tune_typed(int H, int W, int cin, int cout, int key_taps, hipStream_t st) {
 
 }  // namespace
 
+extern "C" int stv_conv_fits(int H, int W, int cin, int cout, int taps, int cin2, int form, int dtype) {
+  if (dtype != STV_F32 && dtype != STV_BF16 && dtype != STV_BF16X3) return STV_ERR_ARG;
+  return fits(H, W, cin, cout, taps, dtype, form, cin2) ? STV_OK : STV_ERR_ARG;
+}
+
 extern "C" int stv_conv_config(int H, int W, int cin, int cout, int taps, int dtype) {
+  const bool route = taps == kRouteTaps && dtype != STV_BF16X3;
+  if ((route || taps == 9 || taps == 1) && !fits(H, W, cin, cout, route ? 9 : taps, dtype, route ? kFormRoute : kFormPlain))
+    return -(100 + STV_ERR_ARG);
   if (dtype == STV_BF16X3) return (taps == 9 || taps == 1) ? choose_cfg(H, W, cin, cout, kX3Key, taps) : -1;
   return choose_cfg(H, W, cin, cout, dtype == STV_BF16 ? 2 : 4, taps);
 }
@@ -415,8 +421,9 @@ extern "C" int stv_conv_tune(int H, int W, int cin, int cout, int taps, int dtyp
   if (H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || (taps != 9 && taps != 1 && taps != kRouteTaps)) return -(100 + STV_ERR_ARG);
   if (dtype != STV_F32 && dtype != STV_BF16 && dtype != STV_BF16X3) return -(100 + STV_ERR_ARG);
   if (taps == kRouteTaps && dtype != STV_BF16) return -(100 + STV_ERR_ARG);
+  const bool route_key = taps == kRouteTaps;
+  if (!fits(H, W, cin, cout, route_key ? 9 : taps, dtype, route_key ? kFormRoute : kFormPlain)) return -(100 + STV_ERR_ARG);
   if (dtype == STV_BF16X3) {
-    if (!x3_fits(H, W, cin, cout, taps)) return -(100 + STV_ERR_ARG);
     if (cin % 8 || cout % 4) return -1;
     const char* mode = getenv("STV_CONV_TUNE");
     if (!mode || atoi(mode) <= 0) return choose_cfg(H, W, cin, cout, kX3Key, taps);
@@ -424,8 +431,6 @@ extern "C" int stv_conv_tune(int H, int W, int cin, int cout, int taps, int dtyp
     if (known >= 0) return known;
     return tune_typed<float, true>(H, W, cin, cout, taps, static_cast<hipStream_t>(stream));
   }
-  if ((size_t)H * W * (size_t)(cin > cout ? cin : cout) >= (size_t)1 << 31) return -(100 + STV_ERR_ARG);
-  if (taps == kRouteTaps && (size_t)4 * H * W * (size_t)cout * 2 >= (size_t)1 << 31) return -(100 + STV_ERR_ARG);
   const int esize = dtype == STV_BF16 ? 2 : 4;
   if ((cin % (32 / esize)) || (cout % (16 / esize))) return -1;          // direct-kernel shape: nothing to tune
   // STV_CONV_TUNE: unset = use the table (imported + measured so far), never measure; 0 = analytic choice only;
@@ -445,15 +450,15 @@ extern "C" int stv_conv_igemm(const void* x, const void* w, const float* bias, c
   if ((flags & STV_MASK) && !ref) return STV_ERR_ARG;
   if (flags & STV_POOL_ONLY) return STV_ERR_ARG;          // only stv_conv_igemm_pool has a pooled map to write instead of y
   if (taps != 9 && taps != 1) return STV_ERR_ARG;
+  if (!fits(H, W, cin, cout, taps, dtype)) return STV_ERR_ARG;
   if (dtype == STV_BF16X3) {
-    if (!x3_fits(H, W, cin, cout, taps) || !x3_weights_ok(taps, flags)) return STV_ERR_ARG;
+    if (!x3_weights_ok(taps, flags)) return STV_ERR_ARG;
     ConvArgs a{x, w, bias, ref, y, H, W, cin, cout, flags, nullptr, nullptr, nullptr, nullptr, 0};
     hipStream_t st = static_cast<hipStream_t>(stream);
     return taps == 9 ? launch_x3<9>(a, st) : launch_x3<1>(a, st);
   }
   // the direct fallback (shapes the matrix-core tiling does not cover) reads plain weights only
   if ((flags & STV_W_BLOCKED) && choose_cfg(H, W, cin, cout, dtype == STV_F32 ? 4 : 2, taps) < 0) return STV_ERR_ARG;
-  if ((size_t)H * W * (size_t)(cin > cout ? cin : cout) >= (size_t)1 << 31) return STV_ERR_ARG;
   ConvArgs a{x, w, bias, ref, y, H, W, cin, cout, flags, nullptr, nullptr, nullptr, nullptr, 0};
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dtype == STV_F32)
@@ -469,9 +474,9 @@ extern "C" int stv_conv_igemm_pool(const void* x, const void* w, const float* bi
   if (!x || !w || !y_pool || H <= 1 || W <= 1 || cin <= 0 || cout <= 0) return STV_ERR_ARG;
   if (!y && !(flags & STV_POOL_ONLY)) return STV_ERR_ARG;
   if (flags & (STV_MASK | STV_ACCUM)) return STV_ERR_ARG;                     // forward convolutions only
-  if ((size_t)H * W * (size_t)(cin > cout ? cin : cout) >= (size_t)1 << 31) return STV_ERR_ARG;
+  if (!fits(H, W, cin, cout, 9, dtype, kFormPool)) return STV_ERR_ARG;
   if (dtype == STV_BF16X3) {
-    if (!x3_fits(H, W, cin, cout, 9) || !x3_weights_ok(9, flags) || choose_cfg(H, W, cin, cout, kX3Key, 9) < 0) return STV_ERR_ARG;
+    if (!x3_weights_ok(9, flags) || choose_cfg(H, W, cin, cout, kX3Key, 9) < 0) return STV_ERR_ARG;
     ConvArgs a{x, w, bias, nullptr, y, H, W, cin, cout, flags, y_pool, pool_idx, nullptr, nullptr, 0};
     return launch_x3<9>(a, static_cast<hipStream_t>(stream));
   }
@@ -497,8 +502,7 @@ extern "C" int stv_conv_igemm_route(const void* x, const void* w, const void* po
   if (!x || !w || !pool_idx || !y_full || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return STV_ERR_ARG;
   if (dtype != STV_BF16) return STV_ERR_ARG;                                   // packed-word routing: bf16 storage only
   if (flags & (STV_RELU_IN | STV_RELU_OUT | STV_ACCUM | STV_POOL_ONLY)) return STV_ERR_ARG;
-  // 32-bit buffer offsets: the input (H x W x cin) and the routed output (2H x 2W x cout), bf16
-  if ((size_t)H * W * (size_t)cin * 2 >= (size_t)1 << 31 || (size_t)4 * H * W * (size_t)cout * 2 >= (size_t)1 << 31) return STV_ERR_ARG;
+  if (!fits(H, W, cin, cout, 9, dtype, kFormRoute)) return STV_ERR_ARG;       // (the routed output, 2H x 2W x cout, counts)
   if (choose_cfg(H, W, cin, cout, 2, kRouteTaps) < 0) return STV_ERR_ARG;
   ConvArgs a{x, w, nullptr, nullptr, y_full, H, W, cin, cout, flags, nullptr, nullptr, nullptr, nullptr, 0};
   a.route_idx = pool_idx;
@@ -514,15 +518,14 @@ extern "C" int stv_conv_igemm_dual(const void* x, const void* w, const void* x2,
   if (!x || !w || !x2 || !w2 || !y || H <= 0 || W <= 0 || cin <= 0 || cin2 <= 0 || cout <= 0) return STV_ERR_ARG;
   if ((flags & STV_MASK) && !ref) return STV_ERR_ARG;
   if (flags & (STV_RELU_IN | STV_RELU_OUT | STV_POOL_ONLY)) return STV_ERR_ARG;   // a gradient path: no activations, no pooled output
+  if (!fits(H, W, cin, cout, 9, dtype, kFormDual, cin2)) return STV_ERR_ARG;
   if (dtype == STV_BF16X3) {
-    if (!x3_fits(H, W, cin, cout, 9, cin2) || !x3_weights_ok(9, flags) || choose_cfg(H, W, cin, cout, kX3Key, 9) < 0 || cin2 % 8)
+    if (!x3_weights_ok(9, flags) || choose_cfg(H, W, cin, cout, kX3Key, 9) < 0 || cin2 % 8)
       return STV_ERR_ARG;
     ConvArgs a{x, w, nullptr, ref, y, H, W, cin, cout, flags, nullptr, nullptr, x2, w2, cin2};
     return launch_x3<9>(a, static_cast<hipStream_t>(stream));
   }
   if (dtype != STV_F32 && dtype != STV_BF16) return STV_ERR_ARG;
-  const size_t cmax = (size_t)(cin > cout ? cin : cout) > (size_t)cin2 ? (size_t)(cin > cout ? cin : cout) : (size_t)cin2;
-  if ((size_t)H * W * cmax >= (size_t)1 << 31) return STV_ERR_ARG;
   const int es = dtype == STV_F32 ? 4 : 2;
   // both terms run in the matrix-core kernel: its channel granularity applies to both K extents
   if (choose_cfg(H, W, cin, cout, es, 9) < 0 || cin2 % (32 / es)) return STV_ERR_ARG;

@@ -34,6 +34,11 @@ extern thread_local uint32_t g_stv_next_w_bytes;
 
 namespace {
 
+// bytes of an [a][b][c] tensor of T as a descriptor's 32-bit record count
+template <typename T>
+__device__ __forceinline__ uint32_t map_bytes(int a, int b, int c) {
+  return (uint32_t)(a * b * c) * (uint32_t)sizeof(T);      // (the element count is below 2^31; only the byte count reaches it)
+}
 
 template <typename T, int TH_, int BN_, int WM_, int WN_, int TAPS_, int KS_ = 1, int NBUF_ = 3, bool M16_ = false,
           bool X3_ = false>
@@ -197,9 +202,11 @@ __device__ __forceinline__ void conv_mainloop(const Phase<typename C::Elem>& ph,
   const int x0 = gm.x0, y0 = gm.y0, n0 = gm.n0;
   const int nchunks = ph.cin / C::CK;
   // ---- DMA pieces of this wave: per-lane source byte offsets (out of range -> zero fill) ----
-  constexpr uint32_t kOob = 0x80000000u;   // >= num_records for every tensor this kernel accepts
-  const int x_bytes = gm.H * gm.W * ph.cin * (int)sizeof(T);
-  const int w_bytes = C::TAPS * gm.cout * ph.cin * (int)sizeof(T);
+  // kOob: >= num_records for every tensor this kernel accepts (conv_args.h: conv_fits holds every record count to
+  // <= 2^31 bytes).  The counts are formed in uint32_t: a tensor of exactly 2^31 bytes is a valid count, not an int.
+  constexpr uint32_t kOob = 0x80000000u;
+  const uint32_t x_bytes = map_bytes<T>(gm.H, gm.W, ph.cin);
+  const uint32_t w_bytes = map_bytes<T>(C::TAPS, gm.cout, ph.cin);
   // bytes from one K-stage to the next: 32 along a pixel's (or plain weight row's) channels,
   // a whole [cout][CK] slab in the K-blocked weight layout
   const int w_stride = ph.w_blocked ? gm.cout * C::KB : C::KB;
@@ -239,7 +246,7 @@ __device__ __forceinline__ void conv_mainloop(const Phase<typename C::Elem>& ph,
     const bool in = g < C::IN_PIECES;
     const bool live = g < C::PIECES && stage < nchunks && !(STV_DIAG & 1);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<T*>(in ? ph.x : ph.w), 0, live ? (in ? x_bytes : w_bytes) : 0, 0x00020000);
+        const_cast<T*>(in ? ph.x : ph.w), 0, live ? (int)(in ? x_bytes : w_bytes) : 0, 0x00020000);
     char* dst = buf + (g < C::PIECES ? g * 1024 : C::SPARE_OFF);
     if (STV_X_AUX != 0 && in) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)dst, 16, p_off[j], stage * C::KB, 0, STV_X_AUX);
     else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)dst, 16, p_off[j], stage * (in ? C::KB : w_stride), 0, 0);
@@ -442,8 +449,8 @@ __device__ __forceinline__ void conv_mainloop16(const Phase<bf16_t>& ph, const G
   const int nchunks = ph.cin / C::CK;              // 16-channel K-stages (even: the host checks cin % 32 == 0)
   const int npairs = nchunks >> 1;
   constexpr uint32_t kOob = 0x80000000u;
-  const int x_bytes = gm.H * gm.W * ph.cin * (int)sizeof(T);
-  const int w_bytes = C::TAPS * gm.cout * ph.cin * (int)sizeof(T);
+  const uint32_t x_bytes = map_bytes<T>(gm.H, gm.W, ph.cin);
+  const uint32_t w_bytes = map_bytes<T>(C::TAPS, gm.cout, ph.cin);
   const int w_stride = ph.w_blocked ? gm.cout * C::KB : C::KB;
   auto piece_id = [&](int j) { return j * C::NWAVES + wave; };                  // wave-uniform
   uint32_t p_off[C::PPW];
@@ -479,7 +486,7 @@ __device__ __forceinline__ void conv_mainloop16(const Phase<bf16_t>& ph, const G
     const bool in = g < C::IN_PIECES;
     const bool live = g < C::PIECES && stage < nchunks && !(STV_DIAG & 1);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<T*>(in ? ph.x : ph.w), 0, live ? (in ? x_bytes : w_bytes) : 0, 0x00020000);
+        const_cast<T*>(in ? ph.x : ph.w), 0, live ? (int)(in ? x_bytes : w_bytes) : 0, 0x00020000);
     char* dst = pair + sub * C::STAGE_BYTES + (g < C::PIECES ? g * 1024 : C::SPARE_OFF);
     if (STV_X_AUX != 0 && in) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)dst, 16, p_off[j], stage * C::KB, 0, STV_X_AUX);
     else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)dst, 16, p_off[j], stage * (in ? C::KB : w_stride), 0, 0);
@@ -689,8 +696,8 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
   if constexpr (C::TAPS == 9) {
     if (a.x2 != nullptr) {
       if (a.flags & STV_MASK) {
-        const int ref_bytes = a.H * a.W * a.cout * (int)sizeof(T);
-        const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.ref), 0, ref_bytes, 0x00020000);
+        const uint32_t ref_bytes = map_bytes<T>(a.H, a.W, a.cout);
+        const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.ref), 0, (int)ref_bytes, 0x00020000);
 #pragma unroll
         for (int mt = 0; mt < C::MT; ++mt) {
           const int gy = y0 + wm * C::MT + mt, gx = x0 + r;
@@ -735,7 +742,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
   const bool relu_out = (a.flags & STV_RELU_OUT) != 0;
   const bool do_mask = (a.flags & STV_MASK) != 0 && !mask_done && a.route_out == nullptr;
   const bool do_acc = (a.flags & STV_ACCUM) != 0;
-  const int out_bytes = a.H * a.W * a.cout * (int)sizeof(T);
+  const int out_bytes = (int)map_bytes<T>(a.H, a.W, a.cout);         // (the descriptor's 32-bit count: 2^31 is the bit pattern INT_MIN)
   const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y != nullptr ? out_bytes : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_ref = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(a.ref), 0, do_mask ? out_bytes : 0, 0x00020000);
@@ -744,7 +751,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
   const bool route_mask = (a.flags & STV_MASK) != 0 && route;        // with a route, MASK names the pre-pool ReLU
   const __amdgpu_buffer_rsrc_t rs_ridx = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(a.route_idx), 0, route ? a.H * a.W * a.cout : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_route = __builtin_amdgcn_make_buffer_rsrc(a.route_out, 0, route ? 4 * out_bytes : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_route = __builtin_amdgcn_make_buffer_rsrc(a.route_out, 0, route ? (int)(4u * (uint32_t)out_bytes) : 0, 0x00020000);
 
   if (C::KS == 2) {               // the second K group hands its partial sums over through LDS
     float* cs = reinterpret_cast<float*>(smem);
@@ -848,7 +855,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
                 const uint32_t ioff = off != kOob ? (off >> 1) : kOob;       // byte map: same element index
                 const auto ib = __builtin_amdgcn_raw_buffer_load_b64(rs_ridx, ioff, 0, 0);
                 const int gy = y0 + wm * C::MT + mt, gx = x0 + r;            // (only the full-resolution map is ever routed)
-                const uint32_t base = (uint32_t)((((2 * gy) * (2 * a.W) + 2 * gx) * a.cout + nn) * 2);
+                const uint32_t base = (uint32_t)(((2 * gy) * (2 * a.W) + 2 * gx) * a.cout + nn) * 2u;    // (dead rows: may pass 2^31, unused)
 #pragma unroll
                 for (int pos = 0; pos < 4; ++pos) {
                   uint32_t keep[4];
@@ -891,7 +898,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_igemm_kernel(ConvArgs a) {
     // max'ed sums - no second pass over HBM.  Even lanes store pooled pixel r / 2.
     if constexpr (C::MT % 2 == 0) if (a.pool != nullptr) {     // (a wave must own both rows of a pooling window)
       const int Hp = a.H >> 1, Wp = a.W >> 1;
-      const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(a.pool, 0, Hp * Wp * a.cout * (int)sizeof(T), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(a.pool, 0, (int)map_bytes<T>(Hp, Wp, a.cout), 0x00020000);
       // the pooled sums are formed where they are consumed (a [MT/2][NT] array of them would be 64 more registers on
       // the 16x128 tile, on top of 128 accumulators: it spilled)
       auto pooled = [&](int mp, int nt, int i) -> float {

@@ -128,7 +128,7 @@ int run_all(stv_program* p, void* st) {
 
 }  // namespace
 
-extern "C" int stv_version(void) { return 118; }
+extern "C" int stv_version(void) { return 119; }
 
 extern "C" int stv_program_create(const stv_op_t* ops, int n_ops, stv_program** out) {
   if (!ops || n_ops <= 0 || !out) return STV_ERR_ARG;

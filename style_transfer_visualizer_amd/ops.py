@@ -106,6 +106,16 @@ def conv_uses_ws(H: int, W: int, cin: int, cout: int, dtype: torch.dtype, *, fla
     return bool(_lib.load().stv_conv_uses_ws(H, W, cin, cout, 9, dtype_code(dtype), flags, int(has_ref), int(has_pool)))
 
 
+CONV_MAX_BYTES = 2 ** 31      # what one tensor of a conv launch may hold (stv.h stv_conv_fits: 32-bit byte offsets)
+CONV_PLAIN, CONV_POOL, CONV_DUAL, CONV_ROUTE = 0, 1, 2, 3      # stv.h STV_CONV_*: the forms stv_conv_fits answers for
+
+
+def conv_fits(H: int, W: int, cin: int, cout: int, dtype: torch.dtype, *, form: int = CONV_PLAIN, taps: int = 9,
+              cin2: int = 0, split: bool = False) -> bool:
+    """True when the conv entry point of ``form`` passes its size guard for this shape (stv_conv_fits: host arithmetic)."""
+    return int(_lib.load().stv_conv_fits(H, W, cin, cout, taps, cin2, form, dtype_code(dtype, split=split))) == 0
+
+
 TUNE_ROUTE = 109      # stv.h STV_TUNE_ROUTE: `taps` value that tunes the shape as conv_igemm_route runs it
 
 

@@ -225,6 +225,18 @@ class Schedule:
         act = torch.empty(H, W, C, device=self.device, dtype=self.dtype)
         return Buf(H, W, C, act)
 
+    def _check_map(self, layer: int, H: int, W: int, C: int) -> None:
+        """Refuses a conv whose output map the conv kernels cannot address (32-bit byte offsets: ops.CONV_MAX_BYTES per
+        tensor, include/stv.h stv_conv_fits).  Every activation of a schedule is such a map or a pooled, smaller one."""
+        rows = H + 2 * self.halo
+        nbytes = rows * W * C * torch.empty(0, dtype=self.dtype).element_size()
+        if nbytes > ops.CONV_MAX_BYTES:
+            name = {torch.bfloat16: "bf16", torch.float32: "fp32"}.get(self.dtype, str(self.dtype))
+            ways = ("" if self.dtype == torch.bfloat16 else "bf16 storage, ") + "a smaller image size, or row strips on several GPUs"
+            msg = (f"layer {layer}: its {rows}x{W}x{C} {name} map holds {nbytes} bytes, over the conv kernels' limit of "
+                   f"{ops.CONV_MAX_BYTES} bytes per tensor (32-bit offsets): use {ways}")
+            raise ValueError(msg)
+
     def interior(self, t: torch.Tensor) -> torch.Tensor:
         """The strip's own rows of an NHWC buffer (the whole buffer without halos)."""
         return t[self.halo:t.shape[0] - self.halo] if self.halo else t
@@ -242,6 +254,7 @@ class Schedule:
             out_idx = i
             if kind == "conv":
                 conv: nn.Conv2d = layers[i]
+                self._check_map(i, H, W, conv.out_channels)      # before anything of this layer is allocated
                 w = conv.weight.detach().to(self.device, torch.float32)
                 bias = (conv.bias.detach().to(self.device, torch.float32).contiguous()
                         if conv.bias is not None else None)
@@ -427,8 +440,7 @@ class Schedule:
         return (self.switches.fuse_pool_bwd and pool_nd.kind == "pool" and pool_nd.idx is not None
                 and self.dtype == torch.bfloat16 and not s.taps and not nd.relu_in and not s.relu_fused
                 and pool_nd.src.H == 2 * s.H and pool_nd.src.W == 2 * s.W
-                and 4 * s.act.numel() * s.act.element_size() < 2 ** 31
-                and d.act.numel() * d.act.element_size() < 2 ** 31)
+                and ops.conv_fits(s.H, s.W, d.C, s.C, self.dtype, form=ops.CONV_ROUTE))
 
     def _partials(self, tap: Tap) -> torch.Tensor:
         """The split-K Gram slabs of a style tap (scratch, allocated at first use)."""

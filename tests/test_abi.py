@@ -27,7 +27,10 @@ def test_library_loads_and_exports_every_declared_symbol():
 
 def test_version_and_sizing_helpers_run_without_gpu():
     lib = _lib.load()
-    assert lib.stv_version() >= 100
+    assert lib.stv_version() >= 119
+    # the conv size guard as a query (version 119): 4096^2 x 64 is 2 GiB in bf16 and 4 GiB in fp32
+    assert lib.stv_conv_fits(4096, 4096, 64, 64, 9, 0, 0, _lib.STV_BF16) == 0
+    assert lib.stv_conv_fits(4096, 4096, 64, 64, 9, 0, 0, _lib.STV_F32) == 1
     # pure host arithmetic, no device work
     assert lib.stv_gram_ksplit(1 << 20, 64) >= 1
     assert lib.stv_gram_partials_bytes(4096, 512) == lib.stv_gram_ksplit(4096, 512) * 512 * 512 * 4

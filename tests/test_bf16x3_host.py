@@ -86,7 +86,10 @@ def test_storage_only_entry_points_reject_bf16x3():
 
 
 def test_byte_guard_counts_bytes():
-    """4096 x 4096 x 64 fp32 = 4 GiB: 2^30 elements pass an element count, the 32-bit byte descriptors do not."""
+    """4096 x 4096 x 64 fp32 = 4 GiB: 2^30 elements pass an element count, the 32-bit byte descriptors do not.
+    (Every form, precision and tensor on both sides of the bound: tests/test_conv_limits_host.py, which holds the
+    library's one predicate to a second writing of the byte counts; the maps of exactly 2^31 bytes on the GPU:
+    tests/test_gpu_conv_limits.py.)"""
     lib = _lib.load()
     p = ctypes.c_void_p(16)
     assert lib.stv_conv_igemm(p, p, None, None, p, 4096, 4096, 64, 64, 9, 0, _lib.STV_BF16X3, None) == 1
