@@ -9,6 +9,11 @@ mutations, in tests/test_layerwise_host.py).  The matrix cases then run the prod
 pre-pool maps not stored, graph replay) and require bit-identical scores, image gradient and stored tensors.  Every
 case asserts the schedule decisions it exists for.  Weights carry a non-zero bias per layer.
 
+The structures that joined the step later - average pooling, spatial guidance (one Gram chain and one gradient term per
+region), style layer weights, the Laplacian terms - run as the rows of ``lw.STEP_CASES`` through the same three steps:
+checked run, decisions, product defaults.  Their sizes: 40x24 (odd pooled maps: rows and columns an average pool drops),
+64x48 (three regions all present at the 4x3 tap), 42x26 (image rows and columns outside the Laplacian's cells).
+
 Sizes: 64x48 (non-square, four pools down to 4x3), 32x32 (the deepest map is 2x2), 40x24 (pooled maps become odd: 5x3
 in front of the fourth pool, whose backward can then not ride in a dgrad - routed and unrouted pools in one schedule).
 """
@@ -19,7 +24,7 @@ import functools
 import pytest
 import torch
 
-from style_transfer_visualizer_amd import _lib, core_model, synthetic
+from style_transfer_visualizer_amd import _lib, core_model, guidance, synthetic
 from tests import layerwise as lw
 from tests.conftest import record_parity
 
@@ -305,3 +310,192 @@ def test_total_variation_term_joins_the_checked_image_gradient(monkeypatch):
     _, eng, _, _ = _checked_step(monkeypatch, "step default 32x32 bf16 tv_w=50", lw.LAYOUTS["default"], "bf16", 32, 32, tv_w=50.0)
     prog = _fused_program(eng)
     assert len(_ops(prog, _lib.OP_TV)) == 2 and _ops(prog, _lib.OP_TV)[1] == _ops(prog, _lib.OP_CONV_FIRST_DGRAD)[0] + 1
+
+
+# ------------------------------------- average pooling, spatial guidance, layer weights, Laplacian terms (lw.STEP_CASES)
+def _case_model(monkeypatch, name: str, precision: str, **env):
+    """The model of one ``lw.STEP_CASES`` row with targets set, a fresh leaf image on the device, the host image."""
+    spec = lw.STEP_CASES[name]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    weights = _weights(synthetic.VGG19_CFG)
+    monkeypatch.setattr(core_model, "initialize_vgg", lambda: core_model.build_vgg_features(weights, synthetic.VGG19_CFG).eval())
+    style_at, content_at = lw.case_layout(spec)
+    H, W = spec["size"]
+    R = spec.get("regions", 0)
+    kw = {}
+    if R:
+        kw.update(guide_regions=R, region_weights=list(lw.REGION_WEIGHTS[R]))
+    if "layer_w" in spec:
+        kw["style_layer_weights"] = list(spec["layer_w"])
+    if "lap_pools" in spec:
+        kw["lap_pools"] = spec["lap_pools"]
+    model = core_model.StyleContentModel(list(style_at), list(content_at), precision=precision, pooling=spec.get("pooling", "max"), **kw).to(DEV)
+    style, content, x0 = _images(H, W)
+    labels = {}
+    if R:
+        content_labels, style_labels = lw.guide_labels(R, H, W)
+        labels = dict(content_labels=content_labels, style_labels=style_labels)
+        # the label maps by the model's own down-sampling: every region present at every tap, the deepest (4x3) included
+        for which in (content_labels, style_labels):
+            shapes = guidance.tap_shapes(H, W, synthetic.VGG19_CFG, style_at)
+            counts = guidance.check_counts(guidance.tap_maps(which, shapes), R, "content")
+            assert all(min(row) >= 1 for row in counts) and bool((which == guidance.NO_REGION).any())
+    model.set_targets(style.to(DEV), content.to(DEV), **labels)
+    return model, x0.to(DEV).requires_grad_(True), x0
+
+
+def _step(model, x, spec) -> tuple:
+    scores = tuple(float(v) for v in model.loss_and_grad(x, STYLE_W, CONTENT_W, tv_w=spec.get("tv_w", 0.0), lap_w=spec.get("lap_w", 0.0)))
+    torch.cuda.synchronize()
+    return scores
+
+
+def _op_at(prog, i: int) -> int:
+    return prog.op_meta[i][0]
+
+
+def _assert_avg(prog, eng, name):
+    nodes = eng.sched.nodes
+    pools = [nd for nd in nodes if nd.kind in ("pool", "avgpool")]
+    assert pools and all(nd.kind == "avgpool" and not nd.fused and nd.idx is None for nd in pools)
+    assert all(nd.route is None for nd in nodes) and all(nd.dst.stored for nd in nodes)
+    assert len(_ops(prog, _lib.OP_AVGPOOL_FWD)) == len(_ops(prog, _lib.OP_AVGPOOL_BWD)) == len(pools)
+    assert not _ops(prog, _lib.OP_POOL_FWD) and not _ops(prog, _lib.OP_POOL_BWD)
+    for nd in pools:                     # rows and columns the floor drops, as the only writer: +0
+        s = nd.src
+        if not s.taps and (s.H % 2 or s.W % 2):
+            assert not bool(s.grad[2 * (s.H // 2):].any()) and not bool(s.grad[:, 2 * (s.W // 2):].any())
+    accum = [i for i in _ops(prog, _lib.OP_AVGPOOL_BWD) if prog.op_flags[i] & _lib.ACCUM]
+    if name == "avg default":
+        assert any(nd.src.H % 2 and nd.src.W % 2 and not nd.src.taps for nd in pools) and not accum
+    if name == "avg pending relu":      # (the layout ends at layer 7: one pool, behind the tapped conv 2)
+        assert [nd.relu_in for nd in pools] == [True]
+    if name == "avg content7":
+        assert [nd.layer for nd in pools if nd.relu_in] == [9] and len(pools) == 4
+    if name == "avg pool taps":
+        assert [(nd.layer, nd.kind) for nd in nodes if nd.dst.taps] == [(4, "avgpool"), (9, "avgpool"), (18, "avgpool")]
+    if name == "avg shared buffer":     # the dgrad of conv 7 accumulates onto the content gradient the forward half wrote
+        assert any(prog.op_flags[i] & _lib.ACCUM for i in _ops(prog, _lib.OP_CONV) if prog.op_meta[i][5] == 9)
+    if name == "avg prepool":           # and here the pool's own backward does
+        assert len(accum) >= 1 and all(t.grad_fused for t in eng.sched.content_taps)
+
+
+def _assert_guided(prog, eng, rep, name):
+    s, R = eng.sched, eng.guide.n
+    products = [i for i in _ops(prog, _lib.OP_CONV) if prog.op_meta[i][5] == 1]
+    assert len(_ops(prog, _lib.OP_MASK_SPLIT)) == len(s.style_taps) and len(products) == R * len(s.style_taps)
+    assert all(nd.gram is None for nd in s.nodes) and not any(t.partials_fused for t in s.style_taps)
+    multi = [prog.op_meta[i][6] for i in _ops(prog, _lib.OP_GRAM_MULTI)]
+    chains = R * len(s.style_taps)
+    assert multi == [min(8, chains - k) for k in range(0, chains, 8)] and len(s.all_chains()) == chains
+    if name == "guided R=3":
+        assert multi == [8, 7]
+    tapped = {f"grad L{nd.layer:02d} {nd.kind}" for nd in s.nodes if any(t.kind == "style" for t in nd.dst.taps)
+              and (R > 1 or nd is not s.nodes[-1])}
+    assert tapped <= set(rep.multi_stage)
+    # only the very first product of the chain (the deepest tap's first region) stores
+    assert [bool(prog.op_flags[i] & _lib.ACCUM) for i in products] == [bool(s.nodes[-1].dst.taps[0].kind != "style")] + [True] * (len(products) - 1)
+    if name == "guided relu taps":      # one in-place mask per tapped ReLU output, behind the last of its R products
+        masked = [nd.layer for nd in s.nodes if nd.dst.relu_fused and any(t.kind == "style" for t in nd.dst.taps)]
+        behind = [i for i in _ops(prog, _lib.OP_RELU_BWD) if all(j in products for j in range(i - R, i))]
+        relus = [nd.layer for nd in s.nodes if nd.kind == "relu"]     # (the backward of the materialised ReLU follows its output's products too)
+        assert masked == [5, 10] and relus == [1] and len(behind) == 3 and all(i + 1 not in products for i in behind)
+        assert len(_ops(prog, _lib.OP_RELU_BWD)) == 4                  # and the mask behind the content term of conv 21
+    if name == "guided shared buffer":  # content gradient written in the forward half, then the dgrad and R products accumulate
+        shared = next(nd for nd in s.nodes if nd.layer == 5).dst
+        assert sorted(t.kind for t in shared.taps) == ["content", "style"] and all(t.grad_fused for t in s.content_taps)
+        assert any(prog.op_flags[i] & _lib.ACCUM for i in _ops(prog, _lib.OP_CONV) if prog.op_meta[i][5] == 9)
+
+
+def _assert_lap(prog, eng, spec):
+    tv = 1 if spec.get("tv_w") else 0
+    n = len(spec["lap_pools"])
+    lap, dgrad = _ops(prog, _lib.OP_LAP), _ops(prog, _lib.OP_CONV_FIRST_DGRAD)[0]
+    assert len(lap) == 2 * n and lap[:n] == list(range(tv, tv + n))                      # LOSS forms at the head, behind TV's
+    assert lap[n:] == list(range(dgrad + 1 + tv, dgrad + 1 + tv + n))                    # GRAD forms behind the dgrad and TV
+    assert all(prog.op_meta[i][5] == _lib.LAP_LOSS for i in lap[:n]) and all(prog.op_meta[i][5] == _lib.LAP_GRAD for i in lap[n:])
+    assert all(prog.op_flags[i] & _lib.ACCUM for i in lap[n:]) and [prog.op_meta[i][4] for i in lap[n:]] == list(spec["lap_pools"])
+    if tv:
+        assert _ops(prog, _lib.OP_TV) == [0, dgrad + 1]
+
+
+@pytest.mark.parametrize(("name", "precision"), lw.STEP_PARAMS, ids=lambda v: v.replace(" ", "-"))
+def test_every_stored_tensor_of_the_new_structures(name, precision, monkeypatch):
+    spec = lw.STEP_CASES[name]
+    H, W = spec["size"]
+    case = f"step {name} {H}x{W} {precision}"
+    model, x, x0 = _case_model(monkeypatch, name, precision, **CHECK_ENV)
+    scores = _step(model, x, spec)
+    eng = _engine(model)
+    rep = lw.check_step(eng, x0, style_w=STYLE_W, content_w=CONTENT_W, x_grad=x.grad, tv_w=spec.get("tv_w", 0.0),
+                        lap_w=spec.get("lap_w", 0.0), layer_w=spec.get("layer_w"), record=record_parity, case=case)
+    grad = x.grad.clone()
+    regions = model.last_region_losses().clone() if eng.guide is not None else None
+    prog = _fused_program(eng)
+    # ---- the decisions this case exists for
+    if spec.get("pooling") == "avg":
+        _assert_avg(prog, eng, name)
+    if eng.guide is not None:
+        _assert_guided(prog, eng, rep, name)
+    if "layer_w" in spec:                # the zero-weight tap: every seed of it is a zero
+        for c in eng.sched.all_chains():
+            parent = c.parent if c.parent is not None else c
+            assert bool((c.sgrad == 0).all()) == (spec["layer_w"][parent.order] == 0.0)
+    if "lap_pools" in spec:
+        _assert_lap(prog, eng, spec)
+        # pixels outside every pool's cells carry the dgrad (+ TV) value bit for bit: the same step without the term
+        model.loss_and_grad(x, STYLE_W, CONTENT_W, tv_w=spec.get("tv_w", 0.0))
+        torch.cuda.synchronize()
+        outside = torch.ones(H, W, dtype=torch.bool, device=DEV)
+        for p in spec["lap_pools"]:
+            outside[:H // p * p, :W // p * p] = False
+        assert torch.equal(x.grad[..., outside], grad[..., outside])
+        assert bool(outside.any()) == all(H % p or W % p for p in spec["lap_pools"])
+        assert not torch.equal(x.grad, grad)
+    # ---- the product's defaults: gradient slabs, dead pre-pool maps not stored, graph replay
+    model2, x2, _ = _case_model(monkeypatch, name, precision, STV_GRAD_ARENA="1", STV_SKIP_PREPOOL="1", STV_HIP_GRAPH="1")
+    scores2 = _step(model2, x2, spec)
+    eng2 = _engine(model2)
+    assert eng2.use_graph and eng2.sched.grad_arena
+    assert scores2 == scores
+    assert torch.equal(x2.grad, grad)
+    skipped = 0
+    for nd, nd2 in zip(eng.sched.nodes, eng2.sched.nodes, strict=True):
+        if nd2.dst.stored:
+            assert torch.equal(nd.dst.act, nd2.dst.act), f"L{nd.layer:02d} {nd.kind}: stored activation differs"
+        skipped += not nd2.dst.stored
+    for t, t2 in zip(eng.sched.all_chains(), eng2.sched.all_chains(), strict=True):
+        assert torch.equal(t.sgrad, t2.sgrad), f"Gram chain {t.order}: seed differs"
+    if eng.guide is not None:
+        for t, t2 in zip(eng.sched.style_taps, eng2.sched.style_taps, strict=True):
+            assert torch.equal(t.slabs, t2.slabs), f"style tap {t.order}: region slabs differ"
+        assert torch.equal(model2.last_region_losses(), regions)
+    for r, r2 in zip(eng.lap_resid, eng2.lap_resid, strict=True):
+        assert torch.equal(r, r2)
+    record_parity(case, "product defaults vs the checked run", 0.0, 0.0,
+                  f"bit-identical scores, image gradient, seeds, slabs, residuals, {len(eng.sched.nodes) - skipped} activations; "
+                  f"{skipped} pre-pool maps not stored, {eng2.sched._grad_slabs.shape[0]} gradient slabs")
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_autograd_path_with_average_pooling(precision, monkeypatch):
+    H, W = 40, 24
+    taps = lw.LAYOUTS["default"]
+    monkeypatch.setattr(core_model, "initialize_vgg",
+                        lambda: core_model.build_vgg_features(_weights(synthetic.VGG19_CFG), synthetic.VGG19_CFG).eval())
+    for k, v in CHECK_ENV.items():
+        monkeypatch.setenv(k, v)
+    model = core_model.StyleContentModel(list(taps[0]), list(taps[1]), precision=precision, pooling="avg").to(DEV)
+    style, content, x0 = _images(H, W)
+    model.set_targets(style.to(DEV), content.to(DEV))
+    x = x0.to(DEV).requires_grad_(True)
+    n = len(taps[0]) + len(taps[1])
+    gout = [3e4 * (1.0 + 0.37 * i) for i in range(n)]
+    style_l, content_l = model(x)
+    sum(w * v for w, v in zip(gout, list(style_l) + list(content_l))).backward()
+    torch.cuda.synchronize()
+    eng = _engine(model)
+    assert eng.pooling == "avg" and sum(nd.kind == "avgpool" for nd in eng.sched.nodes) == 4
+    lw.check_step(eng, x0, style_w=1.0, content_w=1.0, x_grad=x.grad, gout=gout, record=record_parity,
+                  case=f"autograd avg default {H}x{W} {precision}")

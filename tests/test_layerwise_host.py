@@ -13,17 +13,30 @@ kernels round.  Asserted:
   pre-written content gradient overwritten by the pooling backward routed onto it) fails, naming the mutated tensor;
 * the schedule's decision fields are consulted per node: where a field takes both values in one schedule, reading it
   as one global value fails.
+
+The same three for the structures of ``lw.STEP_CASES`` - average pooling, spatial guidance, style layer weights, the
+Laplacian terms.  The stand-in has ``avgpool_fwd`` / ``avgpool_bwd`` (the header's summation order; RELU_IN, MASK, ACCUM),
+``mask_split`` and ``lap`` (LOSS and GRAD); its Gram finish resolves a chain over ``s.all_chains()`` and divides by the op's
+own norm; ``set_targets`` forms the per-region targets by the float64 definition of tests/guidance_ref.py and the pooled
+Laplacian targets; ``fused_step`` builds the op list as ``_Engine.loss_and_grad`` does.  Mutations: pairwise summation in
+the pool, a lost or misplaced mask, a lost ACCUM and a written odd tail in its backward; label 255 copied into slab 0 and
+two slabs swapped; a region norm from the parent's pixel count (in the op, and in the schedule), two region weights
+swapped, the second region's product without ACCUM, a region's product applied twice, the ReLU mask behind the first term;
+a layer weight in the seed or in the scale only; a Laplacian GRAD launch without ACCUM, in front of the storing dgrad, with
+the other pool's coefficient, or writing a pixel outside the cells.  The refusals of ``check_step`` raise.
 """
 from __future__ import annotations
 
 import functools
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from style_transfer_visualizer_amd import _lib, core_model, plan, synthetic
+from style_transfer_visualizer_amd import _lib, core_model, guidance, ops, plan, synthetic
 from tests import bf16x3_emul as emul
+from tests import guidance_ref, lap_ref
 from tests import layerwise as lw
 
 CPU = torch.device("cpu")
@@ -34,17 +47,32 @@ CHECK_ENV = {"STV_GRAD_ARENA": "0", "STV_SKIP_PREPOOL": "0"}
 
 
 @functools.cache
-def vgg_layers(cfg: tuple = synthetic.VGG19_CFG) -> list:
-    return list(core_model.build_vgg_features(lw.biased_weights(cfg), cfg).eval().children())
+def vgg_layers(cfg: tuple = synthetic.VGG19_CFG, pooling: str = "max") -> list:
+    vgg = core_model.build_vgg_features(lw.biased_weights(cfg), cfg).eval()
+    return list(core_model.replace_pooling(vgg, pooling).children())
 
 
-def make_engine(monkeypatch, layout, precision: str, H: int, W: int, cfg: tuple = synthetic.VGG19_CFG, **env):
+def make_guide(regions: int, H: int, W: int):
+    return guidance.make_guide(regions, list(lw.REGION_WEIGHTS[regions]), *lw.guide_labels(regions, H, W))
+
+
+def make_engine(monkeypatch, layout, precision: str, H: int, W: int, cfg: tuple = synthetic.VGG19_CFG, *, pooling: str = "max",
+                regions: int = 0, lap_pools: tuple = (), **env):
     for k, v in {**CHECK_ENV, **env}.items():
         monkeypatch.setenv(k, v)
     dtype, split = PRECISIONS[precision]
     style_at, content_at = layout
-    layers = vgg_layers(cfg)[:max(style_at + content_at) + 1]
-    return core_model._Engine(layers, sorted(style_at), sorted(content_at), H, W, dtype, CPU, split=split, assume_device=True)
+    layers = vgg_layers(cfg, pooling)[:max(style_at + content_at) + 1]
+    extra = {"lap_pools": lap_pools} if lap_pools else {}
+    if regions:      # (the guide reaches the engine as it does from the model)
+        extra["guide"] = make_guide(regions, H, W)
+    return core_model._Engine(layers, sorted(style_at), sorted(content_at), H, W, dtype, CPU, split=split, assume_device=True, **extra)
+
+
+def cpu_loss_combine(parts, table, scale, style_w, content_w, losses, scores) -> None:
+    """``ops.loss_combine`` for ``engine.region_losses()`` on host tensors: the partials added in double, one fp32 result."""
+    for i, (o, c, _) in enumerate(table.tolist()):
+        losses[i] = (parts[int(o):int(o) + int(c)].double().sum() * scale[i].double()).float()
 
 
 # ------------------------------------------------------------------------------------------------ the stand-in executor
@@ -92,6 +120,8 @@ class StandIn:
         self.bf16, self.x3 = eng.dtype == torch.bfloat16, eng.split
         self.mutate = mutate or (None, None)
         self.hits = 0
+        self.products_on: dict = {}          # gradient buffer -> 1x1 products launched onto it so far (this step)
+        self.lap_w, self.layer_w = 0.0, None
 
     def mut(self, kind: str, key) -> bool:
         if self.mutate[0] == kind and (self.mutate[1] is key or (not isinstance(key, torch.Tensor) and self.mutate[1] == key)):
@@ -151,21 +181,71 @@ class StandIn:
     def op_relu_fwd(self, op, r) -> None:
         put(r["q0"], hwc(r["p0"]).clamp_min(0.0))
 
+    def op_avgpool_fwd(self, op, r) -> None:
+        x = r["p0"].detach().float()
+        if op.flags & _lib.RELU_IN:
+            x = x.clamp_min(0.0)
+        Hp, Wp = int(op.H) // 2, int(op.W) // 2
+        a, b = x[0:2 * Hp:2, 0:2 * Wp:2], x[0:2 * Hp:2, 1:2 * Wp:2]
+        c, d = x[1:2 * Hp:2, 0:2 * Wp:2], x[1:2 * Hp:2, 1:2 * Wp:2]
+        # the header's order, every fp32 sum rounded on its own; one rounding to storage
+        total = ((a + b) + (c + d)) if self.mut("avg_pairwise", r["q0"]) else (((a + b) + c) + d)
+        r["q0"].copy_(total * 0.25)
+
+    def op_mask_split(self, op, r) -> None:
+        src, out = r["p0"], r["q0"]
+        lab = r["p1"].reshape(src.shape[0], src.shape[1], 1).long()
+        if self.mut("label255_into_slab0", out):
+            lab = torch.where(lab == 255, torch.zeros_like(lab), lab)
+        swap = self.mut("swap_slabs", out)
+        for k in range(int(op.cout)):
+            want = {0: 1, 1: 0}.get(k, k) if swap else k
+            out[k].copy_(torch.where(lab == want, src, torch.zeros_like(src)))
+
+    def op_lap(self, op, r) -> None:
+        p, H, W = int(op.cout), int(op.H), int(op.W)
+        Hp, Wp = H // p, W // p
+        if int(op.taps) == _lib.LAP_LOSS:
+            res = lap_ref.resid(r["p0"], r["p1"].numpy(), p, np.float32)
+            r["q0"].copy_(torch.from_numpy(res))
+            r["q1"][:_lib.LAP_LOSS_PARTS] = 0.0
+            r["q1"][0] = float((res * res).sum(dtype=np.float32))
+            return
+        assert int(op.taps) == _lib.LAP_GRAD
+        coef = float(op.f0)
+        if self.mut("lap_swap_coef", p):
+            q = next(v for v in self.eng.lap_pools if v != p)
+            coef = core_model.lap_coef(self.lap_w, int(op.cin), H // q, W // q, q)
+        accum = bool(op.flags & _lib.ACCUM) and not self.mut("lap_lost_accum", p)
+        out = lap_ref.grad_accum(r["q0"].numpy(), r["q2"], p, coef, accum=accum)
+        if self.mut("lap_margin", p):
+            out[0, Hp * p, 0] += np.float32(1e-3)
+        r["q2"].copy_(torch.from_numpy(out).reshape(r["q2"].shape))
+
     # -- loss head
     def op_gram_partial(self, op, r) -> None:
         pass                                 # (the raw Gram is summed where it is finished, from the same activation)
 
-    def finish(self, tap, *, target, loss_part, sgrad, coef: float, coef_dev) -> None:
+    def finish(self, tap, *, norm: float, target, loss_part, sgrad, coef: float, coef_dev) -> None:
+        """``tap``: the chain the op's partials belong to (its ``buf`` is the region's slab under guidance); ``norm``: the op's."""
         C = tap.buf.C
         f = tap.buf.act.detach().float().reshape(-1, C)
         n = f.shape[0]
+        if self.mut("norm_parent", sgrad):
+            norm = float(C * n)
+        if self.mut("swap_lambda", sgrad):
+            lam = self.eng.guide.weights
+            k = tap.order % len(lam)
+            coef = coef * lam[(k + 1) % len(lam)] / lam[k]
+        if self.mut("seed_without_w", sgrad):
+            coef = coef / self.layer_w[tap.order]
         if self.x3:
             (h, lo) = emul.split(f)
             h, lo = h.float(), lo.float()
             R = h.t() @ h + h.t() @ lo + lo.t() @ h
         else:
             R = f.t() @ f
-        norm = torch.tensor(float(C * n), dtype=torch.float32)
+        norm = torch.tensor(norm, dtype=torch.float32)
         G = R.clamp(max=plan.GRAM_CLAMP_MAX) / norm
         if target is None:
             return
@@ -181,14 +261,14 @@ class StandIn:
             sgrad.copy_(torch.where(R <= plan.GRAM_CLAMP_MAX, kk * d, torch.zeros_like(d)).reshape(sgrad.shape))
 
     def op_gram_finish(self, op, r) -> None:
-        tap = next(t for t in self.s.style_taps if t.partials is r["p0"])
-        self.finish(tap, target=r.get("p1"), loss_part=r.get("q1"), sgrad=r.get("q2"), coef=float(op.f2), coef_dev=r.get("p2"))
+        tap = next(t for t in self.s.all_chains() if t.partials is r["p0"])
+        self.finish(tap, norm=float(op.f1), target=r.get("p1"), loss_part=r.get("q1"), sgrad=r.get("q2"), coef=float(op.f2), coef_dev=r.get("p2"))
 
     def op_gram_multi(self, op, r) -> None:
         by_ptr = {t.data_ptr(): t for t in r.values() if isinstance(t, torch.Tensor)}
         for e in list(r["p0"])[:int(op.n)]:
-            tap = next(t for t in self.s.style_taps if t.partials.data_ptr() == e.partials)
-            self.finish(tap, target=by_ptr.get(e.target), loss_part=by_ptr.get(e.loss_part), sgrad=by_ptr.get(e.sgrad),
+            tap = next(t for t in self.s.all_chains() if t.partials is not None and t.partials.data_ptr() == e.partials)
+            self.finish(tap, norm=float(e.norm), target=by_ptr.get(e.target), loss_part=by_ptr.get(e.loss_part), sgrad=by_ptr.get(e.sgrad),
                         coef=float(e.coef), coef_dev=by_ptr.get(e.coef_dev))
 
     def op_content_loss(self, op, r) -> None:
@@ -201,6 +281,10 @@ class StandIn:
 
     def op_loss_combine(self, op, r) -> None:
         parts, table, scale = r["p0"], r["p1"], r["p2"]
+        scale = scale.clone()
+        for i in range(len(scale)):
+            if self.mut("scale_without_w", i):
+                scale[i] = scale[i] / self.layer_w[i]
         terms = [(parts[int(o):int(o) + int(c)].double().sum() * scale[i].double()).float() for i, (o, c, _) in enumerate(table.tolist())]
         kinds = [int(k) for _, _, k in table.tolist()]
         r["q0"][:len(terms)] = torch.stack(terms)
@@ -219,8 +303,12 @@ class StandIn:
         term = self.product(lambda a, w, rev: conv_f_1x1(a, w, rev), hwc(r["p0"]), r["p1"].detach().float().reshape(C, C), self.x3)
         accum = bool(op.flags & _lib.ACCUM) and not self.mut("lost_accum", r["q0"])
         put(r["q0"], term, accum)
-        if self.mut("tap_twice", r["q0"]):
+        if self.mut("tap_twice", r["q0"]) or self.mut("region_twice", r["p0"]):
             put(r["q0"], term, True)
+        done = self.products_on[id(r["q0"])] = self.products_on.get(id(r["q0"]), 0) + 1
+        if done == 1 and self.mut("mask_early", r["q0"]):      # the in-place ReLU mask behind the FIRST term (op_relu_bwd skips it)
+            act = next(n.dst.act for n in self.s.nodes if n.dst.grad is r["q0"])
+            r["q0"].copy_(r["q0"].float() * (act.float() > 0))
 
     def dgrad(self, op, r, nd) -> None:
         g = self.product(conv_b, hwc(r["p0"]), self.conv_w(nd), self.x3)
@@ -271,7 +359,31 @@ class StandIn:
         accum = bool(op.flags & _lib.ACCUM) and not (self.mut("lost_accum", dx) or self.mut("route_overwrites", dx))
         put(dx, unpool(dy, q, H, W), accum)
 
+    def op_avgpool_bwd(self, op, r) -> None:
+        dx = r["q0"]
+        H, W = int(op.H), int(op.W)
+        Hp, Wp = H // 2, W // 2
+        v = torch.zeros(H, W, int(op.cin))
+        v[:2 * Hp, :2 * Wp] = (0.25 * r["p1"].float()).repeat_interleave(2, dim=0).repeat_interleave(2, dim=1)
+        if op.flags & _lib.MASK and not self.mut("lost_mask", dx):
+            ref = r["p0"]
+            if self.mut("wrong_mask", dx):
+                ref = next(n.dst.act for n in self.s.nodes if n.dst.act.shape == ref.shape and n.dst.act is not ref)
+            v = torch.where(ref.float() > 0, v, torch.zeros_like(v))
+        if bool(op.flags & _lib.ACCUM) and not self.mut("lost_accum", dx):
+            out = dx.float().clone()                       # the rows and columns the floor drops stay as they are
+            out[:2 * Hp, :2 * Wp] += v[:2 * Hp, :2 * Wp]
+        else:
+            out = v
+        if self.mut("odd_tail_written", dx):
+            assert H % 2 or W % 2
+            out[2 * Hp:, :] = 0.5
+            out[:, 2 * Wp:] = 0.5
+        dx.copy_(out)
+
     def op_relu_bwd(self, op, r) -> None:
+        if r["p1"] is r["q0"] and self.mutate[0] == "mask_early" and self.mutate[1] is r["q0"]:
+            return
         g = r["p1"].float() * (r["p0"].float() > 0)
         accum = bool(op.flags & _lib.ACCUM) and not self.mut("lost_accum", r["q0"])
         r["q0"].copy_(g + r["q0"].float() if accum else g)
@@ -303,23 +415,40 @@ class StandIn:
         s = self.s
         self.run(s.forward_ops(style_img))
         for tap in s.style_taps:
+            if s.guide:      # per region, by the float64 definition, from the style image's own label map and counts
+                f64 = tap.buf.act.detach().double().permute(2, 0, 1).unsqueeze(0)
+                for r, c in enumerate(tap.regions):
+                    c.target = guidance_ref.region_gram(f64, self.eng.guide.style_labels, r).float().contiguous()
+                continue
             f = tap.buf.act.detach().float().reshape(-1, tap.buf.C)
             tap.target = ((f.t() @ f).clamp(max=plan.GRAM_CLAMP_MAX) / float(f.numel())).contiguous()
         self.run(s.forward_ops(content_img))
         for tap in s.content_taps:
             tap.target = tap.buf.act.clone()
+        if self.eng.lap_pools:
+            self.eng.bind_lap_targets([torch.from_numpy(lap_ref.pool(content_img, p)) for p in self.eng.lap_pools])
 
-    def fused_step(self, x: torch.Tensor, style_w: float, content_w: float, tv_w: float = 0.0) -> torch.Tensor:
-        """The op list of ``_Engine.loss_and_grad``; returns the image gradient."""
+    def fused_step(self, x: torch.Tensor, style_w: float, content_w: float, tv_w: float = 0.0, lap_w: float = 0.0,
+                   layer_w: tuple | None = None) -> torch.Tensor:
+        """The op list of ``_Engine.loss_and_grad``, built as it builds it; returns the image gradient."""
         eng, s = self.eng, self.s
+        self.lap_w, self.layer_w = lap_w, layer_w
+        self.products_on.clear()
         grad = torch.zeros_like(x)
-        fwd = eng._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w)
+        fwd = eng._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w, layer_w=layer_w)
         bwd = s.backward_ops(grad, content_coef=content_w, coef_dev=None, prewritten=tuple(t for t in s.content_taps if t.grad_fused))
         if tv_w:
             fwd.insert(0, eng._tv_op(x, loss=True))
             k = max(i for i, o in enumerate(bwd) if o.op == _lib.OP_CONV_FIRST_DGRAD)
             bwd.insert(k + 1, eng._tv_op(x, grad=grad, tv_w=tv_w))
-        self.run(fwd + [eng._combine_op(style_w, content_w, None, tv_w)] + bwd)
+        if lap_w:
+            at = 1 if tv_w else 0
+            fwd[at:at] = eng._lap_ops(x)
+            k = max(i for i, o in enumerate(bwd) if o.op == _lib.OP_CONV_FIRST_DGRAD) + (2 if tv_w else 1)
+            if self.mut("lap_insertion", "in front of the dgrad"):      # (which stores: the accumulated terms are lost)
+                k = max(i for i, o in enumerate(bwd) if o.op == _lib.OP_CONV_FIRST_DGRAD)
+            bwd[k:k] = eng._lap_ops(x, grad=grad, lap_w=lap_w)
+        self.run(fwd + [eng._combine_op(style_w, content_w, None, tv_w, layer_w, lap_w)] + bwd)
         return grad
 
     def autograd_step(self, x: torch.Tensor, gout: torch.Tensor) -> torch.Tensor:
@@ -351,13 +480,15 @@ def images(H: int, W: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     return synthetic.synthetic_image(1, H, W), synthetic.synthetic_image(0, H, W), x0.contiguous()
 
 
-def evaluated(monkeypatch, layout, precision, H, W, *, reverse=False, mutate=None, gout=None, tv_w=0.0, cfg=synthetic.VGG19_CFG, **env):
-    eng = make_engine(monkeypatch, layout, precision, H, W, cfg, **env)
+def evaluated(monkeypatch, layout, precision, H, W, *, reverse=False, mutate=None, gout=None, tv_w=0.0, cfg=synthetic.VGG19_CFG,
+              pooling="max", regions=0, lap_pools=(), lap_w=0.0, layer_w=None, **env):
+    eng = make_engine(monkeypatch, layout, precision, H, W, cfg, pooling=pooling, regions=regions, lap_pools=lap_pools, **env)
+    monkeypatch.setattr(ops, "loss_combine", cpu_loss_combine)      # (engine.region_losses() launches it directly)
     style, content, x0 = images(H, W)
     eng.sched.alloc_grads()
     sim = StandIn(eng, reverse=reverse, mutate=mutate(eng) if callable(mutate) else mutate)
     sim.set_targets(style, content)
-    grad = sim.autograd_step(x0, gout) if gout is not None else sim.fused_step(x0, STYLE_W, CONTENT_W, tv_w)
+    grad = sim.autograd_step(x0, gout) if gout is not None else sim.fused_step(x0, STYLE_W, CONTENT_W, tv_w, lap_w, layer_w)
     return eng, x0, grad, sim
 
 
@@ -416,6 +547,66 @@ def test_refuses_rotating_gradients_and_unstored_maps(monkeypatch):
         check(eng, x0, grad)
     eng, x0, grad, _ = evaluated(monkeypatch, LAYOUTS["default"], "bf16", 32, 32, STV_SKIP_PREPOOL="1")
     with pytest.raises(RuntimeError, match="not stored"):
+        check(eng, x0, grad)
+
+
+# ------------------------------------------------------------ average pooling, guidance, layer weights, Laplacian terms
+def evaluated_case(monkeypatch, name: str, precision: str, **kw):
+    spec = {k: v for k, v in lw.STEP_CASES[name].items() if k != "precisions"}
+    layout, (H, W) = lw.case_layout(spec), spec.pop("size")
+    del spec["layout"]
+    return evaluated(monkeypatch, layout, precision, H, W, **{**spec, **kw})
+
+
+def check_case(name: str, eng, x0, grad, **kw):
+    spec = lw.STEP_CASES[name]
+    return check(eng, x0, grad, **{**{k: spec[k] for k in ("tv_w", "lap_w", "layer_w") if k in spec}, **kw})
+
+
+NEW_KINDS = {"avg": {"avgpool forward", "gradient (avgpool)"}, "guided": {"region slab", "region loss"}, "lap": {"lap residual"},
+             "all": {"avgpool forward", "gradient (avgpool)", "region slab", "region loss", "lap residual"}, "layer": set()}
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["order-as-is", "order-reversed"])
+@pytest.mark.parametrize(("name", "precision"), lw.STEP_PARAMS, ids=lambda v: v.replace(" ", "-"))
+def test_reference_arithmetic_stays_inside_the_intervals_of_the_new_structures(name, precision, reverse, monkeypatch):
+    eng, x0, grad, _ = evaluated_case(monkeypatch, name, precision, reverse=reverse)
+    rep = check_case(name, eng, x0, grad)
+    assert NEW_KINDS[name.split()[0]] <= set(rep.rows)
+    if eng.guide is not None:      # every tapped buffer takes one launch per region: all of them went through several stages
+        assert {f"grad L{nd.layer:02d} {nd.kind}" for nd in eng.sched.nodes if any(t.kind == "style" for t in nd.dst.taps)
+                and (eng.guide.n > 1 or nd is not eng.sched.nodes[-1])} <= set(rep.multi_stage)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_autograd_path_with_average_pooling(precision, monkeypatch):
+    gout = torch.tensor([3e4 * (1.0 + 0.37 * i) for i in range(6)])
+    eng, x0, grad, _ = evaluated(monkeypatch, LAYOUTS["default"], precision, 40, 24, gout=gout, pooling="avg")
+    rep = check(eng, x0, grad, gout=gout)
+    assert {"avgpool forward", "gradient (avgpool)"} <= set(rep.rows)
+
+
+def test_the_new_refusals(monkeypatch):
+    eng, x0, grad, _ = evaluated_case(monkeypatch, "avg default", "bf16")
+    with pytest.raises(RuntimeError, match="lap_w = 3 on an engine without lap_pools"):
+        check(eng, x0, grad, lap_w=3.0)
+    pool = next(nd for nd in eng.sched.nodes if nd.kind == "avgpool")
+    pool.kind = "lppool"
+    with pytest.raises(RuntimeError, match="no rule for node kind 'lppool'"):
+        check(eng, x0, grad)
+    pool.kind = "avgpool"
+    eng.sched.content_taps[0].kind = "histogram"
+    with pytest.raises(RuntimeError, match="no rule for tap kind 'histogram'"):
+        check(eng, x0, grad)
+    eng, x0, grad, _ = evaluated_case(monkeypatch, "guided R=2", "bf16")
+    eng.sched.style_taps[1].regions = None
+    with pytest.raises(RuntimeError, match=r"guided schedule without attached regions \(style tap 1\)"):
+        check(eng, x0, grad)
+    eng, x0, grad, _ = evaluated_case(monkeypatch, "guided R=2", "bf16")
+    with pytest.raises(RuntimeError, match="gout"):
+        check(eng, x0, grad, gout=[1.0] * 6)
+    eng.guide = None
+    with pytest.raises(RuntimeError, match="guide = 2 on an engine whose guide is None"):
         check(eng, x0, grad)
 
 
@@ -579,3 +770,119 @@ def test_every_decision_field_is_read_per_node(monkeypatch):
                 nd.dst.relu_fused = value
         with pytest.raises(lw.LayerwiseMismatch):
             check(eng, x0, grad)
+
+
+# ------------------------------------------- mutations of the new structures: each fails, naming the mutated tensor
+def mutated_case(monkeypatch, name: str, precision: str, mutate, first: str, *, hits: int | None = None):
+    eng, x0, grad, sim = evaluated_case(monkeypatch, name, precision, mutate=mutate)
+    assert sim.hits >= 1 if hits is None else sim.hits == hits, sim.hits
+    with pytest.raises(lw.LayerwiseMismatch) as err:
+        check_case(name, eng, x0, grad)
+    assert err.value.tensors[0] == first, err.value.tensors
+    return eng
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_avgpool_summed_pairwise(precision, monkeypatch):
+    """(a+b)+(c+d) in place of ((a+b)+c)+d.  fp32 storage only: a window of four bf16 values sums exactly in fp32 in either
+    order (8-bit significands, exponents a few apart), so bf16 storage cannot tell the two orders apart."""
+    eng0, _, _, _ = evaluated_case(monkeypatch, "avg default", precision)      # (the pool runs three times: two captures, the step)
+    eng = mutated_case(monkeypatch, "avg default", precision, lambda e: ("avg_pairwise", node_of(e, 4).dst.act), "act L04 avgpool")
+    assert not torch.equal(node_of(eng0, 4).dst.act, node_of(eng, 4).dst.act)      # the two orders differ on this input
+
+
+@pytest.mark.parametrize("precision", list(PRECISIONS))
+def test_avgpool_backward_mutations(precision, monkeypatch):
+    # conv 2 -> ReLU (fused) -> avgpool 4: the pool's backward masks with conv 2's stored output
+    eng = mutated_case(monkeypatch, "avg default", precision, lambda e: ("lost_mask", node_of(e, 2).dst.grad), "grad L02 conv", hits=1)
+    assert node_of(eng, 2).dst.relu_fused and not node_of(eng, 4).relu_in
+    mutated_case(monkeypatch, "avg default", precision, lambda e: ("wrong_mask", node_of(e, 2).dst.grad), "grad L02 conv", hits=1)
+    # conv 2 tapped -> the pool takes the pending ReLU itself (relu_in): the mask is then the node's own
+    eng = mutated_case(monkeypatch, "avg pending relu", precision, lambda e: ("lost_mask", node_of(e, 2).dst.grad), "grad L02 conv", hits=1)
+    assert node_of(eng, 4).relu_in and not node_of(eng, 2).dst.relu_fused
+    # content tap on conv 16 in front of avgpool 18: the forward half wrote the gradient, the pool's backward accumulates
+    eng = mutated_case(monkeypatch, "avg prepool", precision, lambda e: ("lost_accum", node_of(e, 16).dst.grad), "grad L16 conv", hits=1)
+    assert node_of(eng, 18).kind == "avgpool" and node_of(eng, 16).dst.taps[0].grad_fused
+    # conv 25's map is 5x3: the fifth row and the third column take no part and must be written +0
+    eng = mutated_case(monkeypatch, "avg default", precision, lambda e: ("odd_tail_written", node_of(e, 25).dst.grad), "grad L25 conv", hits=1)
+    assert (node_of(eng, 25).dst.H, node_of(eng, 25).dst.W) == (5, 3)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_mask_split_mutations(precision, monkeypatch):
+    mutated_case(monkeypatch, "guided R=2", precision, lambda e: ("label255_into_slab0", e.sched.style_taps[2].slabs), "slab style2 r0", hits=1)
+    mutated_case(monkeypatch, "guided R=3", precision, lambda e: ("swap_slabs", e.sched.style_taps[2].slabs), "slab style2 r0", hits=1)
+
+
+@pytest.mark.parametrize("precision", list(PRECISIONS))
+def test_region_chain_mutations(precision, monkeypatch):
+    chain5 = lambda e: e.sched.all_chains()[5]      # noqa: E731  (style tap 2 = conv 10, region 1)
+    mutated_case(monkeypatch, "guided R=2", precision, lambda e: ("norm_parent", chain5(e).sgrad), "seed style5", hits=1)
+    mutated_case(monkeypatch, "guided R=2", precision, lambda e: ("swap_lambda", chain5(e).sgrad), "seed style5", hits=1)
+    # the deepest tap opens the chain: region 0's product stores, region 1's accumulates
+    mutated_case(monkeypatch, "guided R=2", precision, lambda e: ("lost_accum", node_of(e, 28).dst.grad), "grad L28 conv", hits=1)
+    mutated_case(monkeypatch, "guided R=2", precision, lambda e: ("region_twice", chain5(e).buf.act), "grad L10 conv", hits=1)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_relu_mask_behind_the_first_region_term(precision, monkeypatch):
+    eng = mutated_case(monkeypatch, "guided relu taps", precision, lambda e: ("mask_early", node_of(e, 5).dst.grad), "grad L05 conv", hits=1)
+    assert node_of(eng, 5).dst.relu_fused and node_of(eng, 5).dst.taps
+
+
+@pytest.mark.parametrize("precision", list(PRECISIONS))
+def test_layer_weight_in_seed_or_scale_only(precision, monkeypatch):
+    mutated_case(monkeypatch, "layer weights", precision, lambda e: ("seed_without_w", e.sched.style_taps[2].sgrad), "seed style2", hits=1)
+    mutated_case(monkeypatch, "layer weights", precision, ("scale_without_w", 2), "score style", hits=1)
+    eng, x0, grad, _ = evaluated_case(monkeypatch, "layer weights", precision)
+    assert float(eng.sched.style_taps[1].sgrad.float().abs().max()) == 0.0           # the zero-weight tap
+
+
+def test_laplacian_mutations(monkeypatch):
+    """(The term added to the total in front of TV's is not among them: the two orders differ by an fp32 ulp of the total,
+    far inside the derived error of the scores, so no value of the weights makes it observable.)"""
+    mutated_case(monkeypatch, "lap (4,)", "fp32", ("lap_lost_accum", 4), "image grad", hits=1)
+    mutated_case(monkeypatch, "lap (2, 8) tv", "fp32", ("lap_lost_accum", 8), "image grad", hits=1)
+    mutated_case(monkeypatch, "lap (2, 8)", "bf16", ("lap_swap_coef", 2), "image grad", hits=1)
+    mutated_case(monkeypatch, "lap (4,) tv", "fp32", ("lap_margin", 4), "image grad", hits=1)
+    mutated_case(monkeypatch, "lap (2, 8) tv", "bf16", ("lap_insertion", "in front of the dgrad"), "image grad", hits=1)
+    eng, x0, grad, _ = evaluated_case(monkeypatch, "lap (4,)", "fp32")
+    eng.lap_resid[0][1, 2, 3] += 1e-3
+    with pytest.raises(lw.LayerwiseMismatch) as err:
+        check_case("lap (4,)", eng, x0, grad)
+    assert err.value.tensors[0] == "lap resid p4"
+
+
+def test_avgpool_relu_in_is_read_per_node(monkeypatch):
+    """content7: conv 7 is tapped, so the pool behind it takes the pending ReLU itself, the other three pools do not."""
+    eng, x0, grad, _ = evaluated_case(monkeypatch, "avg content7", "bf16")
+    pools = [nd for nd in eng.sched.nodes if nd.kind == "avgpool"]
+    assert _both(nd.relu_in for nd in pools)
+    check_case("avg content7", eng, x0, grad)
+    # read as "no pool takes a ReLU": the pool behind conv 7 is then checked against the mean of unclamped values.  (The
+    # other global reading, "every pool takes one", describes the same values: a pool without relu_in reads a map whose ReLU
+    # ran in the conv's epilogue - clamping it again changes nothing, and its backward carries the mask either way.)
+    eng, x0, grad, _ = evaluated_case(monkeypatch, "avg content7", "bf16")
+    for nd in eng.sched.nodes:
+        if nd.kind == "avgpool":
+            nd.relu_in = False
+    with pytest.raises(lw.LayerwiseMismatch) as err:
+        check_case("avg content7", eng, x0, grad)
+    assert err.value.tensors[0] == "act L09 avgpool"
+
+
+def test_a_region_norm_of_the_parent_in_the_schedule(monkeypatch):
+    """The same error one level up: the schedule itself hands a chain ``C * H * W`` as its norm (what ``attach_regions`` would do
+    with the parent's pixel count), the stand-in runs the ops as built - the checker counts ``n_r`` from the label map itself."""
+    eng = make_engine(monkeypatch, LAYOUTS["default"], "bf16", *lw.GUIDE_SIZE, regions=2)
+    monkeypatch.setattr(ops, "loss_combine", cpu_loss_combine)
+    chain = eng.sched.all_chains()[3]
+    chain.norm = float(chain.buf.C * chain.buf.H * chain.buf.W)
+    style, content, x0 = images(*lw.GUIDE_SIZE)
+    eng.sched.alloc_grads()
+    sim = StandIn(eng)
+    sim.set_targets(style, content)
+    grad = sim.fused_step(x0, STYLE_W, CONTENT_W)
+    with pytest.raises(lw.LayerwiseMismatch) as err:
+        check(eng, x0, grad)
+    assert err.value.tensors[0] == "seed style3"
