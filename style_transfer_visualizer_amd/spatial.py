@@ -34,14 +34,16 @@ HALO_ROWS = 160
 
 
 def strip_rows(H: int, rank: int, world: int) -> tuple[int, int, int, int]:
-    """(core_begin, core_end, ext_begin, ext_end) for `rank`; strip heights are multiples of 16."""
+    """(core_begin, core_end, ext_begin, ext_end) for `rank`; strip heights are multiples of 16.  The verdict is one for
+    the whole partition: an image that leaves ANY rank without rows is refused on EVERY rank (a rank that went on alone
+    would wait in its first exchange for a peer that has raised)."""
     base = -(-H // world)
     base = -(-base // 16) * 16
-    c0 = min(H, rank * base)
-    c1 = min(H, c0 + base)
-    if c1 <= c0:
+    if (world - 1) * base >= H:          # the last rank's strip would be empty
         msg = f"image of {H} rows is too small for {world} strips of at least 16 rows"
         raise ValueError(msg)
+    c0 = min(H, rank * base)
+    c1 = min(H, c0 + base)
     return c0, c1, max(0, c0 - HALO_ROWS), min(H, c1 + HALO_ROWS)
 
 
@@ -107,12 +109,11 @@ class _StripLossHead:
         self.scale = torch.tensor(scale, dtype=torch.float32, device=dev)
         self.phase2.append(s.emit(op=plan.OP_LOSS_COMBINE, p0=self.parts2, p1=self.table, p2=self.scale, q0=self.losses,
                                   q1=self.scores, cin=len(rows), f0=style_w, f1=content_w))
-        # The content-gradient op divides by ITS element count, the loss is normalised by the GLOBAL one.  The shares are
-        # handed out in the order the reverse schedule emits its content-gradient ops (the deepest tap first), as they
-        # always were; with one content tap, or content taps at one resolution, that is each tap's own share.
-        emitted = [t for nd in reversed(s.nodes) for t in nd.dst.taps if t.kind == "content"]
+        # The content-gradient op divides by ITS element count, the loss is normalised by the GLOBAL one: every tap takes
+        # its OWN share (they differ between resolutions: halo rows, floored pooled heights).  `Schedule.backward_ops` reads
+        # the list by tap order, whatever order it emits the content-gradient ops in.
         self.content_coef = [0.0] * n_content
-        for share, tap in zip(local_share, emitted, strict=True):
+        for share, tap in zip(local_share, s.content_taps, strict=True):
             self.content_coef[tap.order] = content_w * share
 
     def reduce(self, world: int, group=None) -> None:
