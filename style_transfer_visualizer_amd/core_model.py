@@ -14,7 +14,9 @@ import copy
 import hashlib
 import os
 import threading
+from collections.abc import Callable
 from pathlib import Path
+from typing import NamedTuple
 from urllib.parse import urlparse
 
 import torch
@@ -422,6 +424,28 @@ def create_feature_blocks(
 
 
 # --------------------------------------------------------------------------- engine
+class _Term(NamedTuple):
+    """One extra term of a step (``_Engine.extra_terms``): its loss partials in ``parts``, the scale of its combine row, and
+    its two ops as ``loss_op(x)`` and ``grad_op(x, grad)``."""
+
+    kind: str           # "tv" | "lap"
+    off: int
+    cnt: int
+    scale: float
+    loss_op: Callable
+    grad_op: Callable
+
+
+class _Head(NamedTuple):
+    """The combine op's operands (``_Engine.head``) and where the extra terms' slots of ``losses`` are."""
+
+    table: torch.Tensor
+    scale: torch.Tensor
+    losses: torch.Tensor
+    tv: int | None          # the row of the total-variation term
+    lap: slice | None       # the rows of the Laplacian terms, one per pool
+
+
 class _Engine:
     """Buffers + command buffers for one (model, image size, device)."""
 
@@ -457,18 +481,14 @@ class _Engine:
         self.n_style_rows = len(s.all_chains())
         n_terms = self.n_style_rows + self.n_content
         off = 0
-        rows, scale = [], []
         for tap in s.all_chains():
             tap.parts_off, tap.parts_cnt = off, ops.gram_loss_parts(tap.buf.C)
             off += tap.parts_cnt
-            rows.append([tap.parts_off, tap.parts_cnt, 0])
-            scale.append(self._style_scale(tap, None))
             tap.sgrad = torch.zeros(1, tap.buf.C, tap.buf.C, device=device, dtype=dtype)
         for tap in s.content_taps:
             tap.parts_off, tap.parts_cnt = off, ops._lib.CONTENT_LOSS_PARTS
             off += tap.parts_cnt
-            rows.append([tap.parts_off, tap.parts_cnt, 1])
-            scale.append(1.0 / float(tap.buf.act.numel()))
+        rows, scale = self._base_rows(None)
         # (the partial sums of the total-variation term sit behind every tap's; only a tv_w > 0 step reads or writes them)
         self.tv_parts_off = off
         # (and those of the Laplacian terms, one block per pool, behind them: an engine without pools allocates none)
@@ -481,9 +501,8 @@ class _Engine:
         self.scores = torch.zeros(4, device=device, dtype=torch.float32)
         self.coef_buf = torch.ones(max(n_terms, 1), device=device, dtype=torch.float32)
         self._programs: dict = {}
-        self._tv_heads: dict = {}        # tv_w -> (table, scale, losses) of the combine op with the extra kind-2 row
-        self._layer_heads: dict = {}     # style layer weights -> (table, scale, losses) of the combine op of a weighted step
-        self._lap_heads: dict = {}       # (tv_w, lap_w, layer weights) -> (table, scale, losses) with the Laplacian rows
+        self._heads: dict = {}           # (tv_w, lap_w, layer weights) -> _Head of the combine op of any step but the plain one
+        self._target_cache: dict = {}    # converted content targets (_nhwc_of)
         self._region_head: tuple | None = None      # (scale, losses, scores) of last_region_losses()' own combine launch
         self.image_channels = int(s.nodes[0].cin)
         check_lap_fits(self.lap_pools, H, W)
@@ -496,18 +515,25 @@ class _Engine:
         self.generation = 0
         self._stage: torch.Tensor | None = None      # fp32 contiguous copy of a non-conforming input
 
-    def _region_weight(self, tap) -> float:
-        """``lambda_r`` of a Gram chain's tap (1.0 without guidance)."""
-        return 1.0 if self.guide is None else self.guide.weights[tap.order % self.guide.n]
+    def _chain_weights(self, tap, layer_w: tuple | None) -> tuple[float, float]:
+        """``(w_l, lambda_r)`` of a Gram chain's tap: the weight of its style layer (1.0 without layer weights) and of its
+        region (1.0 without guidance).  A factor of 1.0 is exact, so the products below are those of the plain step."""
+        layer = tap if tap.parent is None else tap.parent      # (a region's chain hangs under its layer's tap)
+        w = 1.0 if layer_w is None else float(layer_w[layer.order])
+        return w, 1.0 if self.guide is None else self.guide.weights[tap.order % self.guide.n]
 
     def _style_scale(self, tap, layer_w: tuple | None) -> float:
-        """The combine scale of a Gram chain's row, formed in double: ``w_l * lambda_r / C^2`` (without guidance ``w_l / C^2``,
-        without layer weights ``1 / C^2``, exactly as those steps always formed it)."""
-        cc = float(tap.buf.C * tap.buf.C)
-        if self.guide is None:
-            return 1.0 / cc if layer_w is None else float(layer_w[tap.order]) / cc
-        w = 1.0 if layer_w is None else float(layer_w[tap.parent.order])
-        return w * self._region_weight(tap) / cc
+        """The combine scale of a Gram chain's row, formed in double: ``w_l * lambda_r / C^2``."""
+        w, lam = self._chain_weights(tap, layer_w)
+        return w * lam / float(tap.buf.C * tap.buf.C)
+
+    def _base_rows(self, layer_w: tuple | None) -> tuple[list, list]:
+        """Rows ``[offset, count, kind]`` and scales of the combine table's taps: the Gram chains (kind 0), then the content
+        taps (kind 1, ``1 / numel``)."""
+        s = self.sched
+        rows = [[t.parts_off, t.parts_cnt, 0] for t in s.all_chains()] + [[t.parts_off, t.parts_cnt, 1] for t in s.content_taps]
+        scale = [self._style_scale(t, layer_w) for t in s.all_chains()]
+        return rows, scale + [1.0 / float(t.buf.act.numel()) for t in s.content_taps]
 
     # -- op list pieces -------------------------------------------------------
     def _forward_with_losses(self, x: torch.Tensor, *, style_coef: float, with_seed: bool,
@@ -520,10 +546,9 @@ class _Engine:
         fp32 where ``style_coef`` alone is; ``None``: every tap with ``style_coef``."""
         s = self.sched
 
-        def coef_of(tap) -> float:
-            if self.guide is not None:      # style_w * w_l * lambda_r, formed in double
-                return style_coef * (1.0 if layer_w is None else layer_w[tap.parent.order]) * self._region_weight(tap)
-            return style_coef if layer_w is None else style_coef * layer_w[tap.order]
+        def coef_of(tap) -> float:      # style_w * w_l * lambda_r, left to right, in double
+            w, lam = self._chain_weights(tap, layer_w)
+            return style_coef * w * lam
         if content_coef is not None:
             s.alloc_grads()          # the content term's gradient is written during the forward half
 
@@ -561,37 +586,6 @@ class _Engine:
             return s.forward_ops(x, after_node=after) + tail
         return s.forward_ops(x) + [op for node in s.nodes for op in after(node)] + tail
 
-    def layer_head(self, layer_w: tuple) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(table, scale, losses) of the combine op of a step with style layer weights: the engine's table, a scale vector
-        whose row of style tap ``l`` is ``fp32(layer_w[l] / (C*C))`` (the weight rides in the scale, so the style score is
-        ``sum_l w_l * loss_l``), and a losses vector of its own: the engine's keeps the unweighted terms ``forward()``
-        returns.  One triple per weight tuple."""
-        head = self._layer_heads.get(layer_w)
-        if head is None:
-            if len(self._layer_heads) >= 16:
-                self._layer_heads.pop(next(iter(self._layer_heads)))
-            sc = [self._style_scale(tap, layer_w) for tap in self.sched.all_chains()]
-            sc += [1.0 / float(tap.buf.act.numel()) for tap in self.sched.content_taps]
-            head = self._layer_heads[layer_w] = (self.table, torch.tensor(sc, dtype=torch.float32, device=self.device),
-                                                 torch.zeros_like(self.losses))
-        return head
-
-    def tv_head(self, tv_w: float, layer_w: tuple | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(table, scale, losses) of the combine op of a ``tv_w > 0`` step: the engine's rows (those of :meth:`layer_head`
-        with ``layer_w``) plus one kind-2 row whose scale carries the weight, and a losses vector with that term's slot at
-        the end.  One triple per weight (and weight tuple)."""
-        cache, key = (self._tv_heads, tv_w) if layer_w is None else (self._layer_heads, (tv_w, layer_w))
-        head = cache.get(key)
-        if head is None:
-            table, scale = (self.table, self.scale) if layer_w is None else self.layer_head(layer_w)[:2]
-            if len(cache) >= 16:
-                cache.pop(next(iter(cache)))
-            row = torch.tensor([[self.tv_parts_off, _lib.TV_LOSS_PARTS, _lib.KIND_EXTRA]], dtype=torch.int32, device=self.device)
-            sc = torch.tensor([tv_scale(tv_w, self.image_channels, self.H, self.W)], dtype=torch.float32, device=self.device)
-            head = cache[key] = (torch.cat([table, row]), torch.cat([scale, sc]),
-                                 torch.zeros(self.n_style_rows + self.n_content + 1, device=self.device, dtype=torch.float32))
-        return head
-
     def _tv_op(self, x: torch.Tensor, *, loss: bool = False, grad: torch.Tensor | None = None, tv_w: float = 0.0):
         """The total-variation op on the image: its loss partials (``loss``), or ``grad += coef * sum(x - n)``."""
         return self.sched.emit(op=_lib.OP_TV, p0=x, q0=self.parts[self.tv_parts_off:] if loss else None, q1=grad,
@@ -599,61 +593,69 @@ class _Engine:
                                f0=tv_coef(tv_w, self.image_channels, self.H, self.W) if grad is not None else 0.0,
                                flags=_lib.ACCUM if grad is not None else 0)
 
-    def lap_head(self, tv_w: float, lap_w: float, layer_w: tuple | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(table, scale, losses) of the combine op of a ``lap_w > 0`` step: the rows of the same step without the term
-        (:meth:`tv_head` with ``tv_w``, else :meth:`layer_head` with ``layer_w``, else the engine's), then one kind-2 row
-        per pool in the order of ``lap_pools``, each scale carrying the weight, and a losses vector with those terms' slots
-        at the end.  One triple per (tv_w, lap_w, layer_w)."""
-        key = (tv_w, lap_w, layer_w)
-        head = self._lap_heads.get(key)
-        if head is None:
-            if tv_w:
-                table, scale = self.tv_head(tv_w, layer_w)[:2]
-            else:
-                table, scale = (self.table, self.scale) if layer_w is None else self.layer_head(layer_w)[:2]
-            if len(self._lap_heads) >= 16:
-                self._lap_heads.pop(next(iter(self._lap_heads)))
-            rows = [[self.lap_parts_off + k * _lib.LAP_LOSS_PARTS, _lib.LAP_LOSS_PARTS, _lib.KIND_EXTRA]
-                    for k in range(len(self.lap_pools))]
-            sc = [lap_scale(lap_w, *r.shape) for r in self.lap_resid]
-            head = self._lap_heads[key] = (
-                torch.cat([table, torch.tensor(rows, dtype=torch.int32, device=self.device)]),
-                torch.cat([scale, torch.tensor(sc, dtype=torch.float32, device=self.device)]),
-                torch.zeros(table.shape[0] + len(rows), device=self.device, dtype=torch.float32))
-        return head
+    def _lap_op(self, k: int, x: torch.Tensor, *, grad: torch.Tensor | None = None, lap_w: float = 0.0):
+        """The Laplacian op of pool ``k`` on the image: the LOSS form (residual and loss partials), or with ``grad`` the
+        GRAD form, ``grad += coef * (L r)`` from the residual the LOSS form left."""
+        p, resid = self.lap_pools[k], self.lap_resid[k]
+        common = dict(op=_lib.OP_LAP, q0=resid, cin=self.image_channels, H=self.H, W=self.W, cout=p)
+        if grad is None:
+            return self.sched.emit(p0=x, p1=self.lap_targets[k], q1=self.parts[self.lap_parts_off + k * _lib.LAP_LOSS_PARTS:],
+                                   taps=_lib.LAP_LOSS, **common)
+        return self.sched.emit(q2=grad, taps=_lib.LAP_GRAD, flags=_lib.ACCUM, f0=lap_coef(lap_w, *resid.shape, p), **common)
 
     def _lap_ops(self, x: torch.Tensor, *, grad: torch.Tensor | None = None, lap_w: float = 0.0) -> list:
-        """The Laplacian ops on the image, one per pool: the LOSS form (residual and loss partials), or with ``grad`` the
-        GRAD form, ``grad += coef * (L r)`` from the residual the LOSS form left."""
-        out = []
-        for k, (p, resid) in enumerate(zip(self.lap_pools, self.lap_resid, strict=True)):
-            common = dict(op=_lib.OP_LAP, q0=resid, cin=self.image_channels, H=self.H, W=self.W, cout=p)
-            if grad is None:
-                out.append(self.sched.emit(p0=x, p1=self.lap_targets[k], q1=self.parts[self.lap_parts_off + k * _lib.LAP_LOSS_PARTS:],
-                                           taps=_lib.LAP_LOSS, **common))
-            else:
-                out.append(self.sched.emit(q2=grad, taps=_lib.LAP_GRAD, flags=_lib.ACCUM,
-                                           f0=lap_coef(lap_w, *resid.shape, p), **common))
-        return out
+        """:meth:`_lap_op` of every pool, in the order of ``lap_pools``."""
+        return [self._lap_op(k, x, grad=grad, lap_w=lap_w) for k in range(len(self.lap_pools))]
+
+    def extra_terms(self, tv_w: float = 0.0, lap_w: float = 0.0) -> list[_Term]:
+        """The terms of a step beyond the taps', in the order of their combine rows, of their loss ops at the head of the
+        forward half and of their accumulate ops behind the first-layer dgrad: total variation with ``tv_w``, then one
+        Laplacian term per pool with ``lap_w``.  The weight rides in the scale, so a term's slot of the losses holds the
+        weighted term.  Head, op list and the model's views are all derived from this list."""
+        terms = []
+        if tv_w:
+            terms.append(_Term("tv", self.tv_parts_off, _lib.TV_LOSS_PARTS, tv_scale(tv_w, self.image_channels, self.H, self.W),
+                               lambda x: self._tv_op(x, loss=True), lambda x, grad: self._tv_op(x, grad=grad, tv_w=tv_w)))
+        for k, resid in enumerate(self.lap_resid if lap_w else ()):
+            terms.append(_Term("lap", self.lap_parts_off + k * _lib.LAP_LOSS_PARTS, _lib.LAP_LOSS_PARTS, lap_scale(lap_w, *resid.shape),
+                               lambda x, k=k: self._lap_op(k, x), lambda x, grad, k=k: self._lap_op(k, x, grad=grad, lap_w=lap_w)))
+        return terms
+
+    def head(self, tv_w: float = 0.0, lap_w: float = 0.0, layer_w: tuple | None = None) -> _Head:
+        """The combine op's operands for a step: the taps' rows (:meth:`_base_rows`; the style layer weights ride in their
+        scales, so the style score is ``sum_l w_l * loss_l``), then one ``KIND_EXTRA`` row per entry of :meth:`extra_terms`.
+        The plain step gets the engine's own table, scale and losses; every other combination a losses vector of its own
+        (the engine's keeps the unweighted terms ``forward()`` returns), one head per ``(tv_w, lap_w, layer_w)`` in a cache
+        of 16, oldest out."""
+        terms = self.extra_terms(tv_w, lap_w)
+        if not terms and layer_w is None:
+            return _Head(self.table, self.scale, self.losses, None, None)
+        key = (tv_w, lap_w, layer_w)
+        head = self._heads.get(key)
+        if head is None:
+            if len(self._heads) >= 16:
+                self._heads.pop(next(iter(self._heads)))
+            rows, scale = self._base_rows(layer_w)
+            tv = [len(rows) + i for i, t in enumerate(terms) if t.kind == "tv"]
+            lap = [len(rows) + i for i, t in enumerate(terms) if t.kind == "lap"]
+            table, losses = self.table, torch.zeros_like(self.losses)
+            if terms:
+                table = torch.tensor(rows + [[t.off, t.cnt, _lib.KIND_EXTRA] for t in terms], dtype=torch.int32, device=self.device)
+                losses = torch.zeros(table.shape[0], device=self.device, dtype=torch.float32)
+            scale = torch.tensor(scale + [t.scale for t in terms], dtype=torch.float32, device=self.device)
+            head = self._heads[key] = _Head(table, scale, losses, tv[0] if tv else None, slice(lap[0], lap[-1] + 1) if lap else None)
+        return head
 
     def _combine_op(self, style_w: float, content_w: float, score_log: tuple | None = None, tv_w: float = 0.0,
                     layer_w: tuple | None = None, lap_w: float = 0.0):
         """``score_log`` = (ring fp32 [3, capacity], device counter int32 [1][, host-visible record count int32 [1]]):
         the combine kernel also appends the three scores to the caller's history ring (stv_loss_combine_log).
-        ``tv_w`` > 0: the table with the total-variation row (:meth:`tv_head`); ``layer_w``: the scale rows that carry the
-        style layer weights (:meth:`layer_head`); ``lap_w`` > 0: the table with the Laplacian rows (:meth:`lap_head`)."""
+        ``tv_w``, ``lap_w``, ``layer_w``: the step's :meth:`head`."""
         ring, count, seq = (tuple(score_log) + (None,))[:3] if score_log is not None else (None, None, None)
-        if lap_w:
-            table, scale, losses = self.lap_head(tv_w, lap_w, layer_w)
-        elif tv_w:
-            table, scale, losses = self.tv_head(tv_w, layer_w)
-        elif layer_w is not None:
-            table, scale, losses = self.layer_head(layer_w)
-        else:
-            table, scale, losses = self.table, self.scale, self.losses
-        return self.sched.emit(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=table, p2=scale, p3=seq,
-                               q0=losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
-                               cin=table.shape[0], f0=style_w, f1=content_w)
+        head = self.head(tv_w, lap_w, layer_w)
+        return self.sched.emit(op=plan.OP_LOSS_COMBINE, p0=self.parts, p1=head.table, p2=head.scale, p3=seq,
+                               q0=head.losses, q1=self.scores, q2=ring, q3=count, n=ring.shape[1] if ring is not None else 0,
+                               cin=head.table.shape[0], f0=style_w, f1=content_w)
 
     def _program(self, key: tuple, builder) -> plan.Program:
         prog = self._programs.get(key)
@@ -788,7 +790,7 @@ class _Engine:
         # The entry keeps the source tensor alive and is only reused for that very tensor object: a key of
         # (address, version) alone can be recycled by the caching allocator for a NEW target tensor once the
         # old one is freed, and the stale converted copy would be returned.
-        cache = self.__dict__.setdefault("_target_cache", {})
+        cache = self._target_cache
         key = (t.data_ptr(), t._version, tuple(t.shape), t.dtype)
         hit = cache.get(key)
         if hit is None or hit[0] is not t:
@@ -812,16 +814,14 @@ class _Engine:
                       layer_w: tuple | None = None, lap_w: float = 0.0) -> None:
         """``then_step`` (an ``optimizers.StepRequest`` for ``x``): the L-BFGS update of ``x`` from ``grad`` is the
         schedule's last op - closure and update are one launch (one hipGraph).
-        ``tv_w`` > 0 adds ``tv_w * TV(x)`` to the total and its gradient to ``grad`` in two launches of ``stv_tv``: the
-        loss partials at the head of the forward half (the combine op, and through ``scores[2]`` the multi-iteration
-        L-BFGS op and the logging ring, need the term before the backward half), the gradient accumulated right behind
-        the first-layer dgrad, which WRITES ``grad``.  ``tv_w`` = 0: the step as it always was, under the same key.
+        ``tv_w`` > 0 adds ``tv_w * TV(x)``, ``lap_w`` > 0 (an engine with ``lap_pools``) ``lap_w * sum_p lap_p(x)`` to the total
+        and their gradients to ``grad``, in two launches per entry of :meth:`extra_terms` (``stv_tv``, ``stv_lap``): the loss
+        forms at the head of the forward half (the combine op, and through ``scores[2]`` the multi-iteration L-BFGS op and
+        the logging ring, need the terms before the backward half), the accumulate forms right behind the first-layer
+        dgrad, which WRITES ``grad``, in front of the L-BFGS op.  Weight 0: the step as it always was, under the same key.
         ``layer_w`` (one weight per style tap, in tap order, not all 1.0): the same op list with ``style_w * layer_w[l]`` as
         tap ``l``'s seed coefficient and ``layer_w[l] / (C*C)`` as its combine scale; the tuple is part of the key.
-        ``None``: the step as it always was, under the same key.
-        ``lap_w`` > 0 (an engine with ``lap_pools``) adds ``lap_w * sum_p lap_p(x)`` and its gradient in two launches of
-        ``stv_lap`` per pool: the LOSS forms at the head of the forward half behind TV's, the GRAD forms behind the
-        first-layer dgrad and TV's accumulate op, in front of the L-BFGS op.  ``lap_w`` = 0: same ops, same key."""
+        ``None``: the step as it always was, under the same key."""
         if layer_w is not None and len(layer_w) != self.n_style:
             msg = f"{len(layer_w)} style layer weights for {self.n_style} style taps"
             raise ValueError(msg)
@@ -834,11 +834,7 @@ class _Engine:
         self.generation += 1
         key = ("fused", x.data_ptr(), grad.data_ptr(), style_w, content_w,
                None if score_log is None else (tuple(t.data_ptr() for t in score_log), tuple(score_log[0].shape)),
-               None if then_step is None else then_step.key()) + ((("tv", tv_w),) if tv_w else ()) + (
-                   (("layer_w", layer_w),) if layer_w is not None else ()) + (
-                   (("lap", lap_w, self.lap_pools),) if lap_w else ()) + (
-                   (("pooling", self.pooling),) if self.pooling != "max" else ()) + (
-                   (self.guide.key(),) if self.guide is not None else ())
+               None if then_step is None else then_step.key()) + self._options_key(tv_w, layer_w, lap_w)
 
         def build():
             s = self.sched
@@ -857,17 +853,20 @@ class _Engine:
                 tail.append(s.emit(**kw))
             fwd = self._forward_with_losses(x, style_coef=style_w, with_seed=True, content_coef=content_w, layer_w=layer_w)
             bwd = s.backward_ops(grad, content_coef=content_w, coef_dev=None, prewritten=fused_content)
-            if tv_w:
-                fwd.insert(0, self._tv_op(x, loss=True))
-                k = max(i for i, o in enumerate(bwd) if o.op == plan.OP_CONV_FIRST_DGRAD)
-                bwd.insert(k + 1, self._tv_op(x, grad=grad, tv_w=tv_w))
-            if lap_w:
-                at = 1 if tv_w else 0
-                fwd[at:at] = self._lap_ops(x)
-                k = max(i for i, o in enumerate(bwd) if o.op == plan.OP_CONV_FIRST_DGRAD) + (2 if tv_w else 1)
-                bwd[k:k] = self._lap_ops(x, grad=grad, lap_w=lap_w)
+            terms = self.extra_terms(tv_w, lap_w)
+            if terms:      # loss forms at the head of the forward half; accumulate forms behind the dgrad that WRITES grad
+                fwd[:0] = [t.loss_op(x) for t in terms]
+                k = max(i for i, o in enumerate(bwd) if o.op == plan.OP_CONV_FIRST_DGRAD) + 1
+                bwd[k:k] = [t.grad_op(x, grad) for t in terms]
             return fwd + [self._combine_op(style_w, content_w, score_log, tv_w, layer_w, lap_w)] + bwd + tail
         self._program(key, build).run(self.use_graph)
+
+    def _options_key(self, tv_w: float, layer_w: tuple | None, lap_w: float) -> tuple:
+        """The optional parts of a step's program key, each present only with its option on: none, the key as it always was."""
+        parts = (("tv", tv_w) if tv_w else None, ("layer_w", layer_w) if layer_w is not None else None,
+                 ("lap", lap_w, self.lap_pools) if lap_w else None, ("pooling", self.pooling) if self.pooling != "max" else None,
+                 self.guide.key() if self.guide is not None else None)
+        return tuple(p for p in parts if p is not None)
 
     def region_losses(self) -> torch.Tensor:
         """The unweighted terms ``loss_{l,r}`` of the last evaluation, ``[L, Ra]``: one more launch of the combine kernel
@@ -978,6 +977,11 @@ class StyleContentModel(nn.Module):
         self._dtype = resolve_precision(precision)
         self._split = resolve_split(precision)       # bf16x3: fp32 storage (self._dtype), split-bf16 products
         self._engines: dict = {}
+        # what the last loss_and_grad() left: its engine, the gradient buffer and the views of its extra terms
+        self._last_engine: _Engine | None = None
+        self._grad_buf: torch.Tensor | None = None
+        self._tv_term: torch.Tensor | None = None
+        self._lap_terms: torch.Tensor | None = None
 
     # -- style layer weights -----------------------------------------------------
     @property
@@ -1016,7 +1020,7 @@ class StyleContentModel(nn.Module):
     def last_region_losses(self) -> torch.Tensor:
         """The unweighted guided style terms ``loss_{l,r}`` of the last ``loss_and_grad``, ``[L, Ra]`` (layers sorted, active
         regions in ascending order)."""
-        eng = getattr(self, "_last_engine", None)
+        eng = self._last_engine
         if eng is None or eng.guide is None:
             msg = "last_region_losses() needs a guided model (guide_regions > 0) and an evaluation by loss_and_grad()"
             raise RuntimeError(msg)
@@ -1187,7 +1191,7 @@ class StyleContentModel(nn.Module):
         if x.dtype != torch.float32 or not x.is_contiguous():
             msg = "loss_and_grad needs a contiguous float32 image"
             raise RuntimeError(msg)
-        grad = getattr(self, "_grad_buf", None)
+        grad = self._grad_buf
         if grad is None or grad.shape != x.shape or grad.device != x.device:
             grad = torch.zeros_like(x, requires_grad=False)
             self._grad_buf = grad
@@ -1197,14 +1201,9 @@ class StyleContentModel(nn.Module):
                           then_step=optimizers.claim_step(x), tv_w=tv_w, layer_w=self._tap_weights,
                           **({"lap_w": lap_w} if lap_w else {}))
         self._last_engine = eng
-        n_terms = eng.n_style_rows + eng.n_content
-        if lap_w:
-            losses = eng.lap_head(tv_w, lap_w, self._tap_weights)[2]
-            self._tv_term = losses[n_terms] if tv_w else None
-            self._lap_terms = losses[n_terms + (1 if tv_w else 0):]
-        else:
-            self._tv_term = eng.tv_head(tv_w, self._tap_weights)[2][n_terms] if tv_w else None
-            self._lap_terms = None
+        head = eng.head(tv_w, lap_w, self._tap_weights)       # (the one the step's combine op wrote)
+        self._tv_term = None if head.tv is None else head.losses[head.tv]
+        self._lap_terms = None if head.lap is None else head.losses[head.lap]
         x.grad = grad
         scores = eng.scores if live_scores else eng.scores.clone()
         return scores[0], scores[1], scores[2]
@@ -1212,13 +1211,13 @@ class StyleContentModel(nn.Module):
     def last_tv_term(self) -> torch.Tensor | None:
         """``tv_w * TV(x)`` of the last ``loss_and_grad`` as a 0-d device view (valid until the next evaluation with
         that weight), or ``None`` when that evaluation ran with ``tv_w == 0``."""
-        return getattr(self, "_tv_term", None)
+        return self._tv_term
 
     def last_lap_terms(self) -> torch.Tensor | None:
         """The weighted Laplacian terms ``lap_w * lap_p(x)`` of the last ``loss_and_grad``, one per pool size in the order of
         ``lap_pools``, as a 1-d device view (valid until the next evaluation with those weights), or ``None`` when that
         evaluation ran with ``lap_w == 0``."""
-        return getattr(self, "_lap_terms", None)
+        return self._lap_terms
 
 
 def lap_option_kwargs(optimization) -> dict:

@@ -135,36 +135,29 @@ class _StripLossHead:
             self.parts2[self._content_slot:self._content_slot + n_c].copy_(self.flat[n_r:n_r + n_c])
 
 
-def _refuse_layer_weights(style_layer_weights) -> None:
-    """Style layer weights other than all ones are refused here, as ``tv_w > 0`` is (blended targets need nothing: the
-    strips take ``style_targets`` as they are)."""
+def _refuse_options(layers, tv_w: float, style_layer_weights, lap_w: float, guide_regions: int) -> None:
+    """What the row-strip path does not build, refused by both kinds of strip before anything is allocated: style layer
+    weights other than all ones (blended targets need nothing: the strips take ``style_targets`` as they are), the Laplacian
+    loss, spatial guidance (masks), average pooling (a stack with ``AvgPool2d`` modules) and the total-variation term."""
     if not style_mix.is_trivial(style_layer_weights):
         msg = (f"style layer weights {list(style_layer_weights)} are not available on the row-strip path: its combine scales "
                "and seed coefficients are one per kind; use weights of 1 here, or a whole image")
         raise ValueError(msg)
-
-
-def _refuse_lap(lap_w: float) -> None:
-    """The Laplacian loss is refused here as ``tv_w > 0`` is."""
     if lap_w:
         msg = ("the Laplacian loss (lap_w > 0) is not available on the row-strip path: its pooled cells and differences across "
                "strip borders and the all-reduced terms are not implemented; use lap_w = 0 here, or a whole image")
         raise ValueError(msg)
-
-
-def _refuse_avgpool(layers) -> None:
-    """Average pooling (``pooling = "avg"``: a stack with ``AvgPool2d`` modules) is refused here as ``tv_w > 0`` is."""
+    if guide_regions:
+        msg = (f"spatial guidance (guide_regions = {guide_regions}, masks) is not available on the row-strip path: the label maps, "
+               "slabs and region counts of a strip and the all-reduced region Grams are not implemented; run the whole image")
+        raise ValueError(msg)
     if any(isinstance(layer, nn.AvgPool2d) for layer in layers):
         msg = ("average pooling (pooling = 'avg') is not available on the row-strip path: the strips' pooling ops are the max-pool "
                "kernels on their own rows; use pooling = 'max' here, or a whole image")
         raise ValueError(msg)
-
-
-def _refuse_guidance(guide_regions: int) -> None:
-    """Spatial guidance (masks) is refused here as ``tv_w > 0`` is."""
-    if guide_regions:
-        msg = (f"spatial guidance (guide_regions = {guide_regions}, masks) is not available on the row-strip path: the label maps, "
-               "slabs and region counts of a strip and the all-reduced region Grams are not implemented; run the whole image")
+    if tv_w:
+        msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
+               "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
         raise ValueError(msg)
 
 
@@ -175,14 +168,7 @@ class SpatialShard:
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
                  style_w: float, content_w: float, tv_w: float = 0.0,
                  style_layer_weights: list[float] | None = None, lap_w: float = 0.0, guide_regions: int = 0) -> None:
-        _refuse_layer_weights(style_layer_weights)
-        _refuse_lap(lap_w)
-        _refuse_guidance(guide_regions)
-        _refuse_avgpool(layers)
-        if tv_w:
-            msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
-                   "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
-            raise ValueError(msg)
+        _refuse_options(layers, tv_w, style_layer_weights, lap_w, guide_regions)
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         dev = content_img.device
@@ -291,14 +277,7 @@ class HaloShard:
                  content_img: torch.Tensor, style_targets: list[torch.Tensor], *, dtype: torch.dtype,
                  style_w: float, content_w: float, group=None, split: bool = False, tv_w: float = 0.0,
                  style_layer_weights: list[float] | None = None, lap_w: float = 0.0, guide_regions: int = 0) -> None:
-        _refuse_layer_weights(style_layer_weights)
-        _refuse_lap(lap_w)
-        _refuse_guidance(guide_regions)
-        _refuse_avgpool(layers)
-        if tv_w:
-            msg = ("the total-variation term (tv_w > 0) is not available on the row-strip path: its differences across "
-                   "strip borders and the all-reduced term are not implemented; use tv_w = 0 here, or a whole image")
-            raise ValueError(msg)
+        _refuse_options(layers, tv_w, style_layer_weights, lap_w, guide_regions)
         if split:
             msg = ("bf16x3 (split-bf16 products) is not available on the row-strip path: use precision fp32 or "
                    "bf16 with HaloShard, or bf16x3 on a whole image")

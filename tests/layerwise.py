@@ -309,14 +309,7 @@ class _Checker:
     # -- the step's own combine head and coefficients
     def head(self) -> tuple:
         """(table, scale, losses) of the combine op this step ran (``_Engine._combine_op``'s choice)."""
-        eng = self.eng
-        if self.lap_w:
-            return eng.lap_head(self.tv_w, self.lap_w, self.layer_w)
-        if self.tv_w:
-            return eng.tv_head(self.tv_w, self.layer_w)
-        if self.layer_w is not None:
-            return eng.layer_head(self.layer_w)
-        return eng.table, eng.scale, eng.losses
+        return self.eng.head(self.tv_w, self.lap_w, self.layer_w)
 
     def weights_of(self, chain) -> tuple[float, float]:
         """(w_l, lambda_r) of a Gram chain's tap."""

@@ -194,7 +194,7 @@ def test_layer_weight_identities(precision, monkeypatch):
     model.style_layer_weights = [1.0] * 5
     ones = _eval(model, x, sw, cw)
     assert all(torch.equal(p, q) for p, q in zip(ones, base, strict=True))
-    assert len(eng._programs) == n_programs and not eng._layer_heads
+    assert len(eng._programs) == n_programs and not eng._heads
     # all 2.0 with style_w / 2: power-of-two scalings are exact
     model.style_layer_weights = [2.0] * 5
     s2, c2, t2, g2 = _eval(model, x, sw / 2, cw)

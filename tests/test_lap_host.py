@@ -201,7 +201,7 @@ def test_op_lists_with_and_without_the_term(monkeypatch, dtype, H, W):
     combine = next(o for o in zero if o.op == _lib.OP_LOSS_COMBINE)
     assert combine.cin == 6 and combine.refs["p1"] is eng.table and combine.refs["p2"] is eng.scale and combine.refs["q0"] is eng.losses
     key_tv0, tv_only = _step(eng, x, grad, tv_w=0.5)
-    assert next(o for o in tv_only if o.op == _lib.OP_LOSS_COMBINE).refs["p1"] is eng.tv_head(0.5)[0]
+    assert next(o for o in tv_only if o.op == _lib.OP_LOSS_COMBINE).refs["p1"] is eng.head(0.5)[0]
     assert not any("lap" in str(k) for k in key_tv0)
 
     for tv_w in (0.0, 0.5):
@@ -248,13 +248,13 @@ def test_op_lists_with_and_without_the_term(monkeypatch, dtype, H, W):
             assert table[n0 + k].tolist() == [eng.lap_parts_off + k * _lib.LAP_LOSS_PARTS, _lib.LAP_LOSS_PARTS, 2]
             assert float(scale[n0 + k]) == _fp32(0.25 / (3 * (H // p) * (W // p))) == core_model.lap_scale(0.25, 3, H // p, W // p)
         assert not (eng.table[:, 2] == 2).any()
-        # the head is cached per (tv_w, lap_w, layer_w); another weight gets its own; tv_head is what it was
+        # the head is cached per (tv_w, lap_w, layer_w); another weight gets its own; the head of tv_w alone is what it was
         _, again = _step(eng, x, torch.zeros(1, 3, H, W), lap_w=0.25, tv_w=tv_w)
         assert next(o for o in again if o.op == _lib.OP_LOSS_COMBINE).refs["p1"] is table
         _, other = _step(eng, x, grad, lap_w=0.125, tv_w=tv_w)
         assert next(o for o in other if o.op == _lib.OP_LOSS_COMBINE).refs["p1"] is not table
-        assert eng.lap_head(tv_w, 0.25)[0] is table
-    assert eng.tv_head(0.5)[0].shape == (7, 3)
+        assert eng.head(tv_w, 0.25)[0] is table
+    assert eng.head(0.5)[0].shape == (7, 3)
 
 
 def test_head_with_layer_weights(monkeypatch):
@@ -266,9 +266,63 @@ def test_head_with_layer_weights(monkeypatch):
     assert key[-3:] == (("tv", 0.5), ("layer_w", lw), ("lap", 2.0, (8,)))
     combine = next(o for o in ops_ if o.op == _lib.OP_LOSS_COMBINE)
     table, scale = combine.refs["p1"], combine.refs["p2"]
-    assert table.shape == (8, 3) and torch.equal(scale[:7], eng.tv_head(0.5, lw)[1])
+    assert table.shape == (8, 3) and torch.equal(scale[:7], eng.head(0.5, layer_w=lw)[1])
     assert table[7].tolist() == [eng.lap_parts_off, _lib.LAP_LOSS_PARTS, 2]
-    assert eng.lap_head(0.5, 2.0, lw)[0] is table and eng.lap_head(0.5, 2.0)[0] is not table
+    assert eng.head(0.5, 2.0, lw)[0] is table and eng.head(0.5, 2.0)[0] is not table
+
+
+@pytest.mark.parametrize("layer_w", [None, (1.0, 0.8, 0.5, 0.0, 0.1)], ids=["unweighted", "weighted"])
+@pytest.mark.parametrize("lap_w", [0.0, 0.25])
+@pytest.mark.parametrize("tv_w", [0.0, 0.5])
+def test_the_one_head_of_every_combination(monkeypatch, tv_w, lap_w, layer_w):
+    """The table is the base rows, then the TV row, then the pool rows; the slots the head names are exactly those rows; the
+    all-off combination is the engine's own three objects."""
+    H = W = 64
+    pools = (4, 16)
+    eng = _host_engine(monkeypatch, torch.bfloat16, H, W, lap_pools=pools)
+    head = eng.head(tv_w, lap_w, layer_w)
+    if not tv_w and not lap_w and layer_w is None:
+        assert head.table is eng.table and head.scale is eng.scale and head.losses is eng.losses
+        assert head.tv is None and head.lap is None and not eng._heads
+        return
+    assert eng.head(tv_w, lap_w, layer_w) is head and list(eng._heads) == [(tv_w, lap_w, layer_w)]
+    assert head.losses is not eng.losses and not head.losses.any()
+    # base rows: the engine's, with the layer weights in the Gram chains' scales and 1 / numel for the content tap
+    want_rows = eng.table.tolist()
+    want_scale = [_fp32((1.0 if layer_w is None else layer_w[t.order]) / float(t.buf.C * t.buf.C)) for t in eng.sched.style_taps]
+    want_scale += [_fp32(1.0 / float(t.buf.act.numel())) for t in eng.sched.content_taps]
+    assert len(want_rows) == 6
+    if layer_w is None:
+        assert want_scale == eng.scale.tolist()
+    # then the TV row, then one row per pool, each of kind 2 with the weight in its scale
+    want_tv, want_lap = None, None
+    if tv_w:
+        want_tv = len(want_rows)
+        want_rows.append([eng.tv_parts_off, _lib.TV_LOSS_PARTS, _lib.KIND_EXTRA])
+        want_scale.append(core_model.tv_scale(tv_w, 3, H, W))
+    if lap_w:
+        want_lap = slice(len(want_rows), len(want_rows) + len(pools))
+        for k, p in enumerate(pools):
+            want_rows.append([eng.lap_parts_off + k * _lib.LAP_LOSS_PARTS, _lib.LAP_LOSS_PARTS, _lib.KIND_EXTRA])
+            want_scale.append(core_model.lap_scale(lap_w, 3, H // p, W // p))
+    assert head.table.dtype == torch.int32 and head.table.tolist() == want_rows
+    assert head.scale.dtype == torch.float32 and head.scale.tolist() == want_scale
+    assert (head.table is eng.table) == (not tv_w and not lap_w)
+    assert head.losses.shape == (len(want_rows),) and head.losses.dtype == torch.float32
+    assert head.tv == want_tv and head.lap == want_lap
+    # the named slots, read as the model reads them, are views of exactly those rows' losses
+    head.losses.copy_(torch.arange(len(want_rows), dtype=torch.float32))
+    if tv_w:
+        assert head.table[head.tv].tolist() == [eng.tv_parts_off, _lib.TV_LOSS_PARTS, 2] and float(head.losses[head.tv]) == 6.0
+    if lap_w:
+        assert head.table[head.lap, 0].tolist() == [eng.lap_parts_off + k * _lib.LAP_LOSS_PARTS for k in range(len(pools))]
+        assert head.losses[head.lap].tolist() == [float(want_lap.start + k) for k in range(len(pools))]
+        assert head.losses[head.lap].data_ptr() == head.losses[want_lap.start:].data_ptr()
+    # the entries of the term list are those rows, in that order
+    terms = eng.extra_terms(tv_w, lap_w)
+    assert [t.kind for t in terms] == (["tv"] if tv_w else []) + (["lap"] * len(pools) if lap_w else [])
+    assert [[t.off, t.cnt, _lib.KIND_EXTRA] for t in terms] == want_rows[6:]
+    assert [_fp32(t.scale) for t in terms] == want_scale[6:]
 
 
 def test_the_update_op_follows_the_accumulate_ops(monkeypatch):

@@ -275,11 +275,11 @@ def test_op_lists_with_and_without_layer_weights(monkeypatch, dtype, H, W):
     x, grad = torch.zeros(1, 3, H, W), torch.zeros(1, 3, H, W)
     eng = _host_engine(monkeypatch, dtype, H, W)
     key_none, plain = _step(eng, x, grad)
-    assert not any("layer_w" in str(part) for part in key_none) and not eng._layer_heads
+    assert not any("layer_w" in str(part) for part in key_none) and not eng._heads
     # all ones reach the engine as None (style_mix.tap_weights): the same key, hence the same program
     assert style_mix.tap_weights([1.0] * 5, [0, 5, 10, 19, 28]) is None
     eng.loss_and_grad(x, grad, STYLE_W, 1.0, layer_w=style_mix.tap_weights([1, 1, 1, 1, 1], [0, 5, 10, 19, 28]))
-    assert set(eng._programs) == {key_none} and not eng._layer_heads
+    assert set(eng._programs) == {key_none} and not eng._heads
 
     lw = (1.0, 0.5, 0.3, 2.0, 0.0)
     key_w, weighted = _step(eng, x, grad, layer_w=lw)
@@ -315,7 +315,7 @@ def test_op_lists_with_and_without_layer_weights(monkeypatch, dtype, H, W):
     key_tv, with_tv = _step(eng, x, grad, layer_w=lw, tv_w=0.5)
     assert ("tv", 0.5) in key_tv and ("layer_w", lw) in key_tv
     c_tv = next(o for o in with_tv if o.op == _lib.OP_LOSS_COMBINE)
-    assert c_tv.cin == 7 and torch.equal(c_tv.refs["p2"][:6], scale) and torch.equal(c_tv.refs["p2"][6:], eng.tv_head(0.5)[1][6:])
+    assert c_tv.cin == 7 and torch.equal(c_tv.refs["p2"][:6], scale) and torch.equal(c_tv.refs["p2"][6:], eng.head(0.5)[1][6:])
     with pytest.raises(ValueError, match="2 style layer weights for 5 style taps"):
         eng.loss_and_grad(x, grad, STYLE_W, 1.0, layer_w=(1.0, 2.0))
     # the forward-only program (forward()) never carries weights
@@ -327,8 +327,8 @@ def test_op_lists_with_and_without_layer_weights(monkeypatch, dtype, H, W):
 def test_the_cache_of_weighted_heads_is_bounded(monkeypatch):
     eng = _host_engine(monkeypatch, torch.float32, 32, 32)
     for i in range(40):
-        eng.layer_head((1.0, 1.0, 1.0, 1.0, float(i + 2)))
-    assert len(eng._layer_heads) <= 16
+        eng.head(layer_w=(1.0, 1.0, 1.0, 1.0, float(i + 2)))
+    assert len(eng._heads) <= 16
 
 
 @pytest.mark.parametrize("cls", [spatial.HaloShard, spatial.SpatialShard])
